@@ -9,11 +9,15 @@ ResNet-50, 256x192 crops, 17 key-points, a 1024-frame synthetic video per GPU
 Inputs are resident in HBM before the timed region.  Random-init weights of the
 named architecture, synthetic crops (no dataset / checkpoint on the box).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-extra] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-extra] [--no-cpu-baseline] [--dump-outputs DIR]
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks are given (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_*); run bare, `--gpus N` starts the N ranks itself as fresh child processes before anything
 touches a GPU (never an exec of this process) and relays rank 0's line.  Frames shard across ranks (weak scaling:
 1024 frames per rank), per-item results are all-gathered; there is no other exchange on this path.
+
+`--dump-outputs DIR` writes, after the timed steps, what rank 0's last timed step returned (key-points, arg-max indices, HP,
+pose score, local-peak mean, THC and a fixed, seeded sample of the heat-maps) as DIR/<name>.npy in float32 / float64, so that
+two builds can be compared output for output on the same seeded inputs.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) carrying
 `roofline` (conv implicit-GEMM launches timed with HIP events), at N = 1 `cpu_baseline` (the oracle restatement
@@ -326,7 +330,7 @@ def conv_roofline(model, x, bbox, is_prev, is_next, hm_buf):
 def cpu_baseline():
     """The oracle (CPU restatement of the reference graph + scorers) on the host cores, bounded sample: 32 crops forward + decode / local-peak /
     THC of 32 items.  The thread count is calibrated AT the measured batch (one warm-up + one timed forward of the 32 crops per candidate,
-    candidates up to every core the process may use), the winner is timed three times (median) and the all-cores figure is reported beside it."""
+    candidates up to every core the process may use), the winner and the all-cores count are timed three times each (median), the faster is reported and the all-cores figure beside it."""
     import numpy as np
     from oracle import nets, scorers, synth
     m = nets.SimplePoseRef(50).eval()
@@ -347,16 +351,27 @@ def cpu_baseline():
             calib[th] = time.perf_counter() - t0
             if time.perf_counter() > budget or calib[th] > 2.5 * min(calib.values()):
                 break                                              # out of time, or far past the optimum (fewer threads only get slower from here)
+
+    def median_fwd(th):                                            # one warm-up + median of 3 timed forwards at `th` threads
+        torch.set_num_threads(th)
+        ts = []
+        with torch.no_grad():
+            m(x)
+            for _ in range(3):
+                t0 = time.perf_counter()
+                hm = m(x).numpy()
+                ts.append(time.perf_counter() - t0)
+        return sorted(ts)[1], hm
+
+    # The calibration timed each candidate once: the winner and the all-cores count are re-timed the same way (median of 3), and the faster of the two
+    # is reported, so the all-cores figure beside it is never a luckier single sample of the same configuration.
     cores = min(calib, key=calib.get)
-    torch.set_num_threads(cores)
-    ts = []
-    with torch.no_grad():
-        m(x)
-        for _ in range(3):
-            t0 = time.perf_counter()
-            hm = m(x).numpy()
-            ts.append(time.perf_counter() - t0)
-    fwd = sorted(ts)[1]
+    fwd, hm = median_fwd(cores)
+    fwd_all = fwd
+    if cores != avail:                                             # (avail is always a candidate: the loop starts there)
+        fwd_all, hm_all = median_fwd(avail)
+        if fwd_all < fwd:
+            cores, fwd, hm = avail, fwd_all, hm_all
     bb = synth.bboxes(n)
     t0 = time.perf_counter()
     import warnings
@@ -380,7 +395,7 @@ def cpu_baseline():
     return {"value": round(n / (fwd + post), 2), "unit": "frames/s", "cores": cores, "cores_available": avail, "cores_visible": visible, "cgroup_cpu_quota": quota, "cpu_model": cpu_model, "kind": "port",
             "sample": f"{n} crops: SimplePose-R50 forward (torch CPU fp32, {cores} threads = the fastest of {sorted(calib)} timed at this batch, median of 3) + numpy decode/local-peak/THC",
             "forward_s": round(fwd, 3), "scoring_s": round(post, 3),
-            "all_cores": {"cores": avail, "value": round(n / (calib[avail] + post), 2), "forward_s": round(calib[avail], 3)} if avail in calib else None,
+            "all_cores": {"cores": avail, "value": round(n / (fwd_all + post), 2), "forward_s": round(fwd_all, 3)},
             "calibration_forward_s": {str(k): round(v, 3) for k, v in sorted(calib.items())}}
 
 
@@ -702,6 +717,23 @@ def extra_configs(dev, world, rank, dist_on):
     return out
 
 
+DUMP_HEATMAP_FRAMES = 128        # heat-maps written by --dump-outputs: 128 of the 1024 frames (27 MB), picked by a fixed seed
+
+
+def dump_outputs(out_dir, s, hm_buf):
+    """The timed path's results of one step (active_learning.scoring.Scores + the heat-maps it scored) as <name>.npy, float32 / float64 only.
+    The full heat-map tensor (214 MB) is cut to a seeded sample of whole frames, written with the frame indices it holds."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frames = np.sort(np.random.default_rng(166).choice(FRAMES, DUMP_HEATMAP_FRAMES, replace=False))
+    arrays = {"keypoints": s.keypoints, "argmax": s.argmax.to(torch.float64), "hp": s.hp, "pose_score": s.pose_score, "localpeak": s.localpeak,
+              "thc": s.thc, "heatmaps_sample": hm_buf[torch.from_numpy(frames).to(hm_buf.device)], "heatmaps_sample_frames": torch.from_numpy(frames).double()}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # launch
 # ---------------------------------------------------------------------------------------------------------------------
@@ -755,7 +787,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the configs[2..4] measurements (headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus))
@@ -805,7 +840,7 @@ def main():
         clock.__enter__()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist:
         td.barrier()
@@ -816,6 +851,8 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         td.all_reduce(t, op=td.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:                    # before anything else reuses hm_buf
+        dump_outputs(a.dump_outputs, last, hm_buf)
 
     roof = conv_roofline(model, x, bbox, is_prev, is_next, hm_buf) if rank == 0 else None
     if roof is not None:

@@ -62,3 +62,33 @@ def test_clock_sampler_and_granted_cpus_read_what_the_box_offers(tmp_path, monke
     assert s["sclk_samples"] >= 10 and 2100.0 <= s["sclk_mhz_min"] <= s["sclk_mhz_mean"] <= s["sclk_mhz_max"] == 2300.0 and s["power_w_mean"] == 1250.0
     late = c.summary(t0=c.t0 + 0.06, t1=c.t1)
     assert late["sclk_mhz_min"] == 2300.0
+
+
+def test_dump_outputs_writes_float_arrays_of_one_step_within_64_mb(tmp_path):
+    """bench.dump_outputs on CPU tensors shaped like one headline step: every Scores field the timed path returns plus the seeded heat-map
+    sample, float32 / float64 only, under 64 MB, the same frames every time; --steps below 1 is refused before anything runs."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from active_learning.scoring import Scores
+    n = bench.FRAMES
+    g = torch.Generator().manual_seed(0)
+    hm = torch.rand((n, 17, 64, 48), generator=g)
+    s = Scores(keypoints=torch.rand((n, 17, 3), generator=g), argmax=torch.randint(0, 64 * 48, (n, 17), dtype=torch.int32, generator=g),
+               hp=torch.rand(n, generator=g), pose_score=torch.rand(n, generator=g, dtype=torch.float64), localpeak=torch.rand(n, generator=g),
+               thc=torch.rand(n, generator=g))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), s, hm)
+    names = {"keypoints", "argmax", "hp", "pose_score", "localpeak", "thc", "heatmaps_sample", "heatmaps_sample_frames"}
+    assert {f[:-4] for f in os.listdir(tmp_path / "a")} == names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    out = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["pose_score"].dtype == np.float64 and np.array_equal(out["argmax"], s.argmax.numpy())
+    frames = out["heatmaps_sample_frames"].astype(np.int64)
+    assert len(frames) == bench.DUMP_HEATMAP_FRAMES and np.all(np.diff(frames) > 0) and np.array_equal(out["heatmaps_sample"], hm.numpy()[frames])
+    for k in names:
+        assert np.array_equal(out[k], np.load(tmp_path / "b" / f"{k}.npy"))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr

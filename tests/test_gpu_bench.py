@@ -104,3 +104,29 @@ def test_bench_gpus_flag_starts_its_own_ranks():
         assert 0.0 <= ex[k]["overlap_hidden_frac"] <= 1.0 and ex[k]["step_without_allreduce_ms"] > 0
         assert abs(ex[k]["crops_per_s"] - 2 * ex[k]["batch_per_gpu"] * 1000.0 / ex[k]["ms_per_step"]) / ex[k]["crops_per_s"] < 0.01
     assert ex["cfg4_hrnet_w32_thc_wpu"]["halo_frames"] == 1                              # rank 0 of 2: one interior edge
+
+
+def test_bench_dump_outputs_repeats_across_runs(tmp_path):
+    """--dump-outputs DIR: the last timed step's results as float .npy files under 64 MB, `steps` / `ms_per_step` as asked, and the same seeded
+    inputs in every run — two runs with different step counts write the same outputs; the dumped arg-max indices point at each sampled plane's maximum."""
+    import numpy as np
+    outs = {}
+    for steps in (1, 3):
+        d = tmp_path / f"s{steps}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--no-extra", "--no-cpu-baseline",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == steps and abs(line["ms_per_step"] - 1024 * 1000.0 / line["value"]) / line["ms_per_step"] < 0.01
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        outs[steps] = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    a, b = outs[1], outs[3]
+    assert set(a) == {"keypoints", "argmax", "hp", "pose_score", "localpeak", "thc", "heatmaps_sample", "heatmaps_sample_frames"} == set(b)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape and not np.isinf(a[k]).any(), k
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-6, equal_nan=True, err_msg=k)
+    assert a["keypoints"].shape == (1024, 17, 3) and a["heatmaps_sample"].shape[1:] == (17, 64, 48)
+    frames = a["heatmaps_sample_frames"].astype(np.int64)
+    planes = a["heatmaps_sample"].reshape(len(frames), 17, -1)
+    at = np.take_along_axis(planes, a["argmax"][frames].astype(np.int64)[..., None], 2)[..., 0]
+    assert np.array_equal(at, planes.max(2))
