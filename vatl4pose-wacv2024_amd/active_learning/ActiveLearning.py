@@ -76,7 +76,14 @@ def _collective(fn):
 
 class ActiveLearning:
     def __init__(self, cfg, opt, eval_dataset=None, train_dataset=None):
+        from . import distributed as D
+        from .driver_paths import derive_video_paths
+        if eval_dataset is None and train_dataset is None and not D.spawned_worker():
+            # the driver's yaml leaves IMG_PREFIX / ANN to the constructor (ActiveLearning.py:67-94); derived here, before the
+            # ('new', ...) broadcast below, so that worker ranks receive the derived config and read no file of their own
+            derive_video_paths(cfg, opt)
         self.cfg, self.opt = cfg, opt
+        self.dataset = cfg.DATASET.EVAL.TYPE
         self.round_cnt = 0
         self.uncertainty = getattr(opt, "uncertainty", "None")
         self.representativeness = getattr(opt, "representativeness", "None")
@@ -95,7 +102,6 @@ class ActiveLearning:
         self.unc_lambda = float(cfg.VAL.get("UNC_LAMBDA", 1.0))
         self.finish_margin = 0.05
         # one process per GPU: join the torchrun group, or (plain single process, opt.num_gpu > 1) start the worker ranks
-        from . import distributed as D
         self._depth = 0
         ngpu = max(1, int(getattr(opt, "num_gpu", 1)))
         world = D.ensure_workers(ngpu)
@@ -219,11 +225,21 @@ class ActiveLearning:
         return model, optimizer, scheduler
 
     def initialize_AE(self):
+        """ActiveLearning.py:886-903: the WPU auto-encoder from its checkpoint (active_learning/driver_paths.py: AE.PRETRAINED, else
+        AE.PRETRAINED_ROOT/Hybrid/WholeBodyAE_zdim<Z>.pth), or randomly initialised when the config names neither.  Called again before
+        every fine-tune (retrain_model): each round starts from the checkpoint, which is read from disk once per construction."""
         from .Whole_body_AE.AutoEncoder import WholeBodyAE
-        ae = WholeBodyAE(z_dim=self.cfg.AE.Z_DIM, input_dim=int(self.cfg.AE.get("INPUT_DIM", 42)))
-        path = self.cfg.AE.get("PRETRAINED", "")
-        if path:
-            ae.load_state_dict(torch.load(path, map_location="cpu"))
+        from .driver_paths import load_ae_checkpoint, resolve_ae_checkpoint
+        ckpt = self.__dict__.get("_ae_checkpoint")
+        if ckpt is None:
+            path = resolve_ae_checkpoint(self.cfg)
+            ckpt = self.__dict__["_ae_checkpoint"] = (path, *load_ae_checkpoint(path, self.cfg)) if path else (None, None, None, None)
+        path, sd, input_dim, z_dim = ckpt
+        if sd is None:
+            ae = WholeBodyAE(z_dim=self.cfg.AE.Z_DIM, input_dim=int(self.cfg.AE.get("INPUT_DIM", 42)))
+        else:
+            ae = WholeBodyAE(z_dim=z_dim, input_dim=input_dim)
+            ae.load_state_dict(sd, strict=True)
         ae = ae.to(self.device).eval()
         from . import distributed as D
         D.broadcast_module_(ae)
@@ -310,7 +326,9 @@ class ActiveLearning:
             ann_all[loc] = bbox_xyxy_to_xywh(bboxes_ann.numpy().astype(np.float64))
             self._mark(f"batch@{a0}")
         bb_all, ip_all, in_all = (bb_dev if bb_dev is not None else vh.upload(bb_h, self.device)), vh.upload(ip_h, self.device), vh.upload(in_h, self.device)
-        ae_flat = self.AE.packed() if self.AE is not None else None
+        # packed afresh for every evaluation (< 3000 parameters, one cat): WholeBodyAE.packed() trusts the parameters' version counters,
+        # which a write through `.data` does not bump
+        ae_flat = vh.pack_ae(self.AE.state_dict(), self.device) if self.AE is not None else None
         s = score_batch(hm_all, bb_all, ip_all, in_all, thc_norm=thc_norm if self.dedup else None, ae_flat=ae_flat,
                         ae_dims=(self.AE.input_dim, self.AE.z_dim) if self.AE is not None else (42, 4),
                         wpu_only38=(self.unc_kind == "WPU"))
@@ -837,6 +855,10 @@ class ActiveLearning:
             self.AE = self.initialize_AE()
             self.last_ae_loss = self.retrain_AE()
             D.broadcast_module_(self.AE)           # the fit shuffles with the rank's own RNG: rank 0's AE is the one every shard scores with
+            work_dir = getattr(self.opt, "work_dir", None)
+            if work_dir and D.is_main():           # :685, the reference's keys (encoder.{0,2,4,6}.*, decoder.{0,2,4,6}.*) as CPU tensors
+                os.makedirs(work_dir, exist_ok=True)
+                torch.save({k: v.detach().cpu() for k, v in self.AE.state_dict().items()}, os.path.join(work_dir, "latest_AE.pth"))
 
     def _global_avg(self, logger):
         """Item-weighted average of a DataLogger over all ranks (the reference logs the loss of the gathered mini-batch)."""

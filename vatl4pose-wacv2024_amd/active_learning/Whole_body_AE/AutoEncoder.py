@@ -25,7 +25,9 @@ class WholeBodyAE(nn.Module):
                                      nn.Linear(12, 24), nn.ReLU(True), nn.Linear(24, d), nn.Sigmoid())
 
     def packed(self) -> torch.Tensor:
-        """Weights flattened in state-dict order for the C ABI (cached per parameter version)."""
+        """Weights flattened in state-dict order for the C ABI (cached per parameter version).  The cache only sees writes that bump
+        a parameter's version counter (optimizers, ``copy_`` on the parameter, ``load_state_dict``); a write through ``p.data`` does
+        not, and leaves the old pack in place.  ``ActiveLearning`` therefore packs afresh for every evaluation."""
         key = tuple(p._version for p in self.parameters()) + (str(next(self.parameters()).device),)
         c = self.__dict__.get("_vatl_packed")
         if c is None or c[0] != key:

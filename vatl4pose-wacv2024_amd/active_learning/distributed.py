@@ -373,9 +373,14 @@ def release_payloads():
             pass
 
 
+def spawned_worker() -> bool:
+    """This process is a worker rank started by ensure_workers (it builds what rank 0 broadcasts)."""
+    return bool(os.environ.get("VATL_WORKER_PARENT"))
+
+
 def mirrored() -> bool:
     """This process is the driver of worker ranks, or one of those workers (every constructor is mirrored)."""
-    return bool(_workers) or bool(os.environ.get("VATL_WORKER_PARENT"))
+    return bool(_workers) or spawned_worker()
 
 
 def barrier():
