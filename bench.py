@@ -9,7 +9,7 @@ ResNet-50, 256x192 crops, 17 key-points, a 1024-frame synthetic video per GPU
 Inputs are resident in HBM before the timed region.  Random-init weights of the
 named architecture, synthetic crops (no dataset / checkpoint on the box).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-extra] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-extra] [--no-cpu-baseline]]
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks are given (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_*); run bare, `--gpus N` starts the N ranks itself as fresh child processes before anything
 touches a GPU (never an exec of this process) and relays rank 0's line.  Frames shard across ranks (weak scaling:
@@ -19,11 +19,13 @@ touches a GPU (never an exec of this process) and relays rank 0's line.  Frames 
 pose score, local-peak mean, THC and a fixed, seeded sample of the heat-maps) as DIR/<name>.npy in float32 / float64, so that
 two builds can be compared output for output on the same seeded inputs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying
-`roofline` (conv implicit-GEMM launches timed with HIP events), at N = 1 `cpu_baseline` (the oracle restatement
-timed on the host cores, bounded sample), and `extra`: the other BASELINE.json configurations measured in the same
-run — configs[2] SimpleBaseline-R50 fine-tune step (fwd + bwd + AdamW, B = 120 per GPU, gradient arena all-reduced over
-RCCL at N > 1), configs[3] HRNet-W32 inference + THC + WPU on a 1024-frame shard with its halo, configs[4]
+Prints ONE JSON line on rank 0 (contract: tests/test_gpu_bench.py) with the headline: `metric`, `value` (frames/s over all ranks),
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`.  A plain run does only that: set-up, warm-up, the timed steps, `--dump-outputs`, the line.
+`--full` runs the same set-up, warm-up and timed steps and then adds what takes runs of its own: `roofline` (conv implicit-GEMM launches of one
+more step timed with HIP events, the shader clock sampled over the timed steps), at N = 1 `cpu_baseline` (the oracle restatement timed on the
+host cores, bounded sample; `--no-cpu-baseline` skips it), and `extra` (`--no-extra` skips it): the headline variants and the other
+BASELINE.json configurations measured in the same run — configs[2] SimpleBaseline-R50 fine-tune step (fwd + bwd + AdamW, B = 120 per GPU,
+gradient arena all-reduced over RCCL at N > 1), configs[3] HRNet-W32 inference + THC + WPU on a 1024-frame shard with its halo, configs[4]
 FastPose-R152 384x288 fine-tune step (B = 32 per GPU, 301 MB gradient all-reduce at N > 1).
 """
 from __future__ import annotations
@@ -780,17 +782,24 @@ def launch_ranks(n: int) -> int:
     return rc
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[2..4] measurements (headline line only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline pass + sampled shader clock, headline variants + configs[2..4] (`extra`), CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the headline variants and the configs[2..4] measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/<name>.npy (rank 0)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def main():
+    a = parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a.gpus))
@@ -835,7 +844,7 @@ def main():
     if dist:
         td.barrier()
     torch.cuda.synchronize()
-    clock = ClockSampler(local) if rank == 0 else None
+    clock = ClockSampler(local) if (rank == 0 and a.full) else None
     if clock is not None:
         clock.__enter__()
     t0 = time.perf_counter()
@@ -854,7 +863,8 @@ def main():
     if a.dump_outputs and rank == 0:                    # before anything else reuses hm_buf
         dump_outputs(a.dump_outputs, last, hm_buf)
 
-    roof = conv_roofline(model, x, bbox, is_prev, is_next, hm_buf) if rank == 0 else None
+    # --full: the measurements that take runs of their own (a plain run goes straight on to the result line)
+    roof = conv_roofline(model, x, bbox, is_prev, is_next, hm_buf) if (rank == 0 and a.full) else None
     if roof is not None:
         # the whole step (conv + pool + layout + scorers + launch gaps) against the FLOPs its conv launches execute: the step-level roofline fraction
         roof["e2e_frac"] = round(roof["executed_flops_per_step"] * a.steps / dt / 1e12 / PEAK_FP32_MFMA, 4)
@@ -869,7 +879,8 @@ def main():
             roof["peak_at_sclk"] = round(at, 2)
             roof["frac_at_sclk"] = round(roof["achieved"] / at, 4)
             roof["e2e_frac_at_sclk"] = round(roof["executed_flops_per_step"] * a.steps / dt / 1e12 / at, 4)
-    variants = headline_variants(model, x, bbox, is_prev, is_next, hm_buf) if (rank == 0 and not a.no_extra) else None
+    run_extra = a.full and not a.no_extra
+    variants = headline_variants(model, x, bbox, is_prev, is_next, hm_buf) if (rank == 0 and run_extra) else None
     devices = [torch.cuda.get_device_name(dev)]
     if dist:                                            # what actually ran: one entry per rank, gathered (not assumed from --gpus)
         box = [None] * world
@@ -878,7 +889,7 @@ def main():
     del model, x, hm_buf
     torch.cuda.empty_cache()
     extra = None
-    if not a.no_extra:
+    if run_extra:
         if dist:
             td.barrier()
         extra = extra_configs(dev, world, rank, dist)
@@ -889,13 +900,14 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "SimpleBaseline-R50 256x192 inference + decode + local-peak + THC-L1, 1024-frame synthetic video per GPU",
                        "frames_per_gpu": FRAMES, "batch": BATCH, "tracks": TRACKS, "parallelism": f"frame-sharded x{world}"},
-            "roofline": roof,
             "world_size_seen": td.get_world_size() if dist else 1, "rank_devices": devices,
         }
+        if roof is not None:
+            line["roofline"] = roof
         if extra is not None:
             extra["headline_variants"] = variants
             line["extra"] = extra
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist:

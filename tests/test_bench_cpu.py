@@ -1,4 +1,4 @@
-"""bench.py launch logic that needs no GPU: a contradictory rank environment and an impossible --gpus fail loudly."""
+"""bench.py launch logic that needs no GPU: a contradictory rank environment and an impossible --gpus fail loudly; --full is off by default."""
 import os
 import subprocess
 import sys
@@ -92,3 +92,14 @@ def test_dump_outputs_writes_float_arrays_of_one_step_within_64_mb(tmp_path):
         assert np.array_equal(out[k], np.load(tmp_path / "b" / f"{k}.npy"))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_full_measurements_are_off_by_default():
+    """A plain command line runs the headline alone; --full turns on the roofline pass, `extra` and the CPU baseline, which --no-extra /
+    --no-cpu-baseline trim."""
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert not a.full and (a.gpus, a.steps, a.warmup) == (1, 3, 2) and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--no-extra", "--no-cpu-baseline"])
+    assert a.full and a.no_extra and a.no_cpu_baseline and (a.steps, a.warmup) == (20, 3)

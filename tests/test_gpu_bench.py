@@ -1,17 +1,19 @@
-"""bench.py keeps its contract: one JSON line with the metric, the roofline and (at N = 1) the CPU baseline objects."""
+"""bench.py keeps its contract: one JSON line with the headline metric; under --full also the roofline, `extra` and (at N = 1) the CPU baseline objects."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUTSIDE_STEPS_BUDGET_S = 30.0          # a plain run: start to exit, less its warm-up and timed steps
 
 
 def test_bench_prints_one_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1"], capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -61,6 +63,26 @@ def test_bench_prints_one_contract_line():
     assert abs(d["value"] - 1024 * 1000.0 / d["ms_per_step"]) / d["value"] < 0.01
 
 
+def test_bench_plain_run_reports_the_headline_only():
+    """Without --full the run times the same steps and prints the headline fields alone: no roofline pass, no `extra`, no CPU baseline, and
+    little time spent outside its warm-up and timed steps."""
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+              "world_size_seen", "rank_devices"):
+        assert k in d, k
+    assert not {"roofline", "extra", "cpu_baseline"} & set(d)
+    assert d["metric"] == "frames/sec pose-infer+uncertainty, 256x192 17-kp" and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["value"] > 5000
+    assert abs(d["value"] - 1024 * 1000.0 / d["ms_per_step"]) / d["value"] < 0.01
+    assert wall - 3 * d["ms_per_step"] / 1000.0 < OUTSIDE_STEPS_BUDGET_S, wall
+
+
 def test_bench_two_ranks_launch_contract():
     """The driver's N > 1 launch line (torch.distributed.run, one rank per GPU) on a 1-GPU box: two ranks share the device and
     talk over gloo (VATL_DIST_BACKEND; RCCL refuses two ranks on one device).  Checks the rendezvous, the per-step result
@@ -71,7 +93,7 @@ def test_bench_two_ranks_launch_contract():
         port = s.getsockname()[1]
     env = dict(os.environ, VATL_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--no-extra"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--no-extra"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -89,8 +111,8 @@ def test_bench_gpus_flag_starts_its_own_ranks():
     env = dict(os.environ, VATL_DIST_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"], capture_output=True, text=True,
-                         timeout=1500, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"], capture_output=True,
+                         text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

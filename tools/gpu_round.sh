@@ -24,13 +24,8 @@ if [[ "$ARGS" == *" prof "* ]]; then
   find gpurun_out/prof -name "*kernel_trace*" -size +30M -delete
 fi
 if [[ "$ARGS" == *" pmc "* ]]; then
-  # HBM traffic counters: one counter per pass, kernel-trace only (MI355X_MICROARCH.md §HBM)
-  for c in FETCH_SIZE WRITE_SIZE; do
-    echo "== rocprofv3 --pmc $c"
-    rm -rf gpurun_out/pmc_$c
-    timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d gpurun_out/pmc_$c -o r1 -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra > gpurun_out/pmc_$c.log 2>&1
-    tail -1 gpurun_out/pmc_$c.log | cut -c1-300
-    ls gpurun_out/pmc_$c | head
-    find gpurun_out/pmc_$c -name "*kernel_trace*" -size +30M -delete
-  done
+  # HBM traffic counters: one counter per pass, kernel-trace only (MI355X_MICROARCH.md §HBM), and their per-step summary;
+  # tag "." puts the passes straight into this script's log directory
+  echo "== rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE"
+  bash tools/pmc_bench.sh .
 fi

@@ -7,8 +7,8 @@ Units and corrections (MI355X_MICROARCH.md §HBM): the counters are in KiB; on g
 FETCH_SIZE reports exactly half of the bytes of a wide coalesced read stream, so it is
 doubled (calibrated here on nchw_to_nhwc_kernel, whose read volume is known exactly:
 N*3*H*W*4 bytes); WRITE_SIZE matched known store volumes (stem output) without correction.
-Each pass ran `bench.py --steps 1 --warmup 0` = 2 forwards of the 1024-frame video
-(one timed step + the roofline pass), so per-step values are totals / 2.
+Each pass ran `bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra` = 2 forwards of the 1024-frame
+video (one timed step + the roofline pass), so per-step values are totals / 2.
 """
 import collections
 import csv
@@ -45,7 +45,7 @@ def main():
             if "stem_pool_kernel<3, 7>" in k:
                 cal, cal_name = v, "stem_pool_kernel<3, 7>"
     summary = {
-        "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes), bench.py --steps 1 --warmup 0, 1024 frames/step",
+        "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes), bench.py --full --steps 1 --warmup 0, 1024 frames/step",
         "fetch_correction": 2.0,
         "calibration": {"kernel": cal_name, "expected_read_bytes": 1024 * 3 * 256 * 192 * 4,
                         "measured_read_bytes_corrected": cal["read_bytes_per_step"] if cal else None,

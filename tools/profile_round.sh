@@ -27,14 +27,14 @@ echo "== FastPose-R152 step (config 5)"; prof cfg5 "$REPO/tools/config_bench.py"
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== rocprofv3 --pmc $c"
   rm -rf "$OUT/pmc_$c"
-  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/pmc_$c" -o r1 -- python3 "$REPO/bench.py" --steps 1 --warmup 0 --no-cpu-baseline --no-extra > "$OUT/pmc_$c.log" 2>&1
+  timeout 900 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/pmc_$c" -o r1 -- python3 "$REPO/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra > "$OUT/pmc_$c.log" 2>&1
   tail -1 "$OUT/pmc_$c.log" | cut -c1-200
 done
 find "$OUT" -name "*kernel_trace*" -size +20M -delete
 find "$OUT" -name "*counter_collection*" -size +40M -delete
 cd "$REPO"
 echo "== scorer roofline"; timeout 600 python3 tools/scorer_bench.py 2>&1 | grep '^{' > "$OUT/scorer_roofline.jsonl"; wc -l "$OUT/scorer_roofline.jsonl"
-echo "== bench (full line)"; timeout 900 python3 bench.py --steps 20 --warmup 3 2>&1 | grep '^{' | tail -1 > "$OUT/bench.json"; cut -c1-300 "$OUT/bench.json"
+echo "== bench (full line)"; timeout 900 python3 bench.py --full --steps 20 --warmup 3 2>&1 | grep '^{' | tail -1 > "$OUT/bench.json"; cut -c1-300 "$OUT/bench.json"
 echo "== config_bench"; timeout 900 python3 tools/config_bench.py 2>&1 | grep '^{' | tee "$OUT/config_bench.jsonl"
 python3 tools/pmc_summary.py "$OUT" "$OUT/pmc_summary.json" 2>&1 | tail -3
 du -sh "$OUT"
