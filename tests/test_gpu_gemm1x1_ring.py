@@ -1,4 +1,4 @@
-"""The LDS-DMA ring kernel for long-K 1x1 layers (csrc/conv_igemm.hip, gemm1x1_ring_kernel), which the default k-loop schedule
+"""The LDS-DMA ring kernel for long-K 1x1 layers (csrc/gemm1x1_ring.hip, gemm1x1_ring_kernel), which the default k-loop schedule
 (vatl_tune_set(0, 4)) takes for them: bit-identical to the tiled implicit GEMM that the other schedules run (vatl_tune_set(0, 2) here;
 the schedules' mutual bit-identity is pinned in tests/test_gpu_conv.py), float64 parity, batch-position independence and the routes."""
 import numpy as np

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Register / LDS budget of every kernel of a csrc file, from hipcc's own remarks (no GPU needed):
 
-    python tools/kernel_resources.py conv_igemm [conv_wgrad ...]
-prints arch VGPRs, accumulator VGPRs, spills, waves per SIMD and LDS bytes per block.  A kernel whose waves leave part of the
+    python tools/kernel_resources.py conv_igemm [gemm1x1_ring conv_streamk conv_wgrad ...]
+(names of csrc/*.hip files; the persistent 1x1 kernels are part of conv_igemm) prints arch VGPRs, accumulator VGPRs, spills, waves per SIMD and LDS bytes per block.  A kernel whose waves leave part of the
 SIMD's 512 registers free lets a small element-wise wave of another stream share the CU (profiles/r05_notes.md)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -49,7 +49,7 @@ WINOGRAD = True
 # 1x1 layers with K = 128 and N a multiple of 128 (Bottleneck.conv3 of stage 2; conv3 + projection of stage 1's first block) through the row-streaming GEMM
 # (csrc/conv1x1_rows.hip: filter slice in registers, 32-pixel tiles; bit-identical to the tiled kernels, which ROWS_GEMM = False selects).
 ROWS_GEMM = True
-# ... and, since round 6, K = 256 with N >= 512 (Bottleneck.conv3 of ResNet stage 3: 256 -> 1024 + skip; `conv1x1_rows256_kernel`, bit-identical as well).
+# ... and, since round 6, K = 256, N a multiple of 128 as well (in the networks here: Bottleneck.conv3 of ResNet stage 3, 256 -> 1024 + skip; `conv1x1_rows256_kernel`, bit-identical as well).
 ROWS_GEMM_K = (128, 256)
 # 32 -> 32 channel 3x3 layers (HRNet's highest-resolution branch) through the wave-private Winograd kernel (csrc/winograd_c32.hip: a wave owns 16 tiles with all 16
 # transform positions, no cross-wave exchange).  False = the general Winograd kernel (same values to fp32 rounding, not the same bits).

@@ -8,6 +8,7 @@
 // T has the bits of the tiled implicit GEMM (same k order); Y1 sums K in 4 x 64 pieces, so it differs from the two-launch path in the last bits (5e-7 of the plane maximum).
 // Measured at 1024 crops of 64x48 pixels (tools/chain_bench.py): 2.00 ms against 2.48 - 2.64 ms for the two tiled launches; the first GEMM alone (w1 == NULL) 1.36 against 1.51 ms.
 #include "common.h"
+#include "buffer.h"
 
 namespace vatl {
 
@@ -28,10 +29,6 @@ struct ChainParams {
 };
 
 constexpr unsigned BOOB = 0xFFFFFFFFu;
-typedef unsigned int bu32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void blds_void;
-__device__ __forceinline__ f32x4 bbuf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)); }
-__device__ __forceinline__ void bbuf_store4(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(bu32x4, v), r, off, 0, 0); }
 
 constexpr int BT_LDT = 260;                       // T tile row pitch (floats)
 constexpr int BT_AS = 32 * 64;                    // one A stage: 32 rows x 64 floats, 16-byte chunks XOR-swizzled by (row & 7)
@@ -46,17 +43,17 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
     const int fr = lane & 31, h = lane >> 5;
     const int nblk = gridDim.x, bid = blockIdx.x;
 
-    const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w3r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w3), 0, p.w3_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t tr = __builtin_amdgcn_make_buffer_rsrc(p.t, 0, p.t_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.t), 0, p.res ? p.t_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ar = buf_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t w3r = buf_rsrc(p.w3, p.w3_bytes);
+    const __amdgpu_buffer_rsrc_t tr = buf_rsrc(p.t, p.t_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res ? p.res : p.t, p.res ? p.t_bytes : 0u);
 
     // filters in MFMA B-fragment order: lane (channel fr of the 32-column block, k half h) holds W[n][8 g + 4 h .. + 3]
     f32x4 w3f[2][8];                              // first GEMM: this wave's 64 output channels, K = 64
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-        for (int g = 0; g < 8; ++g) w3f[nb][g] = bbuf_load4(w3r, (unsigned)(((wave * 64 + nb * 32 + fr) * 64 + 8 * g + 4 * h) * 4));
+        for (int g = 0; g < 8; ++g) w3f[nb][g] = buf_load4(w3r, (unsigned)(((wave * 64 + nb * 32 + fr) * 64 + 8 * g + 4 * h) * 4));
     float sc3[2], bi3[2];
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
@@ -66,11 +63,11 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
     }
     f32x4 w1f[SECOND ? 2 : 1][8];                 // second GEMM: all 64 output channels, this wave's K range [64 wave, 64 wave + 64)
     if constexpr (SECOND) {
-        const __amdgpu_buffer_rsrc_t w1r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w1), 0, p.w1_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t w1r = buf_rsrc(p.w1, p.w1_bytes);
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-            for (int g = 0; g < 8; ++g) w1f[nb][g] = bbuf_load4(w1r, (unsigned)(((nb * 32 + fr) * 256 + wave * 64 + 8 * g + 4 * h) * 4));
+            for (int g = 0; g < 8; ++g) w1f[nb][g] = buf_load4(w1r, (unsigned)(((nb * 32 + fr) * 256 + wave * 64 + 8 * g + 4 * h) * 4));
     }
     const float lo3 = p.relu3 ? 0.f : -INFINITY;
 
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
             const int q = (wave * 2 + u) * 64 + lane;
             const int row = q >> 4, chunk = (q & 15) ^ (row & 7);
             const unsigned off = (unsigned)mt * (32u * 64u * 4u) + (unsigned)(row * 64 + chunk * 4) * 4u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, (blds_void*)(As + buf * BT_AS + (wave * 2 + u) * 256), 16, off, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, (lds_void*)(As + buf * BT_AS + (wave * 2 + u) * 256), 16, off, 0, 0, 0);
         }
     };
 
@@ -97,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
         const unsigned tbase = (unsigned)mt * (32u * 1024u) + tlane;
         f32x4 rs[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) rs[u] = p.res ? bbuf_load4(rr, tbase + (unsigned)u * 4096u) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int u = 0; u < 8; ++u) rs[u] = p.res ? buf_load4(rr, tbase + (unsigned)u * 4096u) : f32x4{0.f, 0.f, 0.f, 0.f};
         if (mt + nblk < p.m_tiles) a_dma(buf ^ 1, mt + nblk);
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc[2];
@@ -131,7 +128,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
                 f32x4 o;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) o[c] = fmaxf(v[c] + rs[u][c], lo3);
-                bbuf_store4(tr, tbase + (unsigned)u * 4096u, o);
+                buf_store4(tr, tbase + (unsigned)u * 4096u, o);
                 if constexpr (SECOND) *reinterpret_cast<f32x4*>(&Ts[row * BT_LDT + c4 * 4]) = o;
             }
         }
@@ -162,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
                 }
             __syncthreads();
             {
-                const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(p.out2, 0, p.o_bytes, 0x00020000);
+                const __amdgpu_buffer_rsrc_t orr = buf_rsrc(p.out2, p.o_bytes);
                 const int q4 = tid & 15, q0 = tid >> 4;              // 16 quads x 16 rows per pass, 2 passes
                 const f32x4 s1 = p.scale1 ? *reinterpret_cast<const f32x4*>(p.scale1 + q4 * 4) : f32x4{1.f, 1.f, 1.f, 1.f};
                 const f32x4 b1 = p.bias1 ? *reinterpret_cast<const f32x4*>(p.bias1 + q4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -179,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
                     f32x4 o;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) o[c] = fmaxf(sum[c] * s1[c] + b1[c], 0.f);
-                    bbuf_store4(orr, ((unsigned)(mt * 32 + row) * 64u + (unsigned)q4 * 4u) * 4u, o);
+                    buf_store4(orr, ((unsigned)(mt * 32 + row) * 64u + (unsigned)q4 * 4u) * 4u, o);
                 }
             }
         }

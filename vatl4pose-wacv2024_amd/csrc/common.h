@@ -47,6 +47,10 @@ inline int ensure_dynamic_lds(const void* kern, int bytes, std::atomic<unsigned>
     return 0;
 }
 
+// Narrow 3x3 layers (conv3x3_halo.hip), tried first by conv_igemm.hip's forward entry: 0 = done, < 0 = error, 1 = not one of its shapes.
+__attribute__((visibility("hidden"))) int conv3x3_halo_try(const float* x, const float* w, const float* scale, const float* bias, const float* residual, float* y, int N, int H, int W,
+                                                           int Cin, int Cout, int CoutPad, int R, int S, int stride, int pad, int relu, hipStream_t st);
+
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

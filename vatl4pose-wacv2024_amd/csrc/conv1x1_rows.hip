@@ -7,6 +7,7 @@
 // tile's stores stay in flight across the barrier into the next tile (counted s_waitcnt: VMEM operations retire in order).  Blocks that share pixel tiles (the N / 128
 // slices) are neighbours on one XCD, so A is read from HBM once.  Same k order as the tiled kernels: bit-identical results.
 #include "common.h"
+#include "buffer.h"
 
 #include <atomic>
 
@@ -23,11 +24,6 @@ struct RowsParams {
     int M, N, relu, m_tiles, nslices;
     unsigned a_bytes, x2_bytes, y_bytes, w_bytes;
 };
-
-typedef unsigned int ru32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void rlds_void;
-__device__ __forceinline__ f32x4 rbuf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0)); }
-__device__ __forceinline__ void rbuf_store4(__amdgpu_buffer_rsrc_t r, unsigned off, f32x4 v) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ru32x4, v), r, off, 0, 0); }
 
 constexpr int RW_AS = 32 * 128;                   // one A stage: 32 rows x 128 floats, 16-byte chunks XOR-swizzled by (row & 7)
 constexpr int RW_LDT = 132;                       // output tile row pitch (floats)
@@ -46,17 +42,17 @@ __global__ __launch_bounds__(256, 3) void conv1x1_rows_kernel(RowsParams p) {
     const int tstep = (gridDim.x >> 3) / p.nslices * 8;
     const int n0 = slice * 128;
 
-    const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? p.x2 : p.a), 0, DUAL ? p.x2_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.y), 0, p.res ? p.y_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ar = buf_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(DUAL ? p.x2 : p.a, DUAL ? p.x2_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t wr = buf_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res ? p.res : p.y, p.res ? p.y_bytes : 0u);
 
     // the filter slice in MFMA B-fragment order: lane (channel fr of the wave's 32, k half h) holds W[n][8 g + 4 h .. + 3], g = 0 .. 15
     f32x4 wf[16];
     const int nw = n0 + wave * 32 + fr;
 #pragma unroll
-    for (int g = 0; g < 16; ++g) wf[g] = rbuf_load4(wr, (unsigned)((nw * 128 + 8 * g + 4 * h) * 4));
+    for (int g = 0; g < 16; ++g) wf[g] = buf_load4(wr, (unsigned)((nw * 128 + 8 * g + 4 * h) * 4));
     const float sc = p.scale ? p.scale[nw] : 1.f, bi = p.bias ? p.bias[nw] : 0.f;
     const float lo = p.relu ? 0.f : -INFINITY;
 
@@ -67,7 +63,7 @@ __global__ __launch_bounds__(256, 3) void conv1x1_rows_kernel(RowsParams p) {
         for (int u = 0; u < 4; ++u) {
             const int q = (wave * 4 + u) * 64 + lane;
             const int row = q >> 5, chunk = (q & 31) ^ (row & 7);
-            rlds_void* dst = (rlds_void*)(As + buf * RW_AS + (wave * 4 + u) * 256);
+            lds_void* dst = (lds_void*)(As + buf * RW_AS + (wave * 4 + u) * 256);
             if constexpr (DUAL) {                                   // chunks 0 .. 15 from a (M, 64), 16 .. 31 from x2 (M, 64): two requests with complementary lanes
                 const unsigned off = (unsigned)mt * (32u * 64u * 4u) + (unsigned)(row * 64 + (chunk & 15) * 4) * 4u;
                 if (chunk < 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, dst, 16, off, 0, 0, 0);
@@ -90,7 +86,7 @@ __global__ __launch_bounds__(256, 3) void conv1x1_rows_kernel(RowsParams p) {
         const unsigned ybase = (unsigned)mt * (32u * nrow) + ylane;
         f32x4 rs[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) rs[u] = p.res ? rbuf_load4(rr, ybase + (unsigned)u * (8u * nrow)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int u = 0; u < 4; ++u) rs[u] = p.res ? buf_load4(rr, ybase + (unsigned)u * (8u * nrow)) : f32x4{0.f, 0.f, 0.f, 0.f};
         if (mt + tstep < p.m_tiles) a_dma(buf ^ 1, mt + tstep);
         __builtin_amdgcn_sched_barrier(0);
         f32x16 acc;
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(256, 3) void conv1x1_rows_kernel(RowsParams p) {
             f32x4 o;
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[c] = fmaxf(v[c] + rs[u][c], lo);
-            rbuf_store4(yr, ybase + (unsigned)u * (8u * nrow), o);
+            buf_store4(yr, ybase + (unsigned)u * (8u * nrow), o);
         }
         // the next tile's A rows were requested before this pass's four stores: wait for them only, the stores stay in flight across the barrier
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -143,15 +139,15 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rows256_kernel(RowsParams p) {
     const int tstep = (gridDim.x >> 3) / p.nslices * 8;
     const int n0 = slice * 128;
 
-    const __amdgpu_buffer_rsrc_t ar = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.a), 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.y), 0, p.res ? p.y_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ar = buf_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t wr = buf_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res ? p.res : p.y, p.res ? p.y_bytes : 0u);
 
     f32x4 wf[32];                                 // lane (channel fr of the wave's 32, k half h): W[n][8 g + 4 h .. + 3], g = 0 .. 31
     const int nw = n0 + wave * 32 + fr;
 #pragma unroll
-    for (int g = 0; g < 32; ++g) wf[g] = rbuf_load4(wr, (unsigned)((nw * RW2_K + 8 * g + 4 * h) * 4));
+    for (int g = 0; g < 32; ++g) wf[g] = buf_load4(wr, (unsigned)((nw * RW2_K + 8 * g + 4 * h) * 4));
     const float sc = p.scale ? p.scale[nw] : 1.f, bi = p.bias ? p.bias[nw] : 0.f;
     const float lo = p.relu ? 0.f : -INFINITY;
 
@@ -161,7 +157,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_rows256_kernel(RowsParams p) {
         for (int u = 0; u < 8; ++u) {
             const int q = (wave * 8 + u) * 64 + lane;
             const int row = q >> 6, chunk = (q & 63) ^ (row & 7);
-            rlds_void* dst = (rlds_void*)(As + buf * RW2_AS + (wave * 8 + u) * 256);
+            lds_void* dst = (lds_void*)(As + buf * RW2_AS + (wave * 8 + u) * 256);
             const unsigned off = (unsigned)mt * (32u * RW2_K * 4u) + (unsigned)(row * RW2_K + chunk * 4) * 4u;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, dst, 16, off, 0, 0, 0);
         }

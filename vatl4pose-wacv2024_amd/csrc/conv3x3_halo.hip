@@ -22,6 +22,8 @@
 // Reduction order per output = (tap, 8-channel group, pair) exactly as conv_igemm_kernel's k-tiles: results are BIT-IDENTICAL to
 // the generic kernel (tests/test_gpu_conv.py), so the evaluation path keeps its batch-position-independent bits.
 #include "common.h"
+#include "buffer.h"
+#include "tune.h"
 
 namespace vatl {
 
@@ -38,7 +40,6 @@ struct HaloParams {
 };
 
 constexpr unsigned HOOB = 0xFFFFFFFFu;
-typedef unsigned int hu32x4 __attribute__((ext_vector_type(4)));
 
 template <int C, int TH, int TW>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
@@ -58,9 +59,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloParams p) {
     int t = blockIdx.x;
     if (t >= p.total) return;
 
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res), 0, p.res ? p.x_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res, p.res ? p.x_bytes : 0u);
 
     // ---- per-thread halo slots (the same for every patch): halo pixel, 16-byte chunk, LDS position
     int hy[NLD], hx[NLD], hq[NLD], hoff[NLD];

@@ -38,256 +38,14 @@
 //
 // The same kernel runs ConvTranspose2d(4,2,1) as four 2x2 sub-pixel phases
 // (blockIdx.y = py*2+px): pad = (1-py, 1-px), output scattered to (2y+py, 2x+px).
-#include "common.h"
+#include "conv_igemm.h"
+#include "tune.h"
 
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
 
 namespace vatl {
-
-struct ConvParams {
-    const float* x;
-    const float* w;
-    const float* scale;
-    const float* bias;
-    const float* res;
-    float* y;
-    int N, H, W, Cin;
-    int Cout, CoutPad;
-    int R, S, stride, pad_y, pad_x;
-    int Ho, Wo, M;
-    int OH, OW, osy, osx, ooy, oox;   // output pixel = (oy*osy+ooy, ox*osx+oox) in an OH x OW image
-    int relu, out_nchw, deconv;
-    int kpr;                          // k-tiles per filter tap  (Cin/32; 1 for the stem)
-    int ktiles;                       // total k-tiles
-    int n_tiles, m_tiles;
-    int order;                        // tile order inside an XCD's run: 0 n-tile fastest, 1 m-tile fastest
-    int stagger;                      // start the second resident block of every CU half a block-time late
-    int K;                            // packed K per output channel
-    double* stats;                    // training: per (row block, channel) partial (sum, sum^2) of the stored tile, or NULL
-    // BatchNorm-backward fusion (data-gradient launches of the fine-tune step): the tile being stored is dL/dy of a
-    // Conv+BN(+ReLU) layer whose conv output is bz (same NHWC layout as y).  The epilogue applies that layer's ReLU mask
-    // (bmy > 0 if given, else bz*bsc+bbi > 0 if bsc is given, else none), stores g = masked gradient and accumulates the
-    // per-channel (sum g, sum g*xhat), xhat = (bz - bmu)*bis, into `stats` — the reduction pass of the BN backward.
-    const float* bz;
-    const float* bmy;
-    const float* bsc;
-    const float* bbi;
-    const float* bmu;
-    const float* bis;
-    // dual-source 1x1 (projection shortcut fused into the block's last conv): k-tiles 0..k1-1 read x (C1 = Cin channels,
-    // one row per output pixel), k-tiles k1.. read x2 (C2 channels, an H2 x W2 image sampled with stride2)
-    const float* x2;
-    int k1, C2, H2, W2, stride2;
-    unsigned x2_bytes;
-    int ablate;                       // profiling only (vatl_tune_set(6, bits), wrong results): 1 = no epilogue
-    // opt-in split-K (small batches): blockIdx.z owns k-tiles [z*kt_per_split, ...) and writes a raw partial tile into
-    // its slice of `part` (output layout of y, NHWC); splitk_reduce_kernel sums the slices in order and applies the epilogue
-    int splits, kt_per_split;
-    float* part;
-    long long part_slice;
-    unsigned x_bytes, w_bytes, y_bytes;   // buffer extents (hardware bounds checks: OOB loads read 0, OOB stores drop)
-    FastDivU d_HoWo, d_Wo;                // m -> (image, row, column) without integer divisions (common.h: fdiv; filled in by dispatch())
-};
-
-constexpr int BK = 32;
-constexpr int LDK = BK;               // LDS row = one k-tile; chunk positions XOR-swizzled (see above)
-// dynamic LDS of a BM x BN block: the two k-loop stages, or the epilogue's output tile if that is larger
-constexpr int conv_smem_floats(int BM, int BN) { return 2 * (BM + BN) * LDK > BM * (BN + 4) ? 2 * (BM + BN) * LDK : BM * (BN + 4); }
-constexpr unsigned OOB = 0xFFFFFFFFu; // byte offset guaranteed outside any descriptor below
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ void buf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, byte_off, 0, 0);
-}
-__device__ __forceinline__ float buf_load1(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ void buf_store1(__amdgpu_buffer_rsrc_t r, unsigned byte_off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, byte_off, 0, 0);
-}
-
-// Epilogue shared by the conv kernels: scale/bias in registers, tile staged through LDS, then full-row 16-byte
-// stores with the residual read the same way (or per-element stores for NCHW / odd channel counts).
-template <int BM, int BN, int WM, int WN, int NT = 256, bool BNB = false>
-__device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)[WM / 32][WN / 32], float* smem, int m0, int n0,
-                                              int ooy, int oox, int wm, int wn, int tid, int lane, int HoWo) {
-    constexpr int TM = WM / 32, TN = WN / 32;
-    // ---- epilogue -------------------------------------------------------------
-    // 1. scale/bias in registers, tile -> LDS (the staging buffers are free after the
-    //    loop's last barrier).  D[row = (e&3) + 8*(e>>2) + 4*(lane>>5)][col = lane&31].
-    constexpr int LDC = BN + 4;
-    float* Cs = smem;
-    // 0. output offsets of this thread's float4 columns and the residual tile, requested BEFORE the LDS
-    //    transpose so that its HBM latency hides behind the accumulator write-out and the barrier
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res), 0, p.res ? p.y_bytes : 0u, 0x00020000);
-    const int OHW = p.OH * p.OW;
-    const bool plain = !p.deconv && p.osy == 1 && p.osx == 1 && p.OH == p.Ho && p.OW == p.Wo;   // NHWC output row index == m
-    const bool vec = !p.out_nchw && (p.Cout & 3) == 0;
-    constexpr int C4 = BN / 4;                         // float4 columns per tile row
-    constexpr int RPP = NT / C4;                       // tile rows per pass
-    constexpr int NP = BM / RPP;                       // passes
-    unsigned offv[NP];
-    f32x4 rsv[NP];
-    if (vec) {
-        const int c4 = tid % C4, r0 = tid / C4;
-        const int n = n0 + c4 * 4;
-        const bool nv = n < p.Cout;
-#pragma unroll
-        for (int u = 0; u < NP; ++u) {
-            const int m = m0 + r0 + u * RPP;
-            int orow = m;
-            if (!plain) {
-                const int b = fdiv(m, p.d_HoWo);
-                const int rem = m - b * HoWo;
-                const int oy = fdiv(rem, p.d_Wo);
-                const int ox = rem - oy * p.Wo;
-                orow = b * OHW + (oy * p.osy + ooy) * p.OW + (ox * p.osx + oox);
-            }
-            offv[u] = (nv && m < p.M) ? (unsigned)(orow * p.Cout + n) << 2 : OOB;
-        }
-        if (p.res) {
-#pragma unroll
-            for (int u = 0; u < NP; ++u) rsv[u] = buf_load4(rr, offv[u]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < NP; ++u) rsv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int cl = wn * WN + j * 32 + (lane & 31);
-        const int n = n0 + cl;
-        const bool nv = n < p.Cout;
-        const float sc = (nv && p.scale) ? p.scale[n] : 1.f;
-        const float bi = (nv && p.bias) ? p.bias[n] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = wm * WM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                Cs[row * LDC + cl] = acc[i][j][e] * sc + bi;
-            }
-    }
-    __syncthreads();
-
-    // 2. LDS -> HBM with full rows: (+ residual) (ReLU), branch-free through descriptors
-    const float lo = p.relu ? 0.f : -INFINITY;
-    if (vec) {
-        const int c4 = tid % C4, r0 = tid / C4;
-        f32x4 ssum = {0.f, 0.f, 0.f, 0.f}, ssq = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (BNB) {
-            // BatchNorm-backward fusion (separate instantiations: the extra tile of z / mask registers must not cost the
-            // inference kernels their occupancy): mask the gradient tile with the consumer layer's ReLU, store g, reduce (g, g*xhat)
-            const __amdgpu_buffer_rsrc_t zr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bz), 0, p.y_bytes, 0x00020000);
-            const __amdgpu_buffer_rsrc_t mr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bmy), 0, p.bmy ? p.y_bytes : 0u, 0x00020000);
-            const int n = n0 + c4 * 4;
-            const bool nv = n < p.Cout;                    // Cout % 4 == 0 on this path: the float4 is in range or entirely out
-            const f32x4 one = {1.f, 1.f, 1.f, 1.f}, nul = {0.f, 0.f, 0.f, 0.f};
-            const f32x4 mu = nv ? *reinterpret_cast<const f32x4*>(p.bmu + n) : nul, is = nv ? *reinterpret_cast<const f32x4*>(p.bis + n) : nul;
-            const f32x4 msc = (nv && p.bsc) ? *reinterpret_cast<const f32x4*>(p.bsc + n) : nul;
-            const f32x4 mbi = (nv && p.bsc) ? *reinterpret_cast<const f32x4*>(p.bbi + n) : one;   // no mask: 0*z + 1 > 0
-            f32x4 zt[NP], yt[NP];
-#pragma unroll
-            for (int u = 0; u < NP; ++u) zt[u] = buf_load4(zr, offv[u]);
-            if (p.bmy) {
-#pragma unroll
-                for (int u = 0; u < NP; ++u) yt[u] = buf_load4(mr, offv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < NP; ++u) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(&Cs[(r0 + u * RPP) * LDC + c4 * 4]);
-                f32x4 g;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float d = v[c] + rsv[u][c];
-                    const bool on = p.bmy ? yt[u][c] > 0.f : fmaf(zt[u][c], msc[c], mbi[c]) > 0.f;
-                    g[c] = on ? d : 0.f;
-                    ssum[c] += g[c];
-                    ssq[c] += g[c] * ((zt[u][c] - mu[c]) * is[c]);       // rows >= M: d = 0 exactly
-                }
-                buf_store4(yr, offv[u], g);
-            }
-        } else {
-#pragma unroll
-        for (int u = 0; u < NP; ++u) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(&Cs[(r0 + u * RPP) * LDC + c4 * 4]);
-            f32x4 o;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) o[c] = fmaxf(v[c] + rsv[u][c], lo);
-            buf_store4(yr, offv[u], o);
-            if (p.stats) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { ssum[c] += o[c]; ssq[c] += o[c] * o[c]; }   // rows >= M hold exact zeros
-            }
-        }
-        }
-        if (p.stats) {
-            // BatchNorm batch statistics of the tile just stored (training forward): per-thread fp32 sums over NP rows,
-            // combined over the RPP row groups in double, one (sum, sum^2) pair per (row block, channel) — the layout
-            // bn_train_finalize_kernel reduces in a fixed order (deterministic, no atomics).
-            lds_barrier();                                 // every thread is done reading Cs (LDS hand-off only: __syncthreads() would wait for the tile's stores)
-            f32x4* sh = reinterpret_cast<f32x4*>(smem);
-            sh[tid] = ssum; sh[NT + tid] = ssq;
-            lds_barrier();
-            if (tid < C4) {
-                double ds[4] = {0, 0, 0, 0}, dq[4] = {0, 0, 0, 0};
-#pragma unroll 2                                           // (full unrolling cost the 128x32 kernel 256 VGPRs and spills)
-                for (int k = 0; k < RPP; ++k) {
-                    const f32x4 a = sh[k * C4 + tid], b = sh[NT + k * C4 + tid];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) { ds[c] += a[c]; dq[c] += b[c]; }
-                }
-                const long long rb = (long long)blockIdx.y * p.m_tiles + m0 / BM;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int n = n0 + tid * 4 + c;
-                    if (n < p.Cout) {
-                        p.stats[(rb * p.Cout + n) * 2 + 0] = ds[c];
-                        p.stats[(rb * p.Cout + n) * 2 + 1] = dq[c];
-                    }
-                }
-            }
-        }
-    } else {
-        // NCHW output (heat-map head) or a channel count that is not a multiple of 4:
-        // one tile row per thread, lanes run along pixels (contiguous in NCHW)
-        constexpr int CPP = NT / BM;                   // tile columns per pass
-        const int row = tid % BM, cl0 = tid / BM;
-        const int m = m0 + row;
-        const bool mv = m < p.M;
-        const int b = fdiv(m, p.d_HoWo);
-        const int rem = m - b * HoWo;
-        const int oy = fdiv(rem, p.d_Wo);
-        const int ox = rem - oy * p.Wo;
-        const int opix = (oy * p.osy + ooy) * p.OW + (ox * p.osx + oox);
-        const int nstride = p.out_nchw ? OHW : 1;
-        const int obase = p.out_nchw ? b * p.Cout * OHW + opix : (b * OHW + opix) * p.Cout;
-        if (p.res) {
-#pragma unroll 4
-            for (int ps = 0; ps < BN / CPP; ++ps) {
-                const int cl = cl0 + ps * CPP;
-                const int n = n0 + cl;
-                const unsigned off = (mv && n < p.Cout) ? (unsigned)(obase + n * nstride) << 2 : OOB;
-                buf_store1(yr, off, fmaxf(Cs[row * LDC + cl] + buf_load1(rr, off), lo));
-            }
-        } else {
-#pragma unroll 8
-            for (int ps = 0; ps < BN / CPP; ++ps) {
-                const int cl = cl0 + ps * CPP;
-                const int n = n0 + cl;
-                const unsigned off = (mv && n < p.Cout) ? (unsigned)(obase + n * nstride) << 2 : OOB;
-                buf_store1(yr, off, fmaxf(Cs[row * LDC + cl], lo));
-            }
-        }
-    }
-}
 
 // VAR selects the k-loop schedule (tuning knob, see vatl_tune_set).  Measured on MI355X, 3x3 512->512
 // @8x6, batch 1024 (tools/conv_bench.py, TFLOP/s): VAR0 126, VAR2 132, VAR3 131, VAR4 138; ablations of
@@ -346,9 +104,9 @@ __global__ __launch_bounds__(NT, 2) void conv_igemm_kernel(ConvParams p) {
     // out-of-range offset (OOB) reads zeros / drops the store, so image borders, M
     // tails and the optional residual need no branches (branches made hipcc drain
     // vmcnt before the MFMAs in the first version of this kernel).
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xr2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? p.x2 : p.x), 0, DUAL ? p.x2_bytes : p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wr = buf_rsrc(wbase, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t xr2 = buf_rsrc(DUAL ? p.x2 : p.x, DUAL ? p.x2_bytes : p.x_bytes);
 
     // ---- per-thread gather state --------------------------------------------
     const int lrow = tid >> 3;        // 0..RP-1
@@ -620,503 +378,11 @@ __global__ __launch_bounds__(NT, 2) void conv_igemm_kernel(ConvParams p) {
     conv_epilogue<BM, BN, WM, WN, NT, BNB>(p, acc, smem, m0, n0, ooy, oox, wm, wn, tid, lane, HoWo);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------------------------
-// Persistent 1x1 / stride-1 kernel (a plain GEMM Y[M][N] = A[M][K] W[N][K]^T with the conv epilogue).
-// The short-K 1x1 layers (conv3 / conv1 of the bottlenecks, K = 64..512) spend as long in the prologue (first
-// operand loads with nothing to overlap) and in the tile write-out as in their 2-16 k-tiles (profiles/r01_notes.md,
-// ablation knob 6).  Here a block stays resident, walks a run of tiles and requests the NEXT tile's first operand
-// tile before the current tile's epilogue, so that latency and the write-out overlap.  Same LDS layout, fragment
-// mapping, MFMA order and epilogue as conv_igemm_kernel: results are bit-identical.
-// ---------------------------------------------------------------------------------------------------------
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 2) void gemm1x1_persistent_kernel(ConvParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                          // [2][BM][LDK]
-    float* Bs = smem + 2 * BM * LDK;           // [2][BN][LDK]
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int WAVES_N = BN / WN;
-    constexpr int LA = BM / 32, LB = BN / 32;
-    constexpr int NG = BK / 8, MPG = 4 * TM * TN;
-    static_assert((BM / WM) * (BN / WN) == 4, "4 waves per block");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int lrow = tid >> 3, kq = tid & 7;
-    const int wpos = (kq ^ ((lrow >> 1) & 7)) * 4;
-    const int frow = lane & 31;
-    int koff[BK / 8];
-#pragma unroll
-    for (int g = 0; g < BK / 8; ++g) koff[g] = ((2 * g + (lane >> 5)) ^ ((frow >> 1) & 7)) * 4;
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
+}  // namespace vatl
 
-    // XCD-aware runs: XCD x (= block id mod 8) owns tiles [x*per, (x+1)*per) in n-fastest order; its blocks walk the run
-    // with a stride of (blocks per XCD), so the blocks that share an activation panel are on the same L2 at the same time
-    const int total = p.m_tiles * p.n_tiles;
-    const int per = (total + 7) >> 3, bpx = gridDim.x >> 3;
-    const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int run_end = min((xcd + 1) * per, total);
-    int t = xcd * per + loc;
-    if (t >= run_end) return;
+#include "gemm1x1_persistent.h"   // the persistent 1x1 family; why it is compiled in this unit: see the file
 
-    unsigned aoff[LA], boff[LB];               // byte offsets of this thread's float4s at k-tile 0
-    int m0, n0;
-    auto setup = [&](int tile, unsigned (&ao)[LA], unsigned (&bo)[LB], int& mm0, int& nn0) {
-        const int m_tile = tile / p.n_tiles, n_tile = tile - m_tile * p.n_tiles;
-        mm0 = m_tile * BM; nn0 = n_tile * BN;
-#pragma unroll
-        for (int i = 0; i < LA; ++i) ao[i] = (unsigned)(((mm0 + lrow + 32 * i) * p.K + kq * 4) * 4);   // rows >= M: past the descriptor -> zeros
-#pragma unroll
-        for (int j = 0; j < LB; ++j) bo[j] = (unsigned)(((nn0 + lrow + 32 * j) * p.K + kq * 4) * 4);
-    };
-    f32x4 ra[LA], rb[LB];
-    auto gload = [&](const unsigned (&ao)[LA], const unsigned (&bo)[LB], int kt, bool live) {
-#pragma unroll
-        for (int i = 0; i < LA; ++i) ra[i] = buf_load4(xr, live ? ao[i] + (unsigned)kt * (BK * 4) : OOB);
-#pragma unroll
-        for (int j = 0; j < LB; ++j) rb[j] = buf_load4(wr, live ? bo[j] + (unsigned)kt * (BK * 4) : OOB);
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < LA; ++i) *reinterpret_cast<f32x4*>(&As[(buf * BM + lrow + 32 * i) * LDK + wpos]) = ra[i];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) *reinterpret_cast<f32x4*>(&Bs[(buf * BN + lrow + 32 * j) * LDK + wpos]) = rb[j];
-    };
-    auto frag_read = [&](f32x4 (&af)[TM], f32x4 (&bf)[TN], int buf, int g) {
-        const float* Ab = As + (buf * BM + wm * WM + frow) * LDK + koff[g];
-        const float* Bb = Bs + (buf * BN + wn * WN + frow) * LDK + koff[g];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(Ab + i * 32 * LDK);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Bb + j * 32 * LDK);
-    };
-
-    setup(t, aoff, boff, m0, n0);
-    gload(aoff, boff, 0, true);
-    lstore(0);
-    __syncthreads();
-    const int HoWo = p.Ho * p.Wo;
-    for (;;) {
-        f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-        f32x4 af[2][TM], bf[2][TN];
-        for (int kt = 0; kt < p.ktiles; ++kt) {
-            const int buf = kt & 1;
-            const bool live = kt + 1 < p.ktiles;
-            frag_read(af[0], bf[0], buf, 0);
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                if (g + 1 < NG) frag_read(af[(g + 1) & 1], bf[(g + 1) & 1], buf, g + 1);
-                if (g == 0) gload(aoff, boff, kt + 1, live);
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g & 1][i][tt], bf[g & 1][j][tt], acc[i][j], 0, 0, 0);
-                if (g + 1 < NG) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-#pragma unroll
-                for (int q = 0; q < MPG; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x016, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (live) lstore(buf ^ 1);
-            __syncthreads();
-        }
-        // request the next tile's first operand tile: in flight during this tile's epilogue
-        const int tn = t + bpx;
-        const bool more = tn < run_end;
-        unsigned aoffn[LA], boffn[LB];
-        int m0n = 0, n0n = 0;
-        if (more) { setup(tn, aoffn, boffn, m0n, n0n); gload(aoffn, boffn, 0, true); }
-        conv_epilogue<BM, BN, WM, WN>(p, acc, smem, m0, n0, 0, 0, wm, wn, tid, lane, HoWo);
-        if (!more) break;
-        __syncthreads();                       // every thread is done with the epilogue's LDS tile
-        lstore(0);
-        __syncthreads();
-        t = tn; m0 = m0n; n0 = n0n;
-#pragma unroll
-        for (int i = 0; i < LA; ++i) aoff[i] = aoffn[i];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) boff[j] = boffn[j];
-    }
-}
-
-// The same persistent GEMM with a DISTANCE-2 operand stream that runs across tile boundaries.  With K = 64 .. 256 a tile has only
-// 2 .. 8 k-tiles; with one k-tile of look-ahead every one of them waits for an HBM round trip that 4096 matrix-pipe cycles do
-// not cover, and the pipe idles (l2.n.c3, K = 128: 61 % of peak at 3.4 TB/s — neither roof).  Here two staging register sets
-// alternate: while k-tile kt is multiplied, k-tile kt+1 sits in registers waiting to be written to LDS and k-tile kt+2 is being
-// requested — and "kt+2" simply continues into the NEXT tile's first two k-tiles, which therefore are in flight during the
-// whole epilogue of the current tile.  Requires an even number of k-tiles (statically indexed register sets).  Same LDS
-// layout, fragment mapping, MFMA order and epilogue: bit-identical to the other two kernels.
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256, 2) void gemm1x1_persistent2_kernel(ConvParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                          // [2][BM][LDK]
-    float* Bs = smem + 2 * BM * LDK;           // [2][BN][LDK]
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int WAVES_N = BN / WN;
-    constexpr int LA = BM / 32, LB = BN / 32;
-    constexpr int NG = BK / 8, MPG = 4 * TM * TN;
-    static_assert((BM / WM) * (BN / WN) == 4, "4 waves per block");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int lrow = tid >> 3, kq = tid & 7;
-    const int wpos = (kq ^ ((lrow >> 1) & 7)) * 4;
-    const int frow = lane & 31;
-    int koff[BK / 8];
-#pragma unroll
-    for (int g = 0; g < BK / 8; ++g) koff[g] = ((2 * g + (lane >> 5)) ^ ((frow >> 1) & 7)) * 4;
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
-
-    const int total = p.m_tiles * p.n_tiles;
-    const int per = (total + 7) >> 3, bpx = gridDim.x >> 3;
-    const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int run_end = min((xcd + 1) * per, total);
-    int t = xcd * per + loc;
-    if (t >= run_end) return;
-
-    unsigned aoff[LA], boff[LB];               // byte offsets of this thread's float4s at k-tile 0
-    int m0, n0;
-    auto setup = [&](int tile, unsigned (&ao)[LA], unsigned (&bo)[LB], int& mm0, int& nn0) {
-        const int m_tile = tile / p.n_tiles, n_tile = tile - m_tile * p.n_tiles;
-        mm0 = m_tile * BM; nn0 = n_tile * BN;
-#pragma unroll
-        for (int i = 0; i < LA; ++i) ao[i] = (unsigned)(((mm0 + lrow + 32 * i) * p.K + kq * 4) * 4);   // rows >= M: past the descriptor -> zeros
-#pragma unroll
-        for (int j = 0; j < LB; ++j) bo[j] = (unsigned)(((nn0 + lrow + 32 * j) * p.K + kq * 4) * 4);
-    };
-    f32x4 sa[2][LA], sb[2][LB];
-    auto issue = [&](f32x4 (&da)[LA], f32x4 (&db)[LB], const unsigned (&ao)[LA], const unsigned (&bo)[LB], int kt, bool live) {
-#pragma unroll
-        for (int i = 0; i < LA; ++i) da[i] = buf_load4(xr, live ? ao[i] + (unsigned)kt * (BK * 4) : OOB);
-#pragma unroll
-        for (int j = 0; j < LB; ++j) db[j] = buf_load4(wr, live ? bo[j] + (unsigned)kt * (BK * 4) : OOB);
-    };
-    auto stash = [&](const f32x4 (&da)[LA], const f32x4 (&db)[LB], int buf) {
-#pragma unroll
-        for (int i = 0; i < LA; ++i) *reinterpret_cast<f32x4*>(&As[(buf * BM + lrow + 32 * i) * LDK + wpos]) = da[i];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) *reinterpret_cast<f32x4*>(&Bs[(buf * BN + lrow + 32 * j) * LDK + wpos]) = db[j];
-    };
-    auto frag_read = [&](f32x4 (&af)[TM], f32x4 (&bf)[TN], int buf, int g) {
-        const float* Ab = As + (buf * BM + wm * WM + frow) * LDK + koff[g];
-        const float* Bb = Bs + (buf * BN + wn * WN + frow) * LDK + koff[g];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(Ab + i * 32 * LDK);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Bb + j * 32 * LDK);
-    };
-
-    setup(t, aoff, boff, m0, n0);
-    issue(sa[0], sb[0], aoff, boff, 0, true);
-    stash(sa[0], sb[0], 0);
-    issue(sa[0], sb[0], aoff, boff, 1, true);          // ktiles >= 2
-    __syncthreads();
-    const int HoWo = p.Ho * p.Wo;
-    const int KT = p.ktiles;
-    for (;;) {
-        f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-        const int tn = t + bpx;
-        const bool more = tn < run_end;
-        unsigned aoffn[LA], boffn[LB];
-        int m0n = 0, n0n = 0;
-        setup(more ? tn : t, aoffn, boffn, m0n, n0n);
-        f32x4 af[2][TM], bf[2][TN];
-        // one k-tile: fragment reads + 64 MFMAs on LDS buffer `buf`, the request of a later k-tile in the first group's shadow,
-        // the write of the waiting register set to the other buffer in the last group's
-        auto ktile = [&](int buf, auto&& request, auto&& write_back) {
-            frag_read(af[0], bf[0], buf, 0);
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                if (g + 1 < NG) frag_read(af[(g + 1) & 1], bf[(g + 1) & 1], buf, g + 1);
-                if (g == 0) request();
-                if (g == NG - 1) write_back();
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g & 1][i][tt], bf[g & 1][j][tt], acc[i][j], 0, 0, 0);
-                if (g + 1 < NG) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-#pragma unroll
-                for (int q = 0; q < MPG; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x216, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            __syncthreads();
-        };
-        for (int kt = 0; kt < KT; kt += 2) {
-            const bool in_tile = kt + 2 < KT;              // k-tiles kt+2, kt+3 belong to this tile; else: the next tile's first two
-            ktile(0, [&] { if (in_tile) issue(sa[1], sb[1], aoff, boff, kt + 2, true); else issue(sa[1], sb[1], aoffn, boffn, 0, more); },
-                  [&] { stash(sa[0], sb[0], 1); });
-            ktile(1, [&] { if (in_tile) issue(sa[0], sb[0], aoff, boff, kt + 3, true); else issue(sa[0], sb[0], aoffn, boffn, 1, more); },
-                  [&] { if (in_tile) stash(sa[1], sb[1], 0); });
-        }
-#ifdef VATL_ABLATION
-        if (p.ablate & 1) {                    // profiling build only: keep the accumulators alive, skip the write-out
-            float sacc = 0.f;
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) sacc += acc[i][j][e];
-            if (sacc == 12345.678f) p.y[0] = sacc;
-        } else
-#endif
-        conv_epilogue<BM, BN, WM, WN>(p, acc, smem, m0, n0, 0, 0, wm, wn, tid, lane, HoWo);
-        if (!more) break;
-        __syncthreads();                       // every thread is done with the epilogue's LDS tile
-        stash(sa[1], sb[1], 0);                // the next tile's k-tile 0 (requested two k-tiles ago); its k-tile 1 waits in set 0
-        __syncthreads();
-        t = tn; m0 = m0n; n0 = n0n;
-#pragma unroll
-        for (int i = 0; i < LA; ++i) aoff[i] = aoffn[i];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) boff[j] = boffn[j];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Stream-K scheduling for launches that cannot fill the chip with whole tiles (fine-tune batches: R50 stage 4 at B = 120 is 360
-// tiles of 64x128 on 768 resident block slots, FastPose-R152 stage 3 at 384x288 / B = 32 is 432 — 47 % / 56 % of the chip for
-// the whole launch).  The launch is exactly as many blocks as there are resident slots; the work is the flat sequence of
-// (tile, k-tile) units, cut into equal contiguous shares, so a block computes the tail of one tile, whole tiles, and the head of
-// another.  A share that STARTS inside a tile leaves that piece's raw fp32 accumulators in the block's slab of a caller-owned
-// workspace and publishes a flag at once (it is the block's first piece); the block that started the tile reaches it as the LAST
-// piece of its own share, adds the slabs of the blocks after it — in block order, a fixed order: bitwise reproducible — and runs
-// the ordinary epilogue (BatchNorm statistics / BatchNorm-backward fusion included).  (The first version had the roles the other
-// way round — the block holding a tile's last k-tile waited, at the START of its share, for a slab its predecessor wrote at the
-// END of its own: a chain of waits through all blocks, 1.7x slower than no stream-K at all.)  Every XCD owns a run of whole tiles and splits it among its own blocks, so a tile's pieces share one L2 and
-// a block only ever waits, with all of its own work done, for pieces that blocks publish before doing anything else: as long as
-// a handful of the launch's blocks are resident the wait ends (blocks without a successor to wait for retire and free their slots).  Visibility does not depend on that placement: slab stores -> s_waitcnt vmcnt(0) ->
-// barrier -> one lane's agent-scope release -> flag (relaxed agent store); the reader polls relaxed with s_sleep, then ONE
-// agent-scope acquire + barrier, then plain loads (cdna_hip_programming.md section 6, guideline 16).  The flags are never reset:
-// every launch carries a new epoch (the workspace is zeroed once, when it is registered).
-// The summation order over K differs from the unsplit kernel's (pieces are added per share), so results agree with it to
-// fp32 rounding, not bit for bit: only the training paths register a workspace (vatl_set_streamk_workspace_thread).
-// ---------------------------------------------------------------------------------------------------------
-struct StreamKArgs {
-    float* slabs;          // [grid][BM*BN] raw accumulators in register order
-    unsigned* flags;       // [grid] last epoch whose slab is complete
-    unsigned epoch;
-    int tiles;             // m_tiles * n_tiles
-};
-
-template <int BM, int BN, int WM, int WN, bool BNB>
-__global__ __launch_bounds__(256, 3) void conv_streamk_kernel(ConvParams p, StreamKArgs sk) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                          // [2][BM][LDK]
-    float* Bs = smem + 2 * BM * LDK;           // [2][BN][LDK]
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int WAVES_N = BN / WN;
-    constexpr int RP = 32;
-    constexpr int LA = BM / RP, LB = BN / RP;
-    constexpr int NG = BK / 8, MPG = 4 * TM * TN;
-    static_assert((BM / WM) * (BN / WN) == 4, "one wave per wave tile");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int lrow = tid >> 3, kq = tid & 7;
-    const int wpos = (kq ^ ((lrow >> 1) & 7)) * 4;
-    const int frow = lane & 31;
-    int koff[BK / 8];
-#pragma unroll
-    for (int g = 0; g < BK / 8; ++g) koff[g] = ((2 * g + (lane >> 5)) ^ ((frow >> 1) & 7)) * 4;
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
-    const int HoWo = p.Ho * p.Wo;
-    const int KT = p.ktiles;
-
-    // this block's share: XCD x (= block id mod 8) owns tiles [T x / 8, T (x+1) / 8), its blocks cut that run's units evenly
-    const int bid = blockIdx.x, xcd = bid & 7, loc = bid >> 3, bpx = gridDim.x >> 3;
-    const int t_lo = (int)((long long)sk.tiles * xcd / 8), t_hi = (int)((long long)sk.tiles * (xcd + 1) / 8);
-    const long long U = (long long)(t_hi - t_lo) * KT;
-    long long u = U * loc / bpx;
-    const long long u_end = U * (loc + 1) / bpx, u_begin = u;
-
-    int abase[LA], iy0[LA], ix0[LA];
-    unsigned boff[LB];
-    f32x4 ra[LA], rb[LB];
-    int g_r = 0, g_s = 0, g_off = 0;
-    auto gtap = [&](int kt) {
-        const int rs = kt / p.kpr;
-        const int c0 = (kt - rs * p.kpr) * BK;
-        g_r = rs / p.S; g_s = rs - g_r * p.S;
-        g_off = (g_r * p.W + g_s) * p.Cin + c0;
-    };
-    auto gloadA = [&](int i, bool live) {
-        const bool ok = live && (unsigned)(iy0[i] + g_r) < (unsigned)p.H && (unsigned)(ix0[i] + g_s) < (unsigned)p.W;
-        ra[i] = buf_load4(xr, ok ? (unsigned)(abase[i] + g_off) << 2 : OOB);
-    };
-    auto gloadB = [&](int j, int kt, bool live) { rb[j] = buf_load4(wr, live ? boff[j] + (unsigned)kt * (BK * 4) : OOB); };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < LA; ++i) *reinterpret_cast<f32x4*>(&As[(buf * BM + lrow + RP * i) * LDK + wpos]) = ra[i];
-#pragma unroll
-        for (int j = 0; j < LB; ++j) *reinterpret_cast<f32x4*>(&Bs[(buf * BN + lrow + RP * j) * LDK + wpos]) = rb[j];
-    };
-    auto frag_read = [&](f32x4 (&af)[TM], f32x4 (&bf)[TN], int buf, int g) {
-        const float* Ab = As + (buf * BM + wm * WM + frow) * LDK + koff[g];
-        const float* Bb = Bs + (buf * BN + wn * WN + frow) * LDK + koff[g];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f32x4*>(Ab + i * 32 * LDK);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Bb + j * 32 * LDK);
-    };
-    typedef __attribute__((address_space(1))) unsigned gu32;
-    f32x4* const slab_mine = reinterpret_cast<f32x4*>(sk.slabs) + (long long)bid * (BM * BN / 4);
-
-    while (u < u_end) {
-        const int tl = (int)(u / KT);
-        const int kb = (int)(u - (long long)tl * KT);
-        const int ke = (int)((long long)kb + (u_end - u) < (long long)KT ? (long long)kb + (u_end - u) : (long long)KT);
-        const int t = t_lo + tl;
-        const int m_tile = t / p.n_tiles, n_tile = t - m_tile * p.n_tiles;
-        const int m0 = m_tile * BM, n0 = n_tile * BN;
-#pragma unroll
-        for (int i = 0; i < LA; ++i) {
-            const int m = m0 + lrow + RP * i;
-            if (m < p.M) {
-                const int b = fdiv(m, p.d_HoWo);
-                const int rem = m - b * HoWo;
-                const int oy = fdiv(rem, p.d_Wo);
-                const int ox = rem - oy * p.Wo;
-                iy0[i] = oy * p.stride - p.pad_y;
-                ix0[i] = ox * p.stride - p.pad_x;
-                abase[i] = ((b * p.H + iy0[i]) * p.W + ix0[i]) * p.Cin + kq * 4;
-            } else {
-                iy0[i] = -(1 << 20); ix0[i] = -(1 << 20); abase[i] = 0;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < LB; ++j) boff[j] = (unsigned)(((n0 + lrow + RP * j) * p.K + kq * 4) * 4);
-
-        f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-        gtap(kb);
-#pragma unroll
-        for (int i = 0; i < LA; ++i) gloadA(i, true);
-#pragma unroll
-        for (int j = 0; j < LB; ++j) gloadB(j, kb, true);
-        lstore(0);
-        __syncthreads();
-        f32x4 af[2][TM], bf[2][TN];
-        for (int kt = kb; kt < ke; ++kt) {
-            const int buf = (kt - kb) & 1;
-            const bool live = kt + 1 < ke;
-            frag_read(af[0], bf[0], buf, 0);
-            gtap(kt + 1);
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                if (g + 1 < NG) frag_read(af[(g + 1) & 1], bf[(g + 1) & 1], buf, g + 1);
-                if (g == 0) {
-#pragma unroll
-                    for (int i = 0; i < LA; ++i) gloadA(i, live);
-                }
-                if (g == 1) {
-#pragma unroll
-                    for (int j = 0; j < LB; ++j) gloadB(j, kt + 1, live);
-                }
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g & 1][i][tt], bf[g & 1][j][tt], acc[i][j], 0, 0, 0);
-                if (g + 1 < NG) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-#pragma unroll
-                for (int q = 0; q < MPG; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x016, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (live) lstore(buf ^ 1);
-            __syncthreads();
-        }
-
-        if (kb > 0) {
-            // the share starts inside this tile (always the block's FIRST piece): hand the accumulators to the block that started
-            // the tile — published right away, so that block finds them waiting when it gets to the tile at the END of its share
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int e4 = 0; e4 < 4; ++e4)
-                        slab_mine[((i * TN + j) * 4 + e4) * 256 + tid] =
-                            f32x4{acc[i][j][4 * e4], acc[i][j][4 * e4 + 1], acc[i][j][4 * e4 + 2], acc[i][j][4 * e4 + 3]};
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store((gu32*)(sk.flags + bid), sk.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        } else {
-            if (ke < KT) {
-                // this block started the tile and its share ends inside it (always the block's LAST piece): add the pieces of the
-                // blocks after it (same XCD: ids bid + 8, bid + 16, ...) in order, up to the one that holds the tile's last k-tile
-                const long long tile_end = (long long)(tl + 1) * KT;
-                long long s1 = u_end;
-                int q = loc + 1;
-                while (s1 < tile_end) {
-                    const long long qe = U * (q + 1) / bpx;
-                    if (qe == s1) { ++q; continue; }               // (a block without units publishes nothing)
-                    const int pb = q * 8 + xcd;
-                    if (tid == 0) {
-                        while (__hip_atomic_load((gu32*)(sk.flags + pb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != sk.epoch)
-                            __builtin_amdgcn_s_sleep(8);
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    }
-                    __syncthreads();
-                    const f32x4* slab = reinterpret_cast<const f32x4*>(sk.slabs) + (long long)pb * (BM * BN / 4);
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-#pragma unroll
-                            for (int e4 = 0; e4 < 4; ++e4) {
-                                const f32x4 v = slab[((i * TN + j) * 4 + e4) * 256 + tid];
-#pragma unroll
-                                for (int c = 0; c < 4; ++c) acc[i][j][4 * e4 + c] += v[c];
-                            }
-                    s1 = qe;
-                    ++q;
-                }
-            }
-            conv_epilogue<BM, BN, WM, WN, 256, BNB>(p, acc, smem, m0, n0, p.ooy, p.oox, wm, wn, tid, lane, HoWo);
-            __syncthreads();                       // the epilogue's LDS tile is free again
-        }
-        u += ke - kb;
-    }
-}
+namespace vatl {
 
 // LDS-DMA variant (VAR 5): operand tiles go HBM/L2 -> LDS directly (buffer_load ... lds, 1 KiB per wave
 // instruction, no staging VGPRs, no ds_write pass).  The DMA destination is lane-linear (base + lane*16 B), so
@@ -1126,8 +392,6 @@ __global__ __launch_bounds__(256, 3) void conv_streamk_kernel(ConvParams p, Stre
 // (conflict-free ds_read_b128).  Out-of-image taps / tail tiles use out-of-range offsets: the DMA writes zeros
 // (verified on MI355X).  Two stages of 32 KiB; the epilogue reuses the space.
 // ---------------------------------------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void lds_void;
-
 // (body in a __device__ function: with the DMA builtin called from a lambda directly inside the __global__
 // template, hipcc 7.2 silently drops the HOST stub of the kernel and the library fails to load)
 template <int BM, int BN, int WM, int WN>
@@ -1157,8 +421,8 @@ __device__ __forceinline__ void conv_igemm_dma_body(const ConvParams& p, float* 
         pad_y = 1 - py; pad_x = 1 - px; ooy = py; oox = px;
         wbase += (long long)blockIdx.y * p.CoutPad * p.K;
     }
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wbase), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wr = buf_rsrc(wbase, p.w_bytes);
 
     // ---- loader state: instruction i of wave w fills tile rows (4i + w)*8 .. +7; lane -> (row, chunk position)
     const int lrow = lane >> 3;                       // row inside the 8-row group
@@ -1270,245 +534,19 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_dma_kernel(ConvParams p) {
     conv_igemm_dma_body<BM, BN, WM, WN>(p, smem);
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Long-K 1x1 / stride-1 layers (K >= 512, and the dual-source conv3 + projection): a plain GEMM Y[M][N] = A[M][K] W[N][K]^T on
-// 128 x 128 tiles with an LDS-DMA OPERAND RING.  The r01 ablation of the tiled kernel puts 12 % of its time on staging (global
-// loads + ds_write: 138 -> 150 TFLOP/s without them), and fp32 MFMAs do not overlap vector instructions on a SIMD.  Here:
-//  * stages of 16 k (two 8-deep fragment groups) = (128 + 128) rows x 64 bytes = 16 KB; a ring of four = 64 KB per block, two blocks
-//    per CU.  While stage s is multiplied, stages s+1 .. s+3 are in flight (look-ahead 3, against 1 for VAR 5 above);
-//  * both operands are staged by buffer_load ... lds only (no staging registers, no ds_write).  A lane's source offset is fixed for
-//    the tile (row * K + chunk); the stage advance is the SGPR soffset s * 64.  The k-loop is MFMAs, ds_read_b128, four DMA
-//    instructions per wave and stage, scalar ops, one counted s_waitcnt and one barrier per stage;
-//  * LDS rows are 64 bytes (4 chunks of 16 B); chunk c of tile row r lives at position c ^ ((r >> 2) & 3), applied on the SOURCE
-//    side (the DMA destination is lane-linear).  Each 16-lane service group of a ds_read_b128 fragment read ({0-3, 12-15, 20-27},
-//    {4-11, 16-19, 28-31}, same + 32) covers rows with four different (r >> 2) & 3 and four different r & 3: all 16 slots of a
-//    256-byte bank row, conflict-free;
-//  * tail rows (m >= M) read row M-1 (in range; their outputs are dropped by the descriptor: offsets >= M * Cout * 4);
-//  * the epilogue writes straight from the accumulator layout (a half wave stores a 128-byte channel run per row, as
-//    conv1x1_rows256_kernel), the residual is requested two stages before the end.
-// Dual source: stages 0 .. 2 k1 - 1 read x (one row per output pixel), the rest read x2 at the row's strided pixel.
-// Same k order as conv_igemm_kernel (lanes 0-31: k = 8g + t, lanes 32-63: k = 8g + 4 + t, groups ascending; x before x2) and the
-// same epilogue arithmetic: bit-identical results.
-// ---------------------------------------------------------------------------------------------------------
-constexpr int RING_BK = 16;                       // k per stage
-constexpr int RING_NS = 4;                        // stages in the ring
-constexpr int RING_STAGE = 256 * RING_BK;         // floats per stage: 128 A rows, then 128 B rows
-constexpr int RING_BYTES = RING_NS * RING_STAGE * (int)sizeof(float);
-
-template <int N>
-__device__ __forceinline__ void ring_wait_vm() {  // s_waitcnt vmcnt(N) with a compile-time N (the DMA requests are not in hipcc's own bookkeeping)
-    static_assert(N == 0 || N == 4 || N == 8 || N == 32 || N == 36, "add the count here");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(36)" ::: "memory");
-}
-
-template <bool DUAL, bool RES>
-__device__ __forceinline__ void gemm1x1_ring_body(const ConvParams& p, float* smem) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;      // 2 x 2 waves of 64 x 64
-
-    // tile order of conv_igemm_kernel (order 0): each XCD a contiguous run, n-tile fastest
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, loc = bid >> 3, q = nblk >> 3, r8 = nblk & 7;
-    const int t = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
-    const int m_tile = t / p.n_tiles, n_tile = t - m_tile * p.n_tiles;
-    const int m0 = m_tile * 128, n0 = n_tile * 128;
-
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xr2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? p.x2 : p.x), 0, DUAL ? p.x2_bytes : p.x_bytes, 0x00020000);
-
-    // ---- loader: DMA instruction u (0, 1) of wave w fills tile rows (4u + w) * 16 .. + 15 of A and of B; lane -> (row lane >> 2,
-    // position lane & 3), which receives the row's chunk (lane & 3) ^ ((row >> 2) & 3) = (lane & 3) ^ ((lane >> 4) & 3)
-    const int lchk = (lane & 3) ^ ((lane >> 4) & 3);
-    unsigned aoff[2], boff[2], aoff2[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int row = (4 * u + wave) * 16 + (lane >> 2);
-        const int m = min(m0 + row, p.M - 1);
-        aoff[u] = (unsigned)m * (unsigned)(p.Cin * 4) + (unsigned)lchk * 16u;
-        aoff2[u] = 0;
-        if (DUAL) {
-            const int b = fdiv(m, p.d_HoWo);
-            const int rem = m - b * p.Ho * p.Wo;
-            const int oy = fdiv(rem, p.d_Wo);
-            const int ox = rem - oy * p.Wo;
-            aoff2[u] = (unsigned)((b * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2) * (unsigned)(p.C2 * 4) + (unsigned)lchk * 16u;
-        }
-        boff[u] = (unsigned)(n0 + row) * (unsigned)(p.K * 4) + (unsigned)lchk * 16u;
-    }
-    const int S = p.ktiles * 2;                   // stages (a multiple of 4: ring_wanted)
-    const int S1 = DUAL ? p.k1 * 2 : S;           // stages that read x
-    // DMA of stage s into ring slot buf: offsets fixed per tile, the stage in soffset; src (compile-time) 1 = the stage reads x2
-    auto issue = [&](auto src, int buf, int s) {
-        float* st = smem + buf * RING_STAGE;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            lds_void* da = (lds_void*)(st + (4 * u + wave) * 256);
-            if constexpr (DUAL && decltype(src)::value == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(xr2, da, 16, aoff2[u], (unsigned)(s - S1) * 64u, 0, 0);
-            else                                             __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, da, 16, aoff[u], (unsigned)s * 64u, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void*)(st + 128 * RING_BK + (4 * u + wave) * 256), 16, boff[u], (unsigned)s * 64u, 0, 0);
-    };
-
-    // ---- fragments: row frow (+ 32 i) of the wave's 64, logical chunk 2g + h, at position (2g + h) ^ ((frow >> 2) & 3)
-    const int frow = lane & 31, h = lane >> 5;
-    const int fsw = (frow >> 2) & 3;
-    const float* Ard[2];
-    const float* Brd[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        Ard[g] = smem + (wm * 64 + frow) * RING_BK + (((2 * g + h) ^ fsw) << 2);
-        Brd[g] = smem + 128 * RING_BK + (wn * 64 + frow) * RING_BK + (((2 * g + h) ^ fsw) << 2);
-    }
-
-    // ---- epilogue operands, requested up front (scale / bias) or two stages before the end (residual)
-    const unsigned rowb = (unsigned)p.Cout * 4u;
-    const unsigned ylane = (unsigned)(m0 + wm * 64 + 4 * h) * rowb + (unsigned)(n0 + wn * 64 + frow) * 4u;   // acc element e of tile (i, j): + row (32 i + (e & 3) + 8 (e >> 2)), + 128 j bytes
-    float sc[2], bi[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + frow;
-        sc[j] = p.scale ? p.scale[n] : 1.f;
-        bi[j] = p.bias ? p.bias[n] : 0.f;
-    }
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(RES ? p.res : p.y), 0, RES ? p.y_bytes : 0u, 0x00020000);
-    float rs[2][2][16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) rs[i][j][e] = 0.f;
-    auto res_load = [&](int i) {                  // 32 loads: the residual of row half i
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                rs[i][j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                  rr, ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u, 0, 0));
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    // One stage.  KIND 0: steady state (stages s+1, s+2 in flight behind s: vmcnt(8)), then the request of stage s+3 into the
-    // slot every wave finished reading before this barrier (stage s-1's); 1: s = S-3, requests the residual's first row half
-    // instead; 2: s = S-2 (stage S-1 and that half younger); 3: s = S-1 (only that half younger), requests the second half.
-    // VMEM operations retire in order, so each count waits for this wave's pieces of stage s exactly.
-    auto stage = [&](auto slot, auto kind, auto src, int s) {
-        constexpr int B = decltype(slot)::value, KIND = decltype(kind)::value;
-        if constexpr (KIND <= 1) ring_wait_vm<8>();
-        else if constexpr (KIND == 2) ring_wait_vm<RES ? 36 : 4>();
-        else ring_wait_vm<RES ? 32 : 0>();
-        __builtin_amdgcn_s_barrier();             // every wave's pieces of stage s have landed; every wave is done reading slot (s - 1) % 4
-        asm volatile("" ::: "memory");
-        f32x4 af[2][2], bf[2][2];
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                af[g][i] = *reinterpret_cast<const f32x4*>(Ard[g] + B * RING_STAGE + i * 32 * RING_BK);
-                bf[g][i] = *reinterpret_cast<const f32x4*>(Brd[g] + B * RING_STAGE + i * 32 * RING_BK);
-            }
-        if constexpr (KIND == 0) issue(src, (B + 3) & 3, s + 3);
-        if constexpr (RES && KIND == 1) res_load(0);
-        if constexpr (RES && KIND == 3) res_load(1);
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][i][tt], bf[g][j][tt], acc[i][j], 0, 0, 0);
-        // pin the order: both groups' fragment reads first (separate registers: the second group's reads must not wait for the
-        // first group's MFMAs), then the four DMA requests one behind each of the first MFMAs, then the rest of the MFMAs
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-        if constexpr (KIND == 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x008, 28, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    using C0 = std::integral_constant<int, 0>;
-    using C1 = std::integral_constant<int, 1>;
-    using C2 = std::integral_constant<int, 2>;
-    using C3 = std::integral_constant<int, 3>;
-
-    using X2 = std::integral_constant<int, DUAL ? 1 : 0>;   // source of the stages past S1 (x itself for the plain form)
-    auto group = [&](auto src, int s) {           // four steady-state stages whose requests all read one source
-        stage(C0{}, C0{}, src, s);
-        stage(C1{}, C0{}, src, s + 1);
-        stage(C2{}, C0{}, src, s + 2);
-        stage(C3{}, C0{}, src, s + 3);
-    };
-
-    issue(C0{}, 0, 0);                            // (S1 >= 4: the first three stages read x)
-    issue(C0{}, 1, 1);
-    issue(C0{}, 2, 2);
-    int s = 0;
-    if constexpr (DUAL) {
-        for (; s < S1 - 4; s += 4) group(C0{}, s);
-        stage(C0{}, C0{}, C0{}, s);               // the group whose requests cross from x to x2 (S1 - 1 | S1 .. S1 + 2)
-        stage(C1{}, C0{}, X2{}, s + 1);
-        stage(C2{}, C0{}, X2{}, s + 2);
-        stage(C3{}, C0{}, X2{}, s + 3);
-        s += 4;
-    }
-    for (; s < S - 4; s += 4) group(X2{}, s);
-    stage(C0{}, C0{}, X2{}, s);                   // the last group: requests the last stage, then the residual
-    stage(C1{}, C1{}, X2{}, s + 1);
-    stage(C2{}, C2{}, X2{}, s + 2);
-    stage(C3{}, C3{}, X2{}, s + 3);
-
-    // ---- write-out from the accumulator layout: element e of tile (i, j) is row 32 i + (e & 3) + 8 (e >> 2) + 4 h, channel
-    // 64 wn + 32 j + frow; rows >= M lie past the descriptor (dropped).  Same arithmetic as conv_epilogue.
-    const float lo = p.relu ? 0.f : -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float v = fmaxf(acc[i][j][e] * sc[j] + bi[j] + rs[i][j][e], lo);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr,
-                                                      ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u, 0, 0);
-            }
-}
-
-template <bool DUAL, bool RES>
-__global__ __launch_bounds__(256, 2) void gemm1x1_ring_kernel(ConvParams p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    gemm1x1_ring_body<DUAL, RES>(p, smem);
-}
-
-template <int BM, int BN, int WM, int WN>
-static int launch_dma(const ConvParams& p, int phases, hipStream_t st);
-
 static std::atomic<int> g_var{4};      // k-loop schedule (vatl_tune_set(0, v)); 4 = shipped default
 static std::atomic<int> g_order{0};    // tile order (vatl_tune_set(1, v))
 static std::atomic<int> g_ablate{0};   // vatl_tune_set(6, bits): 1 = no epilogue, 2 = one k-tile only (profiling ablations, wrong results)
 static std::atomic<int> g_bm{0};       // tile rows (vatl_tune_set(5, v)): 0 = by grid size, 64 or 128 = forced
 static std::atomic<int> g_stagger{0};  // block stagger in percent of the k-loop time (vatl_tune_set(2, v)); 0 = off
 static std::atomic<int> g_splitk_policy{0};  // vatl_tune_set(9, v): 0 = cut by the launch's own block count, 1 = batch-invariant cut (per-image geometry)
+int igemm_set_schedule(int v) { g_var.store(v, std::memory_order_relaxed); return 0; }
+int igemm_set_order(int v) { g_order.store(v, std::memory_order_relaxed); return 0; }
+int igemm_set_ablate(int bits) { g_ablate.store(bits, std::memory_order_relaxed); return 0; }
+int igemm_set_tile_rows(int v) { g_bm.store(v, std::memory_order_relaxed); return 0; }
+int igemm_set_stagger(int v) { g_stagger.store(v, std::memory_order_relaxed); return 0; }
+int igemm_set_splitk_policy(int v) { g_splitk_policy.store(v, std::memory_order_relaxed); return 0; }
+int igemm_ablate_bits() { return g_ablate.load(std::memory_order_relaxed); }
 
 // Split-K (opt-in, vatl_set_splitk_workspace): y = act(sum_z part[z] * scale + bias (+ residual)), slices summed in order.
 // One thread per four channels of one output pixel (Cout % 4 == 0) or per element.
@@ -1544,7 +582,7 @@ static std::atomic<int> g_splitk_any{0};
 static thread_local float* tl_splitk_ws = nullptr;
 static thread_local long long tl_splitk_floats = 0;
 
-static float* splitk_workspace(long long* floats, int* policy) {
+float* splitk_workspace(long long* floats, int* policy) {
     if (tl_splitk_ws) { *floats = tl_splitk_floats; *policy = 1; return tl_splitk_ws; }
     *policy = g_splitk_policy.load(std::memory_order_relaxed);
     if (!g_splitk_any.load(std::memory_order_acquire)) return nullptr;
@@ -1638,126 +676,6 @@ static int launch_dma(const ConvParams& p, int phases, hipStream_t st) {
     return check_launch("conv_igemm_dma");
 }
 
-static std::atomic<int> g_persist_dist{2};   // vatl_tune_set(10, v): operand look-ahead of the persistent 1x1 kernel (1 or 2 k-tiles)
-
-template <int BM, int BN, int WM, int WN, bool D2>
-static int launch_persistent_impl(const ConvParams& p, hipStream_t st) {
-    auto kern = gemm1x1_persistent_kernel<BM, BN, WM, WN>;
-    auto kern2 = gemm1x1_persistent2_kernel<BM, BN, WM, WN>;
-    constexpr int smem = conv_smem_floats(BM, BN) * (int)sizeof(float);
-    static std::atomic<unsigned> configured{0};
-    if (int rc = ensure_dynamic_lds(D2 ? reinterpret_cast<const void*>(kern2) : reinterpret_cast<const void*>(kern), smem, configured, "gemm1x1_persistent")) return rc;
-    ConvParams q = p;
-    q.n_tiles = p.CoutPad / BN;
-    q.m_tiles = cdiv(p.M, BM);
-    const int total = q.m_tiles * q.n_tiles;
-    int grid = 512;                            // two resident blocks per CU
-    if (grid > total) grid = (total + 7) / 8 * 8;
-#ifdef VATL_ABLATION
-    q.ablate = g_ablate.load(std::memory_order_relaxed);
-    if (q.ablate & 4) q.y_bytes = 0;           // every output store (and residual load) out of range: dropped, no HBM writes
-    if (q.ablate & 8) q.x_bytes = 0;           // every activation load out of range: zeros, no HBM reads
-    if ((q.ablate & 2) && q.ktiles > 2) { q.ktiles = 2; }
-#endif
-    if (D2) hipLaunchKernelGGL(kern2, dim3((unsigned)grid), dim3(256), smem, st, q);
-    else    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), smem, st, q);
-    meter_add(0, 2.0 * ((double)q.m_tiles * BM) * ((double)q.n_tiles * BN) * ((double)q.ktiles * BK));
-    meter_route(kRoutePersistent1x1);
-    return check_launch("gemm1x1_persistent");
-}
-
-template <int BM, int BN, int WM, int WN>
-static int launch_persistent(const ConvParams& p, hipStream_t st) {
-    const bool d2 = g_persist_dist.load(std::memory_order_relaxed) == 2 && p.ktiles >= 2 && (p.ktiles & 1) == 0;
-    return d2 ? launch_persistent_impl<BM, BN, WM, WN, true>(p, st) : launch_persistent_impl<BM, BN, WM, WN, false>(p, st);
-}
-
-static std::atomic<int> g_persist{1};  // vatl_tune_set(7, v): persistent kernel for 1x1 layers with K <= 256 v (0 = off)
-static std::atomic<int> g_ring{1};     // LDS-DMA ring kernel for the long-K 1x1 layers; 0 = off: vatl_tune_set(27, 0), profiling variant only (same-box A/B)
-
-template <bool DUAL, bool RES>
-static int launch_ring_impl(const ConvParams& p, hipStream_t st) {
-    auto kern = gemm1x1_ring_kernel<DUAL, RES>;
-    static std::atomic<unsigned> configured{0};
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), RING_BYTES, configured, "gemm1x1_ring")) return rc;
-    ConvParams q = p;
-    q.n_tiles = p.CoutPad / 128;
-    q.m_tiles = cdiv(p.M, 128);
-    q.splits = 1;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(q.m_tiles * q.n_tiles)), dim3(256), RING_BYTES, st, q);
-    meter_add(0, 2.0 * ((double)q.m_tiles * 128) * ((double)q.n_tiles * 128) * ((double)q.ktiles * BK));
-    meter_route(kRouteGemm1x1Ring);
-    return check_launch("gemm1x1_ring");
-}
-
-static int launch_ring(const ConvParams& p, hipStream_t st) {
-    if (p.x2) return launch_ring_impl<true, false>(p, st);           // (the dual form has no residual: ring_wanted)
-    return p.res ? launch_ring_impl<false, true>(p, st) : launch_ring_impl<false, false>(p, st);
-}
-
-// The ring kernel serves whole 128 x 128 tiles of a stride-1 1x1 layer (or the dual-source form) with K a multiple of 64 and at least
-// 16 k-tiles (12 for the dual form, whose x / x2 boundary falls on a multiple of 64 channels), NHWC output, Cout == CoutPad, no training epilogue (statistics / BatchNorm backward) and no
-// split-K workspace; (M + 128) * Cout < 2^30 so that the byte offsets of the tail tile's dropped rows do not wrap.  Default schedule only
-// (knob 0 = 4: the other schedules keep the tiled kernel).  The fine-tune step's data-gradient launches without a BatchNorm-backward
-// epilogue are plain 1x1 GEMMs as well and take it where their shape qualifies (same bits).
-static bool ring_wanted(const ConvParams& p, int phases, int bn, int bm, int var) {
-    if (!g_ring.load(std::memory_order_relaxed) || var != 4 || phases != 1 || bn != 128 || bm != 128) return false;
-    if (p.R != 1 || p.S != 1 || p.stride != 1 || p.pad_y || p.pad_x || p.out_nchw || p.deconv || p.stats || p.bz) return false;
-    if (p.osy != 1 || p.osx != 1 || p.OH != p.Ho || p.OW != p.Wo || p.H != p.Ho || p.W != p.Wo) return false;
-    if (p.Cout != p.CoutPad || (p.ktiles & 1) || p.ktiles < (p.x2 ? 12 : 16)) return false;
-    // dual form: the x / x2 boundary on a whole group of four stages, at least one group of each source (the prologue's three stages
-    // read x), no residual (vatl_conv1x1_dual_fwd has none)
-    if (p.x2 && (p.res || p.k1 < 2 || (p.k1 & 1) || p.ktiles - p.k1 < 2)) return false;
-    if ((long long)(p.M + 128) * p.Cout >= (1LL << 30)) return false;
-    long long ws_floats = 0;
-    int sk_policy = 0;
-    return splitk_workspace(&ws_floats, &sk_policy) == nullptr;
-}
-
-// Stream-K workspace of the calling host thread (vatl_set_streamk_workspace_thread): [1024 flag words][kStreamKGrid slabs of 64 x 128
-// floats].  Thread-local like the split-K one: replica threads never share slabs, and a thread that registered nothing (every
-// inference path) never takes this route.
-constexpr int kStreamKGrid = 768;                 // three resident 64x128 blocks on each of the 256 CUs
-constexpr long long kStreamKBytes = 4096 + (long long)kStreamKGrid * 64 * 128 * 4;
-static thread_local char* tl_streamk_ws = nullptr;
-static thread_local unsigned tl_streamk_epoch = 0;
-static std::atomic<int> g_streamk{1};             // vatl_tune_set(12, v): 0 = never take the stream-K route
-
-template <bool BNB>
-static int launch_streamk(const ConvParams& p, hipStream_t st) {
-    auto kern = conv_streamk_kernel<64, 128, 32, 64, BNB>;
-    constexpr int smem = conv_smem_floats(64, 128) * (int)sizeof(float);
-    static std::atomic<unsigned> configured{0};
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, configured, "conv_streamk")) return rc;
-    ConvParams q = p;
-    q.n_tiles = p.CoutPad / 128;
-    q.m_tiles = cdiv(p.M, 64);
-    q.splits = 1;
-    StreamKArgs sk{};
-    sk.flags = reinterpret_cast<unsigned*>(tl_streamk_ws);
-    sk.slabs = reinterpret_cast<float*>(tl_streamk_ws + 4096);
-    sk.epoch = ++tl_streamk_epoch;
-    if (sk.epoch == 0) sk.epoch = ++tl_streamk_epoch;          // 0 is the "never written" value of a fresh workspace
-    sk.tiles = q.m_tiles * q.n_tiles;
-    hipLaunchKernelGGL(kern, dim3(kStreamKGrid), dim3(256), smem, st, q, sk);
-    meter_add(0, 2.0 * ((double)q.m_tiles * 64) * ((double)q.n_tiles * 128) * ((double)q.ktiles * BK));
-    meter_route(kRouteStreamK);
-    return check_launch("conv_streamk");
-}
-
-// Whole-tile launches that leave a large part of the chip idle take the stream-K route (64x128 tiles only: the tile the
-// dispatcher picks for small launches): fewer than 85 % of the block slots busy over the launch's rounds, a reduction long
-// enough to cut (>= 8 k-tiles) and at least 6 k-tiles of work per block.
-static bool streamk_wanted(const ConvParams& p, int phases, int bn, int bm, bool stem) {
-    if (!tl_streamk_ws || !g_streamk.load(std::memory_order_relaxed) || stem || phases != 1 || bn != 128 || bm != 64 || p.x2 || p.out_nchw || p.deconv ||
-        (p.Cout & 3) || p.ktiles < 8)
-        return false;
-    const long long tiles = (long long)cdiv(p.M, 64) * (p.CoutPad / 128);
-    const long long rounds = (tiles + kStreamKGrid - 1) / kStreamKGrid;
-    if (tiles * 100 >= rounds * kStreamKGrid * 85) return false;
-    return tiles * p.ktiles >= 6LL * kStreamKGrid && tiles >= 64;
-}
-
 // CoutPad granularity the packer must honour for a given Cout.
 static int tile_n_for(int Cout) { return Cout <= 32 ? 32 : (Cout <= 64 ? 64 : 128); }
 
@@ -1814,11 +732,7 @@ static int dispatch(const ConvParams& p_in, int phases, bool stem, hipStream_t s
         return launch<64, 64, 32, 32, false, 4>(p, phases, st);
     }
     // short-K 1x1 / stride-1 layers on whole 128x128 tiles: the persistent GEMM kernel
-    const int pk = g_persist.load(std::memory_order_relaxed);
-    if (pk && bn == 128 && var == 4 && phases == 1 && p.R == 1 && p.S == 1 && p.stride == 1 && p.pad_y == 0 && !p.out_nchw && !p.deconv &&
-        p.osy == 1 && p.osx == 1 && p.OH == p.Ho && p.OW == p.Wo && (p.Cout & 3) == 0 && p.ktiles <= pk * 8 && !p.x2 &&
-        (long long)(p.M + 128) * p.K < (1LL << 30))
-        return launch_persistent<128, 128, 64, 64>(p, st);
+    if (persistent_wanted(p, phases, bn, var)) return launch_persistent(p, st);
     // long-K 1x1 layers on whole 128x128 tiles: the LDS-DMA ring kernel
     if (ring_wanted(p, phases, bn, bm, var)) return launch_ring(p, st);
     if (bn == 128 && var == 5) return launch_dma<128, 128, 64, 64>(p, phases, st);
@@ -1849,86 +763,12 @@ static int dispatch(const ConvParams& p_in, int phases, bool stem, hipStream_t s
 
 }  // namespace vatl
 
-namespace vatl {
-int conv3x3_halo_try(const float* x, const float* w, const float* scale, const float* bias, const float* residual, float* y, int N, int H, int W,
-                     int Cin, int Cout, int CoutPad, int R, int S, int stride, int pad, int relu, hipStream_t st);   // conv3x3_halo.hip
-int conv3x3_halo_enable(int on);
-int wino_set_ablate(int bits);                                 // conv_winograd.hip
-int wino_set_group_kb(int v);
-int wino_set_halves(int v);
-int wino_set_persist(int v);
-int wino_wgrad_set_halves(int v);
-int wino_wgrad_set_table(int v);
-int wino_set_persist_pf(int v);
-int wino_wgrad_set_blocks(int v);                              // winograd_wgrad.hip
-
-}
-
 using namespace vatl;
-
-namespace vatl {                                              // internal hooks behind vatl_tune_set (not part of the C ABI: hidden, C++ linkage)
-__attribute__((visibility("hidden"))) int tune_wgrad_blocks(int blocks);   // conv_wgrad.hip
-__attribute__((visibility("hidden"))) int crop_tune_px(int px);            // crop.hip
-}
-
-extern "C" int vatl_tune_set(int knob, int value) {
-    // PRODUCT KNOBS — process-global route selectors (relaxed atomics; set them before launching from several threads).  Every accepted
-    // value computes the SAME BITS as the default (tests/test_gpu_conv.py, tests/test_gpu_winograd.py assert it per knob); the table in
-    // include/vatl_hip.h is the contract.  Nothing else is accepted by the shipped library.
-    switch (knob) {
-    case 0:  if (value == 0 || value == 2 || value == 4 || value == 5) { g_var.store(value, std::memory_order_relaxed); return 0; } break;
-    case 1:  if (value == 0 || value == 1) { g_order.store(value, std::memory_order_relaxed); return 0; } break;
-    case 5:  if (value == 0 || value == 64 || value == 128) { g_bm.store(value, std::memory_order_relaxed); return 0; } break;
-    case 7:  if (value >= 0 && value <= 64) { g_persist.store(value, std::memory_order_relaxed); return 0; } break;
-    case 8:  if (value == 0 || value == 1) return conv3x3_halo_enable(value); break;
-    case 10: if (value == 1 || value == 2) { g_persist_dist.store(value, std::memory_order_relaxed); return 0; } break;
-    case 18: if (value >= 0 && value <= (1 << 20)) return wino_set_group_kb(value); break;
-    case 21: if (value >= 1 && value <= 3) return wino_set_halves(value); break;
-    case 22: if (value >= 0 && value <= 4096) return wino_set_persist(value); break;
-    case 24: if (value >= 0 && value <= 3) return wino_set_persist_pf(value); break;
-    case 25: if (value == 0 || value == 1) return wino_wgrad_set_table(value); break;
-    default: break;
-    }
-#ifdef VATL_ABLATION
-    // PROFILING VARIANT ONLY (build.py --ablation -> libvatl_hip_ablation.so): knobs that change the summation order (3, 9, 12, 19) or are not pinned bit-identical (23), performance-only
-    // experiments (2, 16, 27) and the ablations that compute WRONG results by construction (0: 10..13, 4, 6, 17; these also need VATL_ALLOW_ABLATION=1).
-    const bool wrong = (knob == 0 && value >= 10) || ((knob == 4 || knob == 6 || knob == 17) && value != 0);
-    if (wrong) {
-        const char* ok = getenv("VATL_ALLOW_ABLATION");
-        if (!ok || ok[0] != '1') return fail(VATL_EINVAL, "tune_set: knob %d value %d is a profiling ablation (wrong results); set VATL_ALLOW_ABLATION=1", knob, value);
-    }
-    if (knob == 0 && value >= 10 && value <= 13) { g_var.store(value, std::memory_order_relaxed); return 0; }
-    if (knob == 2 && value >= 0 && value <= 200) { g_stagger.store(value, std::memory_order_relaxed); return 0; }
-    if (knob == 3 && tune_wgrad_blocks(value) == 0) return 0;
-    if (knob == 4 && value >= 0 && value <= 3) return tune_wgrad_blocks(-value - 1);
-    if (knob == 6 && value >= 0 && value <= 15) { g_ablate.store(value, std::memory_order_relaxed); return 0; }
-    if (knob == 9 && (value == 0 || value == 1)) { g_splitk_policy.store(value, std::memory_order_relaxed); return 0; }
-    if (knob == 12 && (value == 0 || value == 1)) { g_streamk.store(value, std::memory_order_relaxed); return 0; }
-    if (knob == 16 && crop_tune_px(value) == 0) return 0;
-    if (knob == 17 && value >= 0 && value <= 63) return wino_set_ablate(value);
-    if (knob == 19 && value >= 1 && value <= (1 << 20)) return wino_wgrad_set_blocks(value);
-    if (knob == 23 && value >= 1 && value <= 2) return wino_wgrad_set_halves(value);
-    if (knob == 27 && (value == 0 || value == 1)) { g_ring.store(value, std::memory_order_relaxed); return 0; }
-    return fail(VATL_EINVAL, "tune_set: unknown knob %d / value %d", knob, value);
-#else
-    return fail(VATL_EINVAL, "tune_set: knob %d / value %d is not a product knob (include/vatl_hip.h lists them: 0, 1, 5, 7, 8, 10, 18, 21, 22, 24, 25 — all bit-identical); "
-                "knobs that change the summation order, performance experiments and profiling ablations exist only in the variant built with "
-                "`build.py --ablation` (-DVATL_ABLATION)", knob, value);
-#endif
-}
 
 extern "C" int vatl_set_splitk_workspace_thread(float* workspace, int64_t floats) {
     if (workspace && floats <= 0) return fail(VATL_EINVAL, "set_splitk_workspace_thread: empty workspace");
     tl_splitk_ws = workspace;
     tl_splitk_floats = workspace ? (long long)floats : 0;
-    return 0;
-}
-
-extern "C" int64_t vatl_streamk_workspace_bytes(void) { return kStreamKBytes; }
-
-extern "C" int vatl_set_streamk_workspace_thread(void* workspace, int64_t bytes) {
-    if (workspace && bytes < kStreamKBytes) return fail(VATL_EINVAL, "set_streamk_workspace_thread: %lld bytes, need %lld", (long long)bytes, kStreamKBytes);
-    tl_streamk_ws = static_cast<char*>(workspace);
     return 0;
 }
 

@@ -13,6 +13,8 @@
 // natural NHWC layout), so one ds_read_b32 per operand tile feeds an MFMA k-step (lanes 0-31 take
 // pixel 2s, lanes 32-63 pixel 2s+1).  v_mfma_f32_32x32x2_f32, exact fp32.
 #include "common.h"
+#include "buffer.h"
+#include "tune.h"
 
 #include <atomic>
 
@@ -39,10 +41,6 @@ struct WgradParams {
 };
 
 constexpr unsigned WG_OOB = 0xFFFFFFFFu;
-typedef unsigned int wu32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 wg_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
 
 // BN: rows (n) per block, BJ: cols (channels of one tap) per block; wave tile WN x WJ; STEM: Cx = 4, one
 // block column = one filter row (8 taps x 4 channels)
@@ -78,8 +76,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p) {
     const int kt1 = min(kt0 + p.kt_per_split, p.ktiles);
     if (kt0 >= kt1) return;
 
-    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.g), 0, p.g_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t gr = buf_rsrc(p.g, p.g_bytes);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
     const int HoWo = p.Ho * p.Wo;
 
     // Operand addresses advance by 32 pixels per k-tile.  G (plain rows): one add, rows >= M fall outside the buffer
@@ -117,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p) {
     auto gload = [&]() {                                   // loads the next k-tile and advances the pixel state
 #pragma unroll
         for (int q = 0; q < LG; ++q) {
-            rg[q] = wg_load4(gr, goff[q]);
+            rg[q] = buf_load4(gr, goff[q]);
             goff[q] += gadv[q];
         }
 #pragma unroll
@@ -125,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p) {
             const int iy = xoy[q] * p.stride + iyb;
             const int ix = xox[q] * p.stride + ixb + (STEM ? (int)((tid + 256 * q) % (BJ / 4)) : 0);
             const bool ok = xcv[q] && xm[q] < p.M && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-            rx[q] = wg_load4(xr, ok ? (unsigned)xoff[q] << 2 : WG_OOB);
+            rx[q] = buf_load4(xr, ok ? (unsigned)xoff[q] << 2 : WG_OOB);
             xm[q] += 32; xoy[q] += p.d_oy; xox[q] += p.d_ox; xoff[q] += p.adv;
             if (xox[q] >= p.Wo) { xox[q] -= p.Wo; ++xoy[q]; xoff[q] += p.adv_cx; }
             if (xoy[q] >= p.Ho) { xoy[q] -= p.Ho; xoff[q] += p.adv_cy; }
@@ -345,7 +343,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 using namespace vatl;
 
 namespace vatl {
-__attribute__((visibility("hidden"))) int tune_wgrad_blocks(int blocks) {       // reached through vatl_tune_set(3, blocks) / (4, bits) of the profiling variant only
+int tune_wgrad_blocks(int blocks) {       // reached through vatl_tune_set(3, blocks) / (4, bits) of the profiling variant only
     if (blocks < 0) { g_wgrad_ablate.store(-blocks - 1, std::memory_order_relaxed); return 0; }
     if (blocks < 64 || blocks > 65536) return -1;
     g_wgrad_blocks.store(blocks, std::memory_order_relaxed);

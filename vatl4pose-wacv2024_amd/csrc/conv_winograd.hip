@@ -39,6 +39,8 @@
 //     BatchNorm-backward reduction of the fine-tune step's data gradients fused.
 // The per-output arithmetic depends only on the tile's own pixels: results are independent of the batch position (SURVEY.md §7 hard part 3).
 #include "common.h"
+#include "buffer.h"
+#include "tune.h"
 #include "winograd_pack.h"
 
 #include <algorithm>
@@ -54,7 +56,7 @@ struct WinoParams {
     const float* res;
     float* y;
     double* stats;
-    // BatchNorm-backward fusion (data-gradient launches of the fine-tune step; semantics of ConvParams::bz.. in conv_igemm.hip): the
+    // BatchNorm-backward fusion (data-gradient launches of the fine-tune step; semantics of ConvParams::bz.. in conv_igemm.h): the
     // tile being stored is dL/dy of a Conv+BN(+ReLU) layer whose conv output is bz; the epilogue applies that layer's ReLU mask, stores
     // the masked gradient g and accumulates (sum g, sum g*xhat) into `stats`
     const float* bz;
@@ -95,14 +97,6 @@ struct WinoParams {
 constexpr unsigned WOOB_BASE = 0xF0000000u;               // out of range for every descriptor, and still so with a fragment offset added
 constexpr unsigned WOOB = 0xFFFFFFFFu;
 constexpr unsigned WOOB_G = 0xFFFF0000u;                  // staging offset of a zero piece: still out of range with stage * 64 bytes added (stages < 1024, tensors <= 0xFFFF0000 bytes: checked on the host), so the per-stage offset needs no select
-typedef unsigned int wu32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 wbuf_load4(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
-}
-__device__ __forceinline__ void wbuf_store4(__amdgpu_buffer_rsrc_t r, unsigned byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wu32x4, v), r, byte_off, 0, 0);
-}
 
 constexpr int W_TB = 32;                        // tiles per block
 constexpr int W_CK = 16;                        // channels per LDS stage
@@ -119,8 +113,6 @@ template <int MO> struct WinoStage {
     static constexpr int FLOATS = NDMA * 256;
     static constexpr int NLD = (NDMA + 3) / 4;             // per wave
 };
-
-typedef __attribute__((address_space(3))) void wlds_void;
 
 // (body in a __device__ function: with the DMA builtin inside the __global__ template hipcc 7.2 drops the kernel's host stub)
 template <int MO, bool BNB, bool GATHER, int NB>
@@ -155,8 +147,8 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
         pad_y = 1 - py; pad_x = 1 - px; ooy = py; oox = px;
         ubase_ptr += (long long)phase * p.u_phase_floats;
     }
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ubase_ptr), 0, p.u_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t ur = buf_rsrc(ubase_ptr, p.u_bytes);
 
 #ifdef VATL_ABLATION
     const int abl = p.ablate;
@@ -173,7 +165,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
         const int hn0 = n_tile * NB, ut0 = hn0 / p.nhp;
         const unsigned u0 = (unsigned)((((ut0 * p.stages * 2) * 16 + 4 * xi) * p.nhp + (hn0 - ut0 * p.nhp)) * 64 + lane) << 4;
 #pragma unroll
-        for (int nu = 0; nu < 4; ++nu) ua[nu] = wbuf_load4(ur, (abl & 4) ? WOOB : u0 + nu * (p.nhp * 1024u));
+        for (int nu = 0; nu < 4; ++nu) ua[nu] = buf_load4(ur, (abl & 4) ? WOOB : u0 + nu * (p.nhp * 1024u));
     }
 
     // ---- staging by LDS-DMA (buffer_load ... lds: no staging registers, no ds_write pass).  The destination of a wave instruction is
@@ -228,7 +220,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
 #pragma unroll
         for (int u = 0; u < W_NLD; ++u)
             if (xi + NW * u < ST::NDMA)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (wlds_void*)(Rs + buf * STAGE + (xi + NW * u) * 256), 16,
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void*)(Rs + buf * STAGE + (xi + NW * u) * 256), 16,
                                                          goff[u] + (unsigned)cst * (W_CK * 4), 0, 0, 0);
     };
 
@@ -287,7 +279,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
         }
         if (abl & 4) off = WOOB_BASE;                      // (profiling ablation; abl is 0 in the product build)
 #pragma unroll
-        for (int nu = 0; nu < 4; ++nu) dst[nu] = wbuf_load4(ur, off + nu * unu);
+        for (int nu = 0; nu < 4; ++nu) dst[nu] = buf_load4(ur, off + nu * unu);
     };
 
     f32x16 accs[NB][4];
@@ -357,7 +349,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
             }
             if (abl & 4) off = WOOB_BASE;
 #pragma unroll
-            for (int nu = 0; nu < 4; ++nu) dst[nu] = wbuf_load4(ur, off + nu * unu);
+            for (int nu = 0; nu < 4; ++nu) dst[nu] = buf_load4(ur, off + nu * unu);
         };
         for (int st = 0; st < p.stages; ++st) {
             const int buf = st & 1;
@@ -437,10 +429,10 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
         // ---- output transform -----------------------------------------------------------------------------------------------------------------
         // What the write-out needs from global memory (store offsets, skip-connection values, per-channel constants) is requested FIRST, so
         // that it is in flight while the accumulators go through LDS: at the end of the block these latencies are not hidden by anything else.
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res), 0, p.res ? p.y_bytes : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t zr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(BNB ? p.bz : p.x), 0, BNB ? p.y_bytes : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t mr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(BNB ? p.bmy : p.x), 0, (BNB && p.bmy) ? p.y_bytes : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
+        const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res, p.res ? p.y_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t zr = buf_rsrc(BNB ? p.bz : p.x, BNB ? p.y_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t mr = buf_rsrc(BNB ? p.bmy : p.x, (BNB && p.bmy) ? p.y_bytes : 0u);
         const int c4 = tid % C4;
         const int n = n0h + c4 * 4;
         const bool nv = n < p.Cout;
@@ -479,10 +471,10 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
                 }
             }
     #pragma unroll
-            for (int a = 0; a < MO; ++a) rs[u][a] = p.res ? wbuf_load4(rr, off[u][a]) : nul;
+            for (int a = 0; a < MO; ++a) rs[u][a] = p.res ? buf_load4(rr, off[u][a]) : nul;
             if constexpr (EARLY_Z) {
     #pragma unroll
-                for (int a = 0; a < MO; ++a) { zq[u][a] = wbuf_load4(zr, off[u][a]); yq[u][a] = p.bmy ? wbuf_load4(mr, off[u][a]) : nul; }
+                for (int a = 0; a < MO; ++a) { zq[u][a] = buf_load4(zr, off[u][a]); yq[u][a] = p.bmy ? buf_load4(mr, off[u][a]) : nul; }
             }
         }
         };
@@ -536,7 +528,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
     #pragma unroll
                 for (int a = 0; a < MO; ++a) {
                     if constexpr (EARLY_Z) { zt[a] = zq[u][a]; yt[a] = yq[u][a]; }
-                    else { zt[a] = wbuf_load4(zr, off[u][a]); yt[a] = p.bmy ? wbuf_load4(mr, off[u][a]) : nul; }
+                    else { zt[a] = buf_load4(zr, off[u][a]); yt[a] = p.bmy ? buf_load4(mr, off[u][a]) : nul; }
                 }
     #pragma unroll
                 for (int a = 0; a < MO; ++a) {
@@ -549,7 +541,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
                         ssum[c] += gq[c];
                         ssq[c] += gq[c] * ((zt[a][c] - mu[c]) * is[c]);
                     }
-                    wbuf_store4(yr, off[u][a], gq);
+                    buf_store4(yr, off[u][a], gq);
                 }
             } else {
     #pragma unroll
@@ -557,7 +549,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
                     f32x4 o;
     #pragma unroll
                     for (int c = 0; c < 4; ++c) o[c] = fmaxf(yv[a][c] * sc[c] + bi[c] + rs[u][a][c], lo);
-                    wbuf_store4(yr, off[u][a], o);
+                    buf_store4(yr, off[u][a], o);
                     if (p.stats && off[u][a] != WOOB) {
     #pragma unroll
                         for (int c = 0; c < 4; ++c) { ssum[c] += o[c]; ssq[c] += o[c] * o[c]; }
@@ -635,7 +627,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
     static_assert(W_NLD <= 5, "geometry record layout");
     constexpr int PS_FLOATS = 4 * MO * W_TB * W_LDP;
     float* const Ps = PF ? smem + W_ZERO + 2 * STAGE : smem;                     // output-transform tiles [xi][b][tile][32 channels]
-    wu32x4* Gs = reinterpret_cast<wu32x4*>(smem + W_ZERO + 2 * STAGE + (PF ? PS_FLOATS : 0));   // [3][256 threads] x 16 bytes: goff[0..3] | goff[4], ra[0..3] as 16-bit pairs | off[0..3]
+    u32x4* Gs = reinterpret_cast<u32x4*>(smem + W_ZERO + 2 * STAGE + (PF ? PS_FLOATS : 0));   // [3][256 threads] x 16 bytes: goff[0..3] | goff[4], ra[0..3] as 16-bit pairs | off[0..3]
     unsigned g0[8] = {WOOB_G, WOOB_G, WOOB_G, WOOB_G, WOOB_G, WOOB_G, WOOB_G, WOOB_G};
 #pragma unroll
     for (int u = 0; u < W_NLD; ++u) {
@@ -660,7 +652,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
         if (m < Lt && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W)
             g0[u] = (unsigned)(((b * p.H + yy) * p.W + xx) * p.Cin + chunk * 4) << 2;
     }
-    Gs[tid] = wu32x4{g0[0], g0[1], g0[2], g0[3]};
+    Gs[tid] = u32x4{g0[0], g0[1], g0[2], g0[3]};
     // ---- fragment addressing ----
     const int h = lane >> 5;
     {
@@ -674,7 +666,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
             const int q = tl + j / MO;
             ra[j] = (unsigned)xx < (unsigned)p.W ? ((j % MO) * W_NQ + q) * W_CK + ((h ^ ((q >> 2) & 3)) << 2) : MO * W_NQ * W_CK + (h << 2);
         }
-        Gs[NT + tid] = wu32x4{g0[4], ((unsigned)ra[0] & 0xFFFFu) | ((unsigned)ra[1] << 16), ((unsigned)ra[2] & 0xFFFFu) | ((unsigned)ra[3] << 16), 0u};
+        Gs[NT + tid] = u32x4{g0[4], ((unsigned)ra[0] & 0xFFFFu) | ((unsigned)ra[1] << 16), ((unsigned)ra[2] & 0xFFFFu) | ((unsigned)ra[3] << 16), 0u};
     }
     const int ia = xi == 0 ? 0 : (xi == 2 ? 2 : 1);
     const int ib = xi == 0 ? 2 : (xi == 1 ? 2 : (xi == 2 ? 1 : 3));
@@ -687,12 +679,12 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
     const int ut = hn / p.nhp, nh_g = hn - ut * p.nhp;
     const unsigned ubase = (unsigned)((((ut * steps) * 16 + 4 * xi) * p.nhp + nh_g) * 64 + lane) << 4;
     const unsigned ustep = 16u * p.nhp * 1024u, unu = p.nhp * 1024u;
-    const __amdgpu_buffer_rsrc_t ur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u), 0, p.u_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ur = buf_rsrc(p.u, p.u_bytes);
     // ---- write-out: per pass u the thread's (tile, output column, channel quad); store offsets of the first filter half (the second: + 128 bytes) ----
     constexpr int C4 = 32 / 4;
     const int c4 = tid % C4;
     {
-        wu32x4 o4;
+        u32x4 o4;
 #pragma unroll
         for (int u = 0; u < MO; ++u) {
             const int rest = (tid + NT * u) / C4;
@@ -726,17 +718,17 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
         const int step = min(step_, steps - 1);            // (past the last step: the last step's fragments again, no per-lane select)
         const unsigned o = ubase + (unsigned)half * 1024u + (unsigned)step * ustep;
 #pragma unroll
-        for (int nu = 0; nu < 4; ++nu) dst[nu] = wbuf_load4(ur, o + nu * unu);
+        for (int nu = 0; nu < 4; ++nu) dst[nu] = buf_load4(ur, o + nu * unu);
     };
 
     // requests of a period's first two stages + first filter fragments (PF: issued during the write-out of the period before)
     f32x4 ua[4], ub[4];
     auto first_requests = [&](int it) {
-        const __amdgpu_buffer_rsrc_t xq = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (long long)it * p.x_period_floats), 0, p.x_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xq = buf_rsrc(p.x + (long long)it * p.x_period_floats, p.x_bytes);
         u_load_h(ua, 0, 0);
         int tid_p = tid;
         asm volatile("" : "+v"(tid_p));
-        const wu32x4 ga = Gs[tid_p], gb = Gs[NT + tid_p];
+        const u32x4 ga = Gs[tid_p], gb = Gs[NT + tid_p];
         unsigned goff[5];
 #pragma unroll
         for (int k = 0; k < 4; ++k) goff[k] = ga[k];
@@ -747,7 +739,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
 #pragma unroll
                 for (int u = 0; u < W_NLD; ++u)
                     if (xi + NW * u < ST::NDMA)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(xq, (wlds_void*)(Rs + st * STAGE + (xi + NW * u) * 256), 16,
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(xq, (lds_void*)(Rs + st * STAGE + (xi + NW * u) * 256), 16,
                                                                  goff[u] + (unsigned)st * (W_CK * 4), 0, 0, 0);
             }
     };
@@ -761,12 +753,12 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
         const float* xb = p.x + (long long)it * p.x_period_floats;
         float* yb = p.y + (long long)it * p.y_period_floats;
         const float* rb = p.res ? p.res + (long long)it * p.y_period_floats : nullptr;
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, p.x_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr = buf_rsrc(xb, p.x_bytes);
         int tid_o = tid;
         asm volatile("" : "+v"(tid_o));                    // (opaque: the reads below are per period, not hoisted)
         int ra[4];
         {
-            const wu32x4 gc = Gs[NT + tid_o];
+            const u32x4 gc = Gs[NT + tid_o];
             ra[0] = (int)(short)(gc[1] & 0xFFFFu); ra[1] = (int)(short)(gc[1] >> 16);
             ra[2] = (int)(short)(gc[2] & 0xFFFFu); ra[3] = (int)(short)(gc[2] >> 16);
         }
@@ -784,7 +776,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
         auto stage_dma = [&](int buf, int st) {            // (the staging offsets are read from the record at every use: 5 fewer registers live across the stage loop)
             int tid_p = tid_o;
             asm volatile("" : "+v"(tid_p));
-            const wu32x4 ga = Gs[tid_p], gb = Gs[NT + tid_p];
+            const u32x4 ga = Gs[tid_p], gb = Gs[NT + tid_p];
             unsigned goff[5];
 #pragma unroll
             for (int k = 0; k < 4; ++k) goff[k] = ga[k];
@@ -792,7 +784,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
 #pragma unroll
             for (int u = 0; u < W_NLD; ++u)
                 if (xi + NW * u < ST::NDMA)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (wlds_void*)(Rs + buf * STAGE + (xi + NW * u) * 256), 16,
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void*)(Rs + buf * STAGE + (xi + NW * u) * 256), 16,
                                                              goff[u] + (unsigned)st * (W_CK * 4), 0, 0, 0);
         };
         if constexpr (!PF) {
@@ -861,12 +853,12 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
             }
         }
 
-        const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(yb, 0, p.y_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rb), 0, rb ? p.y_bytes : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t yr = buf_rsrc(yb, p.y_bytes);
+        const __amdgpu_buffer_rsrc_t rr = buf_rsrc(rb, rb ? p.y_bytes : 0u);
         // (the write-out's LDS addresses are formed from the opaque copy of the thread id too: as loop invariants hipcc would keep all ~40 of
         // them in registers across the MFMA loop)
         const int lane_o = tid_o & 63, c4o = tid_o % C4;
-        const wu32x4 o4 = Gs[2 * NT + tid_o];
+        const u32x4 o4 = Gs[2 * NT + tid_o];
         unsigned off[MO][MO];
 #pragma unroll
         for (int u = 0; u < MO; ++u)
@@ -884,7 +876,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
             for (int u = 0; u < MO; ++u)
 #pragma unroll
                 for (int a = 0; a < MO; ++a)
-                    rs[u][a] = rb ? wbuf_load4(rr, (nvh[hh] && off[u][a] != WOOB) ? off[u][a] + hoff : WOOB) : nul;
+                    rs[u][a] = rb ? buf_load4(rr, (nvh[hh] && off[u][a] != WOOB) ? off[u][a] + hoff : WOOB) : nul;
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (PF) {                            // the stage buffers are free (barrier after the last stage), this half's skip-connection values are requested
                 if (hh == 0 && it + 1 < it1) first_requests(it + 1);
@@ -916,7 +908,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
                     f32x4 o;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) o[c] = fmaxf(yv[a][c] * sc[c] + bi[c] + rs[u][a][c], lo);
-                    wbuf_store4(yr, (nvh[hh] && off[u][a] != WOOB) ? off[u][a] + hoff : WOOB, o);
+                    buf_store4(yr, (nvh[hh] && off[u][a] != WOOB) ? off[u][a] + hoff : WOOB, o);
                 }
             }
             lds_barrier();                                 // the next half's / the next period's stage goes where these tiles were read (the stores stay in flight)

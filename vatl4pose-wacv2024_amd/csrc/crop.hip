@@ -11,6 +11,7 @@
 // loads + a funnel shift instead of the unaligned 8-byte ones changed nothing, lanes along the output row (2 - 4 cache lines per gather
 // instead of ~15, but four times the store instructions) was 15 % slower.
 #include "common.h"
+#include "tune.h"
 
 #include <atomic>
 
@@ -172,7 +173,7 @@ using namespace vatl;
 
 static std::atomic<int> g_crop_px{8};          // pixels per thread of the warp kernel (vatl::crop_tune_px, profiling variant only: 4 or 8; identical results)
 namespace vatl {
-__attribute__((visibility("hidden"))) int crop_tune_px(int px) { if (px != 4 && px != 8) return -1; g_crop_px.store(px, std::memory_order_relaxed); return 0; }
+int crop_tune_px(int px) { if (px != 4 && px != 8) return -1; g_crop_px.store(px, std::memory_order_relaxed); return 0; }
 }
 
 extern "C" int vatl_crop_warp_affine(const uint8_t* arena, const int64_t* src_off, const int32_t* src_hwf, const double* minv, float* out,

@@ -10,6 +10,7 @@
 // One block of eight waves per CU (two per SIMD); a wave stages its own 6 x 18-pixel input patch by LDS-DMA (16 channels at a time: 7 KB) and never meets a barrier
 // after the filter is in LDS.  Per K-step a wave issues 16 + 8 LDS reads and ~50 vector instructions around 32 MFMAs of 32 cycles.
 #include "common.h"
+#include "buffer.h"
 
 #include <atomic>
 
@@ -28,7 +29,6 @@ struct C32Params {
     FastDivU d_upi, d_uw;
 };
 
-typedef __attribute__((address_space(3))) void c32_lds_void;
 constexpr unsigned C32_OOB = 0xFFFFFFF0u;
 constexpr int C32_U_FLOATS = 8 * 2 * 64 * 16;     // 16384
 constexpr int C32_PATCH = 7 * 256;                // floats of a wave's patch buffer: 6 x 18 pixels x 16 channels = 432 16-byte chunks, 7 requests of 64
@@ -50,9 +50,9 @@ __global__ __launch_bounds__(512, 1) void winograd_c32_kernel(C32Params p) {
     if (tid < 32) { SBs[tid] = p.scale ? p.scale[tid] : 1.f; SBs[32 + tid] = p.bias ? p.bias[tid] : 0.f; }
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.y), 0, p.res ? p.bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.bytes);
+    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res ? p.res : p.y, p.res ? p.bytes : 0u);
 
     // ---- per-lane constants ----
     // staging: request j writes LDS chunks 64 j .. 64 j + 63; chunk id = pixel * 4 + position, position = source quad ^ ((patch column >> 2) & 3): the 16 tiles
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(512, 1) void winograd_c32_kernel(C32Params p) {
 #pragma unroll
         for (int j = 0; j < 7; ++j) {
             const unsigned off = (okbits >> j) & 1 ? (unsigned)(origin + rel[j]) : C32_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (c32_lds_void*)(Ps + j * 256), 16, off, 0, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void*)(Ps + j * 256), 16, off, 0, 0, 0);
         }
     };
 

@@ -27,6 +27,7 @@
 //     row tiles per block, every thread then combines them for whole 16-byte channel groups and stores NHWC channel runs with scale / bias / residual / ReLU.
 // The per-output arithmetic depends only on the tile's own pixels: results do not depend on the batch position.
 #include "common.h"
+#include "buffer.h"
 #include "winograd_pack.h"
 
 #include <atomic>
@@ -42,7 +43,7 @@ struct F4Params {
     const float* res;
     float* y;
     // training epilogues (MODE 1: BatchNorm batch statistics of the raw output; MODE 2: BatchNorm-backward fusion of a data-gradient launch, semantics of
-    // ConvParams::bz .. in conv_igemm.hip): (sum, sum^2) / (sum g, sum g * xhat) per (16-tile row block, channel) as doubles, the layout vatl_bn_train_finalize /
+    // ConvParams::bz .. in conv_igemm.h): (sum, sum^2) / (sum g, sum g * xhat) per (16-tile row block, channel) as doubles, the layout vatl_bn_train_finalize /
     // vatl_bn_bwd_from_stats reduce in a fixed order
     double* stats;
     const float* bz;
@@ -59,7 +60,6 @@ struct F4Params {
     FastDivU d_tpi, d_TW;
 };
 
-typedef __attribute__((address_space(3))) void f4_lds_void;
 constexpr int F4_TB = 16;                                  // tiles per block
 constexpr int F4_NDMA = 36;                                // wave-wide DMA instructions per stage (1 KB each): one per patch pixel, lane = (tile, channel quad)
 constexpr int F4_STAGE = F4_NDMA * 256;                    // floats per stage buffer: 9216 (36 864 bytes)
@@ -84,9 +84,6 @@ template <int XI> __device__ __forceinline__ constexpr bool f4_uses(int i) {
     return XI == 0 ? (i == 0 || i == 2 || i == 4) : (XI == 5 ? (i == 1 || i == 3 || i == 5) : (i >= 1 && i <= 4));
 }
 
-__device__ __forceinline__ f32x4 f4_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
 // F4_ABL (tools/f4_ablate.sh only; wrong results): 1 no filter loads, 2 no LDS reads / row combinations, 4 no staging DMA, 8 no stage barrier,
 // 16 no output transform / write-out (the accumulators stay alive), 32 no wait for the block's first stage and first filter fragments
 #ifndef F4_ABL
@@ -102,7 +99,7 @@ __device__ __forceinline__ f32x4 f4_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned
 // at the point of the stage from which the next wait on a younger fragment batch is farthest away (f4_part, BURST).
 __device__ __forceinline__ f32x4 f4_filter_load(__amdgpu_buffer_rsrc_t r, unsigned off) {
     if constexpr ((F4_ABL & 1) != 0) { f32x4 v; asm volatile("" : "=v"(v)); return v; }
-    else return f4_buf_load4(r, off);
+    else return buf_load4(r, off);
 }
 // compile-time loop index
 template <int I, int N, typename F>
@@ -218,8 +215,8 @@ __device__ __forceinline__ void f4_nu_sums(const f32x4 (&acc)[9][NB], float* Zs,
 template <int WV, int MODE, int NB>
 __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_tile, int n_tile) {
     const int tid = threadIdx.x, lane = tid & 63;
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ur = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.u), 0, p.u_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t ur = buf_rsrc(p.u, p.u_bytes);
 
     // ---- staging geometry: DMA instruction px (= patch pixel (px / 6, px % 6)) of a stage writes the 1 KB row px of the stage buffer; its lane L delivers slot L of
     // that row = (tile L / 4, channel quad (L % 4 - 2 (tile / 8)) & 3): with that rotation the 16 lanes of every ds_read_b128 service group ({0-3, 12-15, 20-27}, ...:
@@ -248,7 +245,7 @@ __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_ti
         const int px = WV + 4 * k, i = px / 6, jx = px - 6 * i;
         const bool ok = ((in >> i) & (in >> (6 + jx)) & 1u) != 0;
         const unsigned off = ok ? tb + (unsigned)i * row_bytes + (unsigned)jx * px_bytes : F4_OOB;
-        if constexpr ((F4_ABL & 4) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (f4_lds_void*)(buf + px * 256), 16, off, (unsigned)stage * 64u, 0, 0);
+        if constexpr ((F4_ABL & 4) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void*)(buf + px * 256), 16, off, (unsigned)stage * 64u, 0, 0);
     };
 
     // ---- operands ----
@@ -312,8 +309,8 @@ __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_ti
     }
     lds_barrier();                                         // every wave is done with the stage buffers
     float* Zs = smem;
-    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res ? p.res : p.y), 0, p.res ? p.y_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res ? p.res : p.y, p.res ? p.y_bytes : 0u);
     const float lo = p.relu ? 0.f : -INFINITY;
     const int c4 = tid & 7;                                // this thread's 16-byte channel group of the 32-channel half (the same for both of its items)
 #pragma unroll
@@ -330,8 +327,8 @@ __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_ti
         if constexpr (MODE == 2) {
             mu = *reinterpret_cast<const f32x4*>(p.bmu + n); is = *reinterpret_cast<const f32x4*>(p.bis + n);
             if (p.bsc) { msc = *reinterpret_cast<const f32x4*>(p.bsc + n); mbi = *reinterpret_cast<const f32x4*>(p.bbi + n); }
-            zr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bz), 0, p.y_bytes, 0x00020000);
-            mr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bmy ? p.bmy : p.bz), 0, p.bmy ? p.y_bytes : 0u, 0x00020000);
+            zr = buf_rsrc(p.bz, p.y_bytes);
+            mr = buf_rsrc(p.bmy ? p.bmy : p.bz, p.bmy ? p.y_bytes : 0u);
         }
         f32x4 s1 = nul, s2 = nul;                          // this thread's share of the two per-channel sums (MODE 1 / 2)
 #pragma unroll
@@ -348,8 +345,8 @@ __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_ti
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const unsigned off = ok ? base + a * rowb : 0xFFFFFFF0u;
-                rs[a] = MODE == 1 ? nul : f4_buf_load4(rr, off);
-                if constexpr (MODE == 2) { zt[a] = f4_buf_load4(zr, off); yt[a] = f4_buf_load4(mr, off); }
+                rs[a] = MODE == 1 ? nul : buf_load4(rr, off);
+                if constexpr (MODE == 2) { zt[a] = buf_load4(zr, off); yt[a] = buf_load4(mr, off); }
             }
             f32x4 S[8];
 #pragma unroll
@@ -377,7 +374,7 @@ __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_ti
                         s2[c] += v[c] * ((zt[a][c] - mu[c]) * is[c]);
                     }
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), yr, ok ? base + a * rowb : 0xFFFFFFF0u, 0, 0);
+                buf_store4(yr, ok ? base + a * rowb : 0xFFFFFFF0u, v);
             }
         }
         if constexpr (MODE != 0) {

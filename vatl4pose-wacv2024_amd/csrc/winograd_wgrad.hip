@@ -19,6 +19,8 @@
 // partial sums into its slice of a workspace and winograd_wgrad_finish_kernel adds the slices in split order, applies the xi side and
 // writes the filter in the tensor's own layout — no atomics, bitwise reproducible.
 #include "common.h"
+#include "buffer.h"
+#include "tune.h"
 
 #include <algorithm>
 #include <atomic>
@@ -47,7 +49,6 @@ struct WinoWgradParams {
 };
 
 constexpr unsigned WWOOB = 0xFFFFFFFFu;
-typedef __attribute__((address_space(3))) void wwlds_void;
 
 // The staging addresses of a launch depend on its geometry only — and forming them in the main kernel (two divisions and ~25 vector instructions per 16-byte
 // request, ~240 per stage and lane) costs 19 - 26 % of its time: vector instructions are not hidden behind the MFMAs on this hardware (profiles/r04_notes.md;
@@ -113,13 +114,13 @@ __device__ __forceinline__ void winograd_wgrad_body(const WinoWgradParams& p, fl
     const int ooy = p.deconv ? py : 0, oox = p.deconv ? px : 0;
     const int t_begin = split * p.tps, t_end = min(t_begin + p.tps, p.Mtiles);
 
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t gr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.g), 0, p.g_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t gr = buf_rsrc(p.g, p.g_bytes);
     // table mode: the tables hold the offsets of channel tile 0 (and gradient phase (0, 0)); this block's tile / phase is in the descriptors' base addresses
     const bool tabled = p.tab_x != nullptr;
     const unsigned xsh = (unsigned)c0 * 4u, gsh = (unsigned)((ooy * p.OW + oox) * p.Cn + n0) * 4u;
-    const __amdgpu_buffer_rsrc_t xrt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x) + c0, 0, p.x_bytes - xsh, 0x00020000);
-    const __amdgpu_buffer_rsrc_t grt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.g) + (gsh >> 2), 0, p.g_bytes - gsh, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrt = buf_rsrc(p.x + c0, p.x_bytes - xsh);
+    const __amdgpu_buffer_rsrc_t grt = buf_rsrc(p.g + (gsh >> 2), p.g_bytes - gsh);
     const unsigned* tx_base = tabled ? p.tab_x + ((long long)(p.deconv ? phase : 0) * p.stages_total) * (p.ndma_x * 64) + xi * 64 + lane : nullptr;
     const unsigned* tg_base = tabled ? p.tab_g + xi * 64 + lane : nullptr;
     unsigned offx[NLX], offg[NLG];                          // the NEXT stage_dma's addresses, loaded a stage ahead
@@ -154,10 +155,10 @@ __device__ __forceinline__ void winograd_wgrad_body(const WinoWgradParams& p, fl
         if (tabled) {
 #pragma unroll
             for (int u = 0; u < NLX; ++u)
-                if (xi + 4 * u < p.ndma_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(xrt, (wwlds_void*)(Xs + (xi + 4 * u) * 256), 16, offx[u], 0, 0, 0);
+                if (xi + 4 * u < p.ndma_x) __builtin_amdgcn_raw_ptr_buffer_load_lds(xrt, (lds_void*)(Xs + (xi + 4 * u) * 256), 16, offx[u], 0, 0, 0);
 #pragma unroll
             for (int u = 0; u < NLG; ++u)
-                if (xi + 4 * u < p.ndma_g) __builtin_amdgcn_raw_ptr_buffer_load_lds(grt, (wwlds_void*)(Gs + (xi + 4 * u) * 256), 16, offg[u], 0, 0, 0);
+                if (xi + 4 * u < p.ndma_g) __builtin_amdgcn_raw_ptr_buffer_load_lds(grt, (lds_void*)(Gs + (xi + 4 * u) * 256), 16, offg[u], 0, 0, 0);
             return;
         }
         const int gr0 = fast_div(t0, p.inv_TW);            // global tile row (image, ty) of the stage's first tile
@@ -175,7 +176,7 @@ __device__ __forceinline__ void winograd_wgrad_body(const WinoWgradParams& p, fl
                     if (b < p.N && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W)
                         off = (unsigned)(((b * p.H + yy) * p.W + xx) * p.Cx + xi_c[u]) << 2;
                 }
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (wwlds_void*)(Xs + (xi + 4 * u) * 256), 16, off, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void*)(Xs + (xi + 4 * u) * 256), 16, off, 0, 0, 0);
             }
         }
 #pragma unroll
@@ -190,7 +191,7 @@ __device__ __forceinline__ void winograd_wgrad_body(const WinoWgradParams& p, fl
                     if (yy < p.H && xx < p.W)
                         off = (unsigned)(((b * p.OH + yy * p.os + ooy) * p.OW + xx * p.os + oox) * p.Cn + gi_c[u]) << 2;
                 }
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(gr, (wwlds_void*)(Gs + (xi + 4 * u) * 256), 16, off, 0, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(gr, (lds_void*)(Gs + (xi + 4 * u) * 256), 16, off, 0, 0, 0);
             }
         }
     };
