@@ -235,6 +235,13 @@ class _ConvBN:
         return _WINOGRAD_F4 and cin >= 64 and cin % 16 == 0 and cout % 64 == 0 and vh.conv3x3_winograd_f4_supported(int(shape[0]), int(shape[1]), int(shape[2]), cin, cout)
 
     # ---- forward -------------------------------------------------------------
+    def _igemm_bnstats(self, x):
+        """z = conv(x) on the implicit GEMM with the batch statistics from its epilogue -> z, save_mean, save_invstd, scale, bias."""
+        bn = self.bn
+        w = vh.pack_conv_weight(self.conv.weight.detach())
+        return vh.conv2d_fwd_bnstats(x, w, self.cout, self.r, self.s, self.stride, self.pad, bn.weight.detach(), bn.bias.detach(),
+                                     bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+
     def forward(self, x, skip=None, relu=None):
         relu = self.relu if relu is None else relu
         bn = self.bn
@@ -248,9 +255,7 @@ class _ConvBN:
                                                                            bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
                                                                            bn.momentum, bn.eps)
         else:
-            w = vh.pack_conv_weight(self.conv.weight.detach())
-            z, mean, invstd, scale, bias = vh.conv2d_fwd_bnstats(x, w, self.cout, self.r, self.s, self.stride, self.pad, bn.weight.detach(),
-                                                                 bn.bias.detach(), bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+            z, mean, invstd, scale, bias = self._igemm_bnstats(x)
         _count_batch(bn)
         y = vh.scale_bias_act(z, scale, bias, skip, relu)
         if relu:
@@ -263,11 +268,8 @@ class _ConvBN:
     def forward_pool(self, x):
         """Conv + BN(train) + ReLU + MaxPool2d(3,2,1) (the trunk's stem tail, Resnet.py:171-172): the affine + ReLU are applied to z
         inside the pooling pass, relu(bn(z)) itself is never written.  -> pooled output; the winners stay on the tape."""
-        w = vh.pack_conv_weight(self.conv.weight.detach())
-        bn = self.bn
-        z, mean, invstd, scale, bias = vh.conv2d_fwd_bnstats(x, w, self.cout, self.r, self.s, self.stride, self.pad, bn.weight.detach(),
-                                                             bn.bias.detach(), bn.running_mean, bn.running_var, bn.momentum, bn.eps)
-        _count_batch(bn)
+        z, mean, invstd, scale, bias = self._igemm_bnstats(x)
+        _count_batch(self.bn)
         y, idx = vh.maxpool3x3s2_fwd_idx_affine(z, scale, bias)
         self.saved = (x, z, None, mean, invstd, False, (scale, bias))
         self.pool_idx = idx
@@ -464,6 +466,36 @@ def _chain_blocks_backward(blocks, dx, grads, pre, flush=None):
     return dx
 
 
+class _HeadT:
+    """The output layer of the three networks: Conv2d(k, 1, k // 2) with bias and no BatchNorm, heat-maps out in NCHW."""
+
+    def __init__(self, conv: nn.Conv2d):
+        self.conv = conv
+        self.cout, self.cin, self.k, _ = conv.weight.shape
+
+    def forward(self, x):
+        """The last launches of a forward pass: the BatchNorm counters the layers before it deferred are flushed on the way."""
+        self.x = x
+        w = vh.pack_conv_weight(self.conv.weight.detach())
+        _, bias = vh.bn_fold(None, None, None, None, 0.0, self.conv.bias.detach(), channels=self.cout)
+        _flush_batch_counters()
+        return vh.conv2d_fwd(x, w, None, bias, self.cout, self.k, self.k, 1, self.k // 2, False, out_nchw=True)
+
+    def backward(self, dout_nchw, grads, consumer=None):
+        """dout (B,J,H,W) NCHW -> dx NHWC; ``consumer``: the BnBwdSpec of the layer that produced the head's input (its BatchNorm
+        reduction then runs in the data gradient's epilogue)."""
+        x, self.x = self.x, None
+        k, p = self.k, self.k // 2
+        dy = vh.nchw_to_nhwc(dout_nchw.contiguous(), 32)                         # 17 -> 32 channels (zeros)
+        grads[self.conv.bias] = vh.col_sum(dy)[:self.cout].contiguous()
+        grads[self.conv.weight] = vh.conv2d_wgrad(x, dy, self.cout, self.cin, k, k, 1, p, out=_gout(grads, self.conv.weight))
+        wd = vh.pack_dgrad_weight(self.conv.weight.detach(), _flipped_taps(k, k), cout_k=32)
+        n, h, w, _ = x.shape
+        if consumer is not None:
+            return vh.conv2d_fwd_ex_bnbwd(dy, wd, self.cin, k, k, 1, p, p, h, w, h, w, 1, 1, 0, 0, consumer)
+        return vh.conv2d_fwd_ex(dy, wd, self.cin, k, k, 1, p, p, h, w, h, w, 1, 1, 0, 0)
+
+
 class SimplePoseTrainer:
     """Tape-based forward/backward of SimplePose in training mode."""
 
@@ -473,7 +505,7 @@ class SimplePoseTrainer:
         self.blocks = [_BottleneckT(b) for stage in t.stages() for b in stage]
         d = m.deconv_layers
         self.deconvs = [_DeconvBN(d[0], d[1]), _DeconvBN(d[3], d[4]), _DeconvBN(d[6], d[7])]
-        self.head = m.final_layer
+        self.head = _HeadT(m.final_layer)
 
     @_planned("forward")
     def forward(self, x_nchw):
@@ -483,28 +515,15 @@ class SimplePoseTrainer:
             x = b.forward(x)
         for d in self.deconvs:
             x = d.forward(x)
-        self.head_in = x
-        hw = vh.pack_conv_weight(self.head.weight.detach())
-        _, hb = vh.bn_fold(None, None, None, None, 0.0, self.head.bias.detach(), channels=self.head.weight.shape[0])
-        _flush_batch_counters()
-        return vh.conv2d_fwd(x, hw, None, hb, self.head.weight.shape[0], 1, 1, 1, 0, False, out_nchw=True)
+        return self.head.forward(x)
 
     @_planned("backward")
     def backward(self, dout_nchw, arena=None, overlap=False):
         """dout (B,J,H,W) NCHW -> {parameter: gradient} for every parameter of the model.  With ``arena`` the gradients are
         its slices; ``overlap`` lets the arena all-reduce finished buckets while the earlier layers are still in flight."""
         grads = _Grads(arena, overlap)
-        j = self.head.weight.shape[0]
-        cin = self.head.weight.shape[1]
-        dy = vh.nchw_to_nhwc(dout_nchw.contiguous(), 32)                         # 17 -> 32 channels (zeros)
-        grads[self.head.bias] = vh.col_sum(dy)[:j].contiguous()
-        grads[self.head.weight] = vh.conv2d_wgrad(self.head_in, dy, j, cin, 1, 1, 1, 0, out=_gout(grads, self.head.weight))
-        wd = vh.pack_dgrad_weight(self.head.weight.detach(), [(0, 0)], cout_k=32)
-        n, h, w, _ = self.head_in.shape
         pre = self.deconvs[-1].bn_spec()
-        dx = vh.conv2d_fwd_ex_bnbwd(dy, wd, cin, 1, 1, 1, 0, 0, h, w, h, w, 1, 1, 0, 0, pre) if pre is not None else \
-            vh.conv2d_fwd_ex(dy, wd, cin, 1, 1, 1, 0, 0, h, w, h, w, 1, 1, 0, 0)
-        self.head_in = None
+        dx = self.head.backward(dout_nchw, grads, consumer=pre)
         for k in range(len(self.deconvs) - 1, -1, -1):
             consumer = self.deconvs[k - 1].bn_spec() if k > 0 else self.blocks[-1].out_spec()
             dx = self.deconvs[k].backward(dx, grads, pre=pre, consumer=consumer)
@@ -588,7 +607,7 @@ class FastPoseTrainer:
         self.blocks = [(_SEBottleneckT(b) if getattr(b, "reduc", False) else _BottleneckT(b)) for stage in t.stages() for b in stage]
         self.duc1 = _ConvBN(m.duc1.conv, m.duc1.bn, True)
         self.duc2 = _ConvBN(m.duc2.conv, m.duc2.bn, True)
-        self.head = m.conv_out
+        self.head = _HeadT(m.conv_out)
 
     @_planned("forward")
     def forward(self, x_nchw):
@@ -597,24 +616,12 @@ class FastPoseTrainer:
             x = b.forward(x)
         x = vh.pixelshuffle2_fwd(x)
         x = vh.pixelshuffle2_fwd(self.duc1.forward(x))
-        x = vh.pixelshuffle2_fwd(self.duc2.forward(x))
-        self.head_in = x
-        j = self.head.weight.shape[0]
-        _, hb = vh.bn_fold(None, None, None, None, 0.0, self.head.bias.detach(), channels=j)
-        _flush_batch_counters()
-        return vh.conv2d_fwd(x, vh.pack_conv_weight(self.head.weight.detach()), None, hb, j, 3, 3, 1, 1, False, out_nchw=True)
+        return self.head.forward(vh.pixelshuffle2_fwd(self.duc2.forward(x)))
 
     @_planned("backward")
     def backward(self, dout_nchw, arena=None, overlap=False):
         grads = _Grads(arena, overlap)
-        j, cin = self.head.weight.shape[:2]
-        dy = vh.nchw_to_nhwc(dout_nchw.contiguous(), 32)
-        grads[self.head.bias] = vh.col_sum(dy)[:j].contiguous()
-        grads[self.head.weight] = vh.conv2d_wgrad(self.head_in, dy, j, cin, 3, 3, 1, 1, out=_gout(grads, self.head.weight))
-        wd = vh.pack_dgrad_weight(self.head.weight.detach(), _flipped_taps(3, 3), cout_k=32)
-        n, h, w, _ = self.head_in.shape
-        dx = vh.conv2d_fwd_ex(dy, wd, cin, 3, 3, 1, 1, 1, h, w, h, w, 1, 1, 0, 0)
-        self.head_in = None
+        dx = self.head.backward(dout_nchw, grads)
         dx, _ = self.duc2.backward(vh.pixelunshuffle2(dx), grads)
         dx, _ = self.duc1.backward(vh.pixelunshuffle2(dx), grads)
         grads.flush()
@@ -730,7 +737,7 @@ class HRNetTrainer:
         for s in (2, 3, 4):
             trans = [None if t is None else _ChainT(t) for t in getattr(m, f"transition{s - 1}")]
             self.stages.append((trans, [_HRModuleT(mod) for mod in getattr(m, f"stage{s}")]))
-        self.head = m.final_layer
+        self.head = _HeadT(m.final_layer)
 
     @_planned("forward")
     def forward(self, x_nchw):
@@ -745,23 +752,12 @@ class HRNetTrainer:
             for mod in mods:
                 xs = mod.forward(xs)
             ys = xs
-        self.head_in = ys[0]
-        j, _, k, _ = self.head.weight.shape
-        _, hb = vh.bn_fold(None, None, None, None, 0.0, self.head.bias.detach(), channels=j)
-        _flush_batch_counters()
-        return vh.conv2d_fwd(ys[0], vh.pack_conv_weight(self.head.weight.detach()), None, hb, j, k, k, 1, k // 2, False, out_nchw=True)
+        return self.head.forward(ys[0])
 
     @_planned("backward")
     def backward(self, dout_nchw, arena=None, overlap=False):
         grads = _Grads(arena, False)                  # the branches' gradients do not complete in arena order: one reduce at the end
-        j, cin, k, _ = self.head.weight.shape
-        dy = vh.nchw_to_nhwc(dout_nchw.contiguous(), 32)
-        grads[self.head.bias] = vh.col_sum(dy)[:j].contiguous()
-        grads[self.head.weight] = vh.conv2d_wgrad(self.head_in, dy, j, cin, k, k, 1, k // 2, out=_gout(grads, self.head.weight))
-        wd = vh.pack_dgrad_weight(self.head.weight.detach(), _flipped_taps(k, k), cout_k=32)
-        n, h, w, _ = self.head_in.shape
-        dys = [vh.conv2d_fwd_ex(dy, wd, cin, k, k, 1, k // 2, k // 2, h, w, h, w, 1, 1, 0, 0)]
-        self.head_in = None
+        dys = [self.head.backward(dout_nchw, grads)]
         for (trans, mods), width in zip(reversed(self.stages), reversed(self.widths)):
             for mod in reversed(mods):
                 dys = mod.backward(dys, grads)

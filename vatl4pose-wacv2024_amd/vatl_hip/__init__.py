@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading as _threading
 
 import torch
 
@@ -220,8 +221,11 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+_tls = _threading.local()                            # per host thread: the plan its pack_* calls consult, the depth of its open splitk_scopes
+
+
 # ----------------------------------------------------------------------------
-# layout / parameter packing
+# layout
 # ----------------------------------------------------------------------------
 
 def nchw_to_nhwc(x: torch.Tensor, cpad: int | None = None) -> torch.Tensor:
@@ -238,6 +242,10 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
     _check(lib().vatl_nhwc_to_nchw(_ptr(x), _ptr(y), n, c, h, w, _stream()), "vatl_nhwc_to_nchw")
     return y
 
+
+# ----------------------------------------------------------------------------
+# metering, tuning knobs, split-K / stream-K scopes
+# ----------------------------------------------------------------------------
 
 ROUTE_NAMES = ("igemm", "igemm_bnbwd", "igemm_dma", "persistent_1x1", "streamk", "rows_1x1", "bottleneck_chain", "stem_pool", "halo_3x3", "winograd",
                "winograd_2h", "winograd_bnbwd", "winograd_persist", "winograd_c32", "wgrad", "winograd_wgrad", "winograd_wgrad_2h", "winograd_wgrad_table", "winograd_f4", "winograd_f4_bnbwd",
@@ -296,7 +304,7 @@ def enable_splitk(megabytes: int = 64, device=None):
 
 
 _splitk_scratch = {}                                 # device index -> free list of workspaces of the automatic small-batch mode
-_splitk_scratch_lock = __import__("threading").Lock()
+_splitk_scratch_lock = _threading.Lock()
 # the batch-invariant cut sizes a layer's split from what a 16-crop batch needs (conv_igemm.hip: launch): the largest is SimplePose's last
 # transposed conv, 3 slices x 16 crops x 64 x 48 x 256 floats = 151 MB; a smaller workspace only makes that layer run unsplit
 SPLITK_SCRATCH_MB = 256
@@ -354,8 +362,63 @@ def latency_mode() -> bool:
     reduction split (one crop: deconv1 = 32 blocks x 128 serial stages) and are 27 - 40 % slower end to end below ~8 crops."""
     return getattr(_tls, "latency_mode", 0) > 0
 
+
+STREAMK_IN_TRAINING = False                          # module constant, not an environment switch (see streamk_scope)
+_streamk_ws = {}                                     # (host thread, device index) -> zero-initialised stream-K workspace
+
+
+class streamk_scope:
+    """Stream-K for this host thread's conv launches while the scope is open (the trainers' forward / backward passes): launches
+    that would leave much of the chip idle share their (tile, k-tile) units evenly over 768 persistent blocks
+    (vatl_set_streamk_workspace_thread).  Results are deterministic but not the unsplit kernels' bits, so nothing outside
+    training opens it — and the trainers open it only when STREAMK_IN_TRAINING is set (off): measured on MI355X (profiles/r03_notes.md) the route
+    gains 8-23 % on the launches it takes when they run ALONE (R50 stage 4 at B = 120, FastPose-R152 stages 3-4 at B = 32), but
+    in the real step the block slots those launches leave idle are where the side stream's weight-gradient kernels run, and 768
+    persistent blocks take that overlap away: fine-tune step 44.8 -> 44.7 ms (R50), 67.5 -> 70.4 ms (R152).  ``force`` opens it
+    regardless (benchmarks, tests)."""
+
+    def __init__(self, device, force: bool = False):
+        self.idx = device.index if device.index is not None else torch.cuda.current_device()
+        self.active = False
+        self.force = force
+
+    def __enter__(self):
+        if not self.force and not STREAMK_IN_TRAINING:
+            return self
+        key = (_threading.get_ident(), self.idx)
+        buf = _streamk_ws.get(key)
+        if buf is None:
+            buf = _streamk_ws[key] = torch.zeros(int(lib().vatl_streamk_workspace_bytes()), device=torch.device("cuda", self.idx), dtype=torch.uint8)
+        _check(lib().vatl_set_streamk_workspace_thread(_ptr(buf, torch.uint8), buf.numel()), "vatl_set_streamk_workspace_thread")
+        self.active = True
+        return self
+
+    def __exit__(self, *exc):
+        if self.active:
+            _check(lib().vatl_set_streamk_workspace_thread(None, 0), "vatl_set_streamk_workspace_thread")
+        return False
+
+
+# ----------------------------------------------------------------------------
+# weight packs and parameter folding
+# ----------------------------------------------------------------------------
+
 def conv_cout_pad(cout: int) -> int:
     return lib().vatl_conv_cout_pad(cout)
+
+
+# VatlPackJob.kind and what the (a, b, c) fields hold for it (include/vatl_hip.h: vatl_pack_weights_multi)
+_PACK_CONV = 0                      # conv forward layout, (a, b, c) = (CoutPad, Spad, CinPad)
+_PACK_DGRAD = 1                     # data-gradient layout, (a, b, c) = (CinPad, CoutK, ntaps) with the taps in tap_r / tap_s
+_PACK_DECONV = 2                    # ConvTranspose2d(4,2,1) layout, src (Cin,Cout,4,4), a = CoutPad
+# Winograd F(2x2,3x3) filter transform, forward / data gradient: (Cout, Cin) of the PACKED filter, a = its padded Cout, b = 32-channel groups per
+# tile (a / 32 <= 1 ? 1 : 2), c = Cin (kind 3) or Cout (kind 4) = the inner dimension of src
+_PACK_WINOGRAD = 3
+_PACK_WINOGRAD_DGRAD = 4
+_PACK_WINOGRAD_DECONV = 5           # Winograd F(3x3,2x2) phase filters of ConvTranspose2d(4,2,1): src (Cin,Cout,4,4), a / b as for kinds 3 / 4, c = Cout
+_PACK_WINOGRAD_DECONV_DGRAD = 6     # the filters of its data gradient: (Cout, Cin) fields = (layer Cin, layer Cout), c = layer Cout
+_PACK_WINOGRAD_F4 = 7               # Winograd F(4x4,3x3) filter transform, forward: (Cout, Cin) of the PACKED filter, c = inner dimension of src
+_PACK_WINOGRAD_F4_DGRAD = 8         # ... data gradient
 
 
 class _PackJob(C.Structure):
@@ -412,57 +475,17 @@ class PackPlan:
             jb.kind, jb.Cout, jb.Cin, jb.R, jb.S, jb.a, jb.b, jb.c = f[:8]
             for t, (tr, ts) in enumerate(f[8]):
                 jb.tap_r[t], jb.tap_s[t] = tr, ts
-            if f[0] == 1:                                    # data-gradient layout [a = CinPad][c = taps][b = CoutK]: 32 x 32 tiles of one tap
+            if f[0] == _PACK_DGRAD:                          # [a = CinPad][c = taps][b = CoutK]: 32 x 32 tiles of one tap
                 blocks += ((f[5] + 31) // 32) * f[7] * ((f[6] + 31) // 32)
-            else:                                            # F(2x2) / F(3x3,2x2) Winograd filters (kinds 3 .. 6): 4096 elements per block; everything else 1024
-                blocks += (dst.numel() + 1023) // 1024 if (f[0] < 3 or f[0] >= 7) else dst.numel() // 4096
+            elif f[0] in (_PACK_WINOGRAD, _PACK_WINOGRAD_DGRAD, _PACK_WINOGRAD_DECONV, _PACK_WINOGRAD_DECONV_DGRAD):
+                blocks += dst.numel() // 4096                # F(2x2) / F(3x3,2x2) Winograd filters: 4096 elements per block
+            else:
+                blocks += (dst.numel() + 1023) // 1024       # everything else 1024
         dev = next(iter(self.jobs.values()))[1].device
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         self.table = host.to(dev)
         self.total_blocks = blocks
         self.ready = True
-
-
-STREAMK_IN_TRAINING = False                          # module constant, not an environment switch (see streamk_scope)
-_streamk_ws = {}                                     # (host thread, device index) -> zero-initialised stream-K workspace
-
-
-class streamk_scope:
-    """Stream-K for this host thread's conv launches while the scope is open (the trainers' forward / backward passes): launches
-    that would leave much of the chip idle share their (tile, k-tile) units evenly over 768 persistent blocks
-    (vatl_set_streamk_workspace_thread).  Results are deterministic but not the unsplit kernels' bits, so nothing outside
-    training opens it — and the trainers open it only when STREAMK_IN_TRAINING is set (off): measured on MI355X (profiles/r03_notes.md) the route
-    gains 8-23 % on the launches it takes when they run ALONE (R50 stage 4 at B = 120, FastPose-R152 stages 3-4 at B = 32), but
-    in the real step the block slots those launches leave idle are where the side stream's weight-gradient kernels run, and 768
-    persistent blocks take that overlap away: fine-tune step 44.8 -> 44.7 ms (R50), 67.5 -> 70.4 ms (R152).  ``force`` opens it
-    regardless (benchmarks, tests)."""
-
-    def __init__(self, device, force: bool = False):
-        self.idx = device.index if device.index is not None else torch.cuda.current_device()
-        self.active = False
-        self.force = force
-
-    def __enter__(self):
-        if not self.force and not STREAMK_IN_TRAINING:
-            return self
-        import threading
-        key = (threading.get_ident(), self.idx)
-        buf = _streamk_ws.get(key)
-        if buf is None:
-            buf = _streamk_ws[key] = torch.zeros(int(lib().vatl_streamk_workspace_bytes()), device=torch.device("cuda", self.idx), dtype=torch.uint8)
-        _check(lib().vatl_set_streamk_workspace_thread(_ptr(buf, torch.uint8), buf.numel()), "vatl_set_streamk_workspace_thread")
-        self.active = True
-        return self
-
-    def __exit__(self, *exc):
-        if self.active:
-            _check(lib().vatl_set_streamk_workspace_thread(None, 0), "vatl_set_streamk_workspace_thread")
-        return False
-
-
-import threading as _threading
-
-_tls = _threading.local()                            # per host thread: the plan its pack_* calls consult
 
 
 def set_pack_plan(plan):
@@ -472,6 +495,31 @@ def set_pack_plan(plan):
     return prev
 
 
+def _pack(key, w, job, planned: bool = True):
+    """What every plan-aware pack_* wrapper does around its one launch.  When the PackPlan of this host thread (set_pack_plan) keeps
+    a buffer for ``key`` that is current for ``w``, that buffer is the result.  Otherwise ``job()`` says what to run: (shape of the
+    packed tensor, C entry point, its arguments between (src, dst) and the stream, the VatlPackJob fields (kind, Cout, Cin, R, S,
+    a, b, c, taps)) — allocate, launch, and let the plan record the job.  A non-contiguous ``w`` is packed from a contiguous copy and
+    stays outside the plan (the plan's one launch reads the parameter's own storage)."""
+    plan = getattr(_tls, "pack_plan", None) if planned and w.is_contiguous() else None
+    if plan is not None:
+        kept = plan.lookup(key, w)
+        if kept is not None:
+            return kept
+    shape, fn, args, fields = job()
+    out = torch.empty(shape, device=w.device, dtype=torch.float32)
+    _check(getattr(lib(), fn)(_ptr(w.contiguous()), _ptr(out), *args, _stream()), fn)
+    if plan is not None:
+        plan.record(key, w, out, fields)
+    return out
+
+
+def _winograd_fields(kind: int, cout: int, cin: int, k: int, inner: int):
+    """VatlPackJob fields of the F(2x2,3x3) / F(3x3,2x2) filter transforms (kinds 3 .. 6)."""
+    pad = int(lib().vatl_winograd_cout_pad(cout))
+    return (kind, cout, cin, k, k, pad, 1 if pad <= 32 else 2, inner, ())
+
+
 def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
     """(Cout,Cin,R,S) -> [CoutPad][R][Spad][CinPad]; the 3-channel stem is padded to 4 channels x 8 taps."""
     cout, cin, r, s = w.shape
@@ -479,16 +527,79 @@ def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
     if r == 1 and s == 1 and cpad == cout and cin != 3 and w.is_contiguous() and w.dtype == torch.float32:
         return w.detach().view(cout, 1, 1, cin)              # (Cout,Cin,1,1) already is the packed [Cout][1][1][Cin]: no copy
     spad, cinpad = (8, 4) if cin == 3 else (s, cin)
-    plan, key = getattr(_tls, "pack_plan", None), ("conv", w.data_ptr(), tuple(w.shape))
-    if plan is not None and w.is_contiguous():
-        kept = plan.lookup(key, w)
-        if kept is not None:
-            return kept
-    out = torch.empty((cpad, r, spad, cinpad), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_conv_weight(_ptr(w.contiguous()), _ptr(out), cout, cin, r, s, cpad, spad, cinpad, _stream()), "vatl_pack_conv_weight")
-    if plan is not None and w.is_contiguous():
-        plan.record(key, w, out, (0, cout, cin, r, s, cpad, spad, cinpad, ()))
-    return out
+    return _pack(("conv", w.data_ptr(), tuple(w.shape)), w, lambda: (
+        (cpad, r, spad, cinpad), "vatl_pack_conv_weight", (cout, cin, r, s, cpad, spad, cinpad),
+        (_PACK_CONV, cout, cin, r, s, cpad, spad, cinpad, ())))
+
+
+def pack_dgrad_weight(w: torch.Tensor, taps, cout_k: int | None = None) -> torch.Tensor:
+    """(Cout,Cin,R,S) -> [CinPad][len(taps)][CoutK] with out[c][t][n] = w[n][c][taps[t]]."""
+    cout, cin, r, s = w.shape
+    cinpad = conv_cout_pad(cin)
+    cout_k = cout_k or cout
+    taps = [(int(a), int(b)) for a, b in taps]
+
+    def job():
+        tr = (C.c_int * len(taps))(*[t[0] for t in taps])
+        ts = (C.c_int * len(taps))(*[t[1] for t in taps])
+        return ((cinpad, len(taps), cout_k), "vatl_pack_dgrad_weight",
+                (cout, cin, r, s, cinpad, cout_k, len(taps), C.cast(tr, C.c_void_p), C.cast(ts, C.c_void_p)),
+                (_PACK_DGRAD, cout, cin, r, s, cinpad, cout_k, len(taps), tuple(taps)))
+    return _pack(("dgrad", w.data_ptr(), tuple(w.shape), tuple(taps), cout_k), w, job, planned=len(taps) <= 16)     # VatlPackJob holds 16 taps
+
+
+def pack_deconv_weight(w: torch.Tensor) -> torch.Tensor:
+    cin, cout, kh, kw = w.shape
+    if (kh, kw) != (4, 4):
+        raise VatlError("only ConvTranspose2d(4, 2, 1) is supported")
+    cpad = conv_cout_pad(cout)
+    return _pack(("deconv", w.data_ptr(), tuple(w.shape)), w, lambda: (
+        (4, cpad, 2, 2, cin), "vatl_pack_deconv4x4s2_weight", (cin, cout, cpad), (_PACK_DECONV, cout, cin, 4, 4, cpad, 0, 0, ())))
+
+
+def pack_winograd_weight(w: torch.Tensor, data_gradient: bool = False) -> torch.Tensor:
+    """(Cout,Cin,3,3) -> the F(2x2,3x3) filter transform G g G^T in MFMA fragment order (csrc/conv_winograd.hip).  With
+    ``data_gradient`` the result is the filter of dX = conv(dY, rot180(w)^T): its output channels are the forward Cin."""
+    co, ci = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3):
+        raise VatlError("pack_winograd_weight: 3x3 filters only")
+    cout, cin = (ci, co) if data_gradient else (co, ci)
+    return _pack(("winograd", w.data_ptr(), tuple(w.shape), bool(data_gradient)), w, lambda: (
+        int(lib().vatl_winograd_weight_floats(cout, cin)), "vatl_pack_winograd_weight", (cout, cin, int(data_gradient)),
+        _winograd_fields(_PACK_WINOGRAD_DGRAD if data_gradient else _PACK_WINOGRAD, cout, cin, 3, ci)))
+
+
+def pack_winograd_f4_weight(w: torch.Tensor, data_gradient: bool = False) -> torch.Tensor:
+    """(Cout,Cin,3,3) -> U = G g G^T of F(4x4,3x3) in the MFMA fragment order of csrc/winograd_f4.hip.  With ``data_gradient`` the result is the filter of
+    dX = conv(dY, rot180(w)^T): its output channels are the forward Cin.  Inside a PackPlan (the trainers' forward / backward) the buffer is kept and refreshed by
+    the step's one re-pack launch."""
+    co, ci = w.shape[:2]
+    cout, cin = (ci, co) if data_gradient else (co, ci)
+    return _pack(("winograd_f4", w.data_ptr(), tuple(w.shape), bool(data_gradient)), w, lambda: (
+        int(lib().vatl_winograd_f4_weight_floats(cout, cin)), "vatl_pack_winograd_f4_weight", (cout, cin, int(data_gradient)),
+        (_PACK_WINOGRAD_F4_DGRAD if data_gradient else _PACK_WINOGRAD_F4, cout, cin, 3, 3, 0, 0, ci, ())))
+
+
+def pack_winograd_deconv_weight(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the four sub-pixel phase filters in the F(3x3,2x2) transform domain,
+    MFMA fragment order (csrc/conv_winograd.hip)."""
+    cin, cout = w.shape[:2]
+    if tuple(w.shape[2:]) != (4, 4):
+        raise VatlError("pack_winograd_deconv_weight: 4x4 filters only")
+    return _pack(("winograd_deconv", w.data_ptr(), tuple(w.shape)), w, lambda: (
+        int(lib().vatl_winograd_deconv_weight_floats(cout, cin)), "vatl_pack_winograd_deconv_weight", (cout, cin),
+        _winograd_fields(_PACK_WINOGRAD_DECONV, cout, cin, 4, cout)))
+
+
+def pack_winograd_deconv_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the filters of its DATA gradient (a 4x4 / stride 2 conv over dz = four pixel
+    phases x 2x2 convolutions) in the F(3x3,2x2) transform domain."""
+    cin, cout = w.shape[:2]
+    if tuple(w.shape[2:]) != (4, 4):
+        raise VatlError("pack_winograd_deconv_dgrad_weight: 4x4 filters only")
+    return _pack(("winograd_deconv_dgrad", w.data_ptr(), tuple(w.shape)), w, lambda: (
+        int(lib().vatl_winograd_deconv_dgrad_weight_floats(cin, cout)), "vatl_pack_winograd_deconv_dgrad_weight", (cin, cout),
+        _winograd_fields(_PACK_WINOGRAD_DECONV_DGRAD, cin, cout, 4, cout)))
 
 
 def pack_conv1x1_dual_weight(w1, scale1, bias1, w2, scale2, bias2):
@@ -503,16 +614,6 @@ def pack_conv1x1_dual_weight(w1, scale1, bias1, w2, scale2, bias2):
     return out, bias
 
 
-def conv1x1_dual_fwd(a, x, w_packed, bias, cout: int, stride2: int, relu: bool, out=None):
-    """relu?(W1' a + W2' x[::s, ::s] + bias): a (N,Ho,Wo,C1) and x (N,H2,W2,C2) NHWC -> (N,Ho,Wo,Cout)."""
-    n, ho, wo, c1 = a.shape
-    _, h2, w2, c2 = x.shape
-    y = out if out is not None else torch.empty((n, ho, wo, cout), device=a.device, dtype=torch.float32)
-    _check(lib().vatl_conv1x1_dual_fwd(_ptr(a), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(y), n, ho, wo, c1, h2, w2, c2, stride2, cout,
-                                       w_packed.shape[0], int(relu), _stream()), "vatl_conv1x1_dual_fwd")
-    return y
-
-
 def pack_winograd_c32_weight(w: torch.Tensor) -> torch.Tensor:
     """(32,32,3,3) -> G g G^T in the LDS order of csrc/winograd_c32.hip."""
     if tuple(w.shape) != (32, 32, 3, 3):
@@ -522,79 +623,58 @@ def pack_winograd_c32_weight(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def conv3x3_winograd_c32_supported(n: int, h: int, w: int, cin: int, cout: int) -> bool:
-    return bool(lib().vatl_conv3x3_winograd_c32_supported(n, h, w, cin, cout))
+def pack_stem_pool_weight(w: torch.Tensor) -> torch.Tensor:
+    """(64,3,7,7) OIHW stem filter -> the fragment order of vatl_stem7x7s2_pool_fwd."""
+    if tuple(w.shape) != (64, 3, 7, 7):
+        raise VatlError(f"pack_stem_pool_weight: expected a (64,3,7,7) filter, got {tuple(w.shape)}")
+    w = w.detach().float().contiguous()
+    out = torch.empty(int(lib().vatl_stem_pool_weight_floats()), device=w.device, dtype=torch.float32)
+    _check(lib().vatl_pack_stem_pool_weight(_ptr(w), _ptr(out), _stream()), "vatl_pack_stem_pool_weight")
+    return out
 
 
-def conv3x3_winograd_c32_fwd(x, u, scale, bias, relu: bool, residual=None, out=None):
-    """3x3 / stride 1 / pad 1, 32 -> 32 channels, NHWC, Winograd F(2x2,3x3) with wave-private tiles (csrc/winograd_c32.hip)."""
-    n, h, w, c = x.shape
-    y = out if out is not None else torch.empty_like(x)
-    assert x.is_contiguous() and y.is_contiguous() and (residual is None or (residual.is_contiguous() and residual.shape == x.shape))
-    _check(lib().vatl_conv3x3_winograd_c32_fwd(_ptr(x), _ptr(u), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, int(relu), _stream()),
-           "vatl_conv3x3_winograd_c32_fwd")
+def pack_stem3_weight(w: torch.Tensor) -> torch.Tensor:
+    """(64,3,3,3) OIHW filter of HRNet's conv1 -> the fragment order of vatl_stem3x3s2_fwd."""
+    if tuple(w.shape) != (64, 3, 3, 3):
+        raise VatlError(f"pack_stem3_weight: expected a (64,3,3,3) filter, got {tuple(w.shape)}")
+    w = w.detach().float().contiguous()
+    out = torch.empty(int(lib().vatl_stem3_weight_floats()), device=w.device, dtype=torch.float32)
+    _check(lib().vatl_pack_stem3_weight(_ptr(w), _ptr(out), _stream()), "vatl_pack_stem3_weight")
+    return out
+
+
+def bn_fold(gamma, beta, mean, var, eps: float, conv_bias=None, channels: int | None = None):
+    c = channels if channels is not None else (var.numel() if var is not None else conv_bias.numel())
+    dev = (var if var is not None else conv_bias).device
+    scale = torch.empty(c, device=dev, dtype=torch.float32)
+    bias = torch.empty(c, device=dev, dtype=torch.float32)
+    _check(lib().vatl_bn_fold(_ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), _ptr(conv_bias), eps, _ptr(scale), _ptr(bias), c, _stream()), "vatl_bn_fold")
+    return scale, bias
+
+
+# ----------------------------------------------------------------------------
+# backbone ops (NHWC)
+# ----------------------------------------------------------------------------
+
+def conv2d_fwd(x, w_packed, scale, bias, cout: int, r: int, s: int, stride: int, pad: int, relu: bool,
+               residual=None, out_nchw: bool = False, out=None):
+    n, h, w, cin = x.shape
+    ho = (h + 2 * pad - r) // stride + 1
+    wo = (w + 2 * pad - s) // stride + 1
+    shape = (n, cout, ho, wo) if out_nchw else (n, ho, wo, cout)
+    y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
+    _check(lib().vatl_conv2d_fwd(_ptr(x), _ptr(w_packed), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout,
+                                 w_packed.shape[0], r, s, stride, pad, int(relu), int(out_nchw), _stream()), "vatl_conv2d_fwd")
     return y
 
 
-
-def pack_winograd_f4_weight(w: torch.Tensor, data_gradient: bool = False) -> torch.Tensor:
-    """(Cout,Cin,3,3) -> U = G g G^T of F(4x4,3x3) in the MFMA fragment order of csrc/winograd_f4.hip.  With ``data_gradient`` the result is the filter of
-    dX = conv(dY, rot180(w)^T): its output channels are the forward Cin.  Inside a PackPlan (the trainers' forward / backward) the buffer is kept and refreshed by
-    the step's one re-pack launch."""
-    co, ci = w.shape[:2]
-    cout, cin = (ci, co) if data_gradient else (co, ci)
-    plan, key = getattr(_tls, "pack_plan", None), ("winograd_f4", w.data_ptr(), tuple(w.shape), bool(data_gradient))
-    if plan is not None and w.is_contiguous():
-        kept = plan.lookup(key, w)
-        if kept is not None:
-            return kept
-    u = torch.empty(int(lib().vatl_winograd_f4_weight_floats(cout, cin)), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_winograd_f4_weight(_ptr(w.contiguous()), _ptr(u), cout, cin, int(data_gradient), _stream()), "vatl_pack_winograd_f4_weight")
-    if plan is not None and w.is_contiguous():
-        plan.record(key, w, u, (8 if data_gradient else 7, cout, cin, 3, 3, 0, 0, ci, ()))
-    return u
-
-
-def conv3x3_winograd_f4_supported(n: int, h: int, w: int, cin: int, cout: int) -> bool:
-    return bool(lib().vatl_conv3x3_winograd_f4_supported(n, h, w, cin, cout))
-
-
-def conv3x3_winograd_f4_fwd(x, u, scale, bias, cout: int, relu: bool, residual=None, out=None):
-    """3x3 / stride 1 / pad 1 conv as Winograd F(4x4,3x3): x NHWC (N,H,W,Cin), H and W multiples of 4 -> (N,H,W,Cout)."""
-    n, h, w, cin = x.shape
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
-    _check(lib().vatl_conv3x3_winograd_f4_fwd(_ptr(x), _ptr(u), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
-           "vatl_conv3x3_winograd_f4_fwd")
-    return y
-
-
-def conv3x3_winograd_f4_fwd_bnstats(x, u, cout: int, gamma, beta, running_mean, running_var, momentum: float, eps: float):
-    """conv3x3_winograd_fwd_bnstats on the F(4x4,3x3) route: -> z, save_mean, save_invstd, scale, bias; running stats updated in place."""
-    n, h, w, cin = x.shape
-    z = torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
-    stats = torch.empty(int(lib().vatl_winograd_f4_stats_row_blocks(n, h, w)) * cout * 2, device=x.device, dtype=torch.float64)
-    used = C.c_int64(0)
-    _check(lib().vatl_conv3x3_winograd_f4_fwd_stats(_ptr(x), _ptr(u), _ptr(z), _ptr(stats, torch.float64), C.addressof(used), n, h, w, cin, cout, _stream()),
-           "vatl_conv3x3_winograd_f4_fwd_stats")
-    return [z] + _bn_finalize(stats, used.value, z.numel() // cout, cout, (gamma, beta, running_mean, running_var, momentum, eps), x.device)
-
-
-def conv3x3_winograd_f4_fwd_bnbwd(x, u, cout: int, spec: "BnBwdSpec", out=None, residual=None):
-    """conv3x3_winograd_fwd_bnbwd on the F(4x4,3x3) route (u: data-gradient packing)."""
-    n, h, w, cin = x.shape
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
-    if y.shape != spec.z.shape:
-        raise VatlError("conv3x3_winograd_f4_fwd_bnbwd: the BatchNorm tensors must have the layout of the output")
-    used = C.c_int64(0)
-    c = spec.z.shape[-1]
-    need = int(lib().vatl_winograd_f4_stats_row_blocks(n, h, w))
-    if (spec.blocks + need) * c * 2 > spec.stats.numel():
-        raise VatlError("conv3x3_winograd_f4_fwd_bnbwd: statistics buffer too small")
-    stats_ptr = spec.stats.data_ptr() + spec.blocks * c * 2 * 8
-    _check(lib().vatl_conv3x3_winograd_f4_fwd_bnbwd(_ptr(x), _ptr(u), _ptr(residual), _ptr(y), n, h, w, cin, cout, _ptr(spec.z), _ptr(spec.mask_y), _ptr(spec.scale),
-                                                    _ptr(spec.bias), _ptr(spec.mean), _ptr(spec.invstd), stats_ptr, C.addressof(used), _stream()),
-           "vatl_conv3x3_winograd_f4_fwd_bnbwd")
-    spec.blocks += used.value
+def conv1x1_dual_fwd(a, x, w_packed, bias, cout: int, stride2: int, relu: bool, out=None):
+    """relu?(W1' a + W2' x[::s, ::s] + bias): a (N,Ho,Wo,C1) and x (N,H2,W2,C2) NHWC -> (N,Ho,Wo,Cout)."""
+    n, ho, wo, c1 = a.shape
+    _, h2, w2, c2 = x.shape
+    y = out if out is not None else torch.empty((n, ho, wo, cout), device=a.device, dtype=torch.float32)
+    _check(lib().vatl_conv1x1_dual_fwd(_ptr(a), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(y), n, ho, wo, c1, h2, w2, c2, stride2, cout,
+                                       w_packed.shape[0], int(relu), _stream()), "vatl_conv1x1_dual_fwd")
     return y
 
 
@@ -633,68 +713,6 @@ def bottleneck_chain_fwd(a, w3, scale3, bias3, skip, w1=None, scale1=None, bias1
     return t, y1
 
 
-def pack_deconv_weight(w: torch.Tensor) -> torch.Tensor:
-    cin, cout, kh, kw = w.shape
-    if (kh, kw) != (4, 4):
-        raise VatlError("only ConvTranspose2d(4, 2, 1) is supported")
-    cpad = conv_cout_pad(cout)
-    plan, key = getattr(_tls, "pack_plan", None), ("deconv", w.data_ptr(), tuple(w.shape))
-    if plan is not None and w.is_contiguous():
-        kept = plan.lookup(key, w)
-        if kept is not None:
-            return kept
-    out = torch.empty((4, cpad, 2, 2, cin), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_deconv4x4s2_weight(_ptr(w.contiguous()), _ptr(out), cin, cout, cpad, _stream()), "vatl_pack_deconv4x4s2_weight")
-    if plan is not None and w.is_contiguous():
-        plan.record(key, w, out, (2, cout, cin, 4, 4, cpad, 0, 0, ()))
-    return out
-
-
-def bn_fold(gamma, beta, mean, var, eps: float, conv_bias=None, channels: int | None = None):
-    c = channels if channels is not None else (var.numel() if var is not None else conv_bias.numel())
-    dev = (var if var is not None else conv_bias).device
-    scale = torch.empty(c, device=dev, dtype=torch.float32)
-    bias = torch.empty(c, device=dev, dtype=torch.float32)
-    _check(lib().vatl_bn_fold(_ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), _ptr(conv_bias), eps, _ptr(scale), _ptr(bias), c, _stream()), "vatl_bn_fold")
-    return scale, bias
-
-
-# ----------------------------------------------------------------------------
-# backbone ops (NHWC)
-# ----------------------------------------------------------------------------
-
-def conv2d_fwd(x, w_packed, scale, bias, cout: int, r: int, s: int, stride: int, pad: int, relu: bool,
-               residual=None, out_nchw: bool = False, out=None):
-    n, h, w, cin = x.shape
-    ho = (h + 2 * pad - r) // stride + 1
-    wo = (w + 2 * pad - s) // stride + 1
-    shape = (n, cout, ho, wo) if out_nchw else (n, ho, wo, cout)
-    y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
-    _check(lib().vatl_conv2d_fwd(_ptr(x), _ptr(w_packed), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout,
-                                 w_packed.shape[0], r, s, stride, pad, int(relu), int(out_nchw), _stream()), "vatl_conv2d_fwd")
-    return y
-
-
-def pack_stem_pool_weight(w: torch.Tensor) -> torch.Tensor:
-    """(64,3,7,7) OIHW stem filter -> the fragment order of vatl_stem7x7s2_pool_fwd."""
-    if tuple(w.shape) != (64, 3, 7, 7):
-        raise VatlError(f"pack_stem_pool_weight: expected a (64,3,7,7) filter, got {tuple(w.shape)}")
-    w = w.detach().float().contiguous()
-    out = torch.empty(int(lib().vatl_stem_pool_weight_floats()), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_stem_pool_weight(_ptr(w), _ptr(out), _stream()), "vatl_pack_stem_pool_weight")
-    return out
-
-
-def pack_stem3_weight(w: torch.Tensor) -> torch.Tensor:
-    """(64,3,3,3) OIHW filter of HRNet's conv1 -> the fragment order of vatl_stem3x3s2_fwd."""
-    if tuple(w.shape) != (64, 3, 3, 3):
-        raise VatlError(f"pack_stem3_weight: expected a (64,3,3,3) filter, got {tuple(w.shape)}")
-    w = w.detach().float().contiguous()
-    out = torch.empty(int(lib().vatl_stem3_weight_floats()), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_stem3_weight(_ptr(w), _ptr(out), _stream()), "vatl_pack_stem3_weight")
-    return out
-
-
 def stem3_fwd(x_nchw: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """NCHW crops (N,3,H,W) -> conv3x3/2 + folded BN + ReLU -> NHWC (N,H/2,W/2,64) in one launch (hrnet.py:109-110, 426-428)."""
     n, c, h, w = x_nchw.shape
@@ -719,98 +737,6 @@ def stem_pool_fwd(x_nchw: torch.Tensor, w_packed: torch.Tensor, scale: torch.Ten
     return y
 
 
-def pack_winograd_weight(w: torch.Tensor, data_gradient: bool = False) -> torch.Tensor:
-    """(Cout,Cin,3,3) -> the F(2x2,3x3) filter transform G g G^T in MFMA fragment order (csrc/conv_winograd.hip).  With
-    ``data_gradient`` the result is the filter of dX = conv(dY, rot180(w)^T): its output channels are the forward Cin."""
-    co, ci = w.shape[:2]
-    if tuple(w.shape[2:]) != (3, 3):
-        raise VatlError("pack_winograd_weight: 3x3 filters only")
-    cout, cin = (ci, co) if data_gradient else (co, ci)
-    plan, key = getattr(_tls, "pack_plan", None), ("winograd", w.data_ptr(), tuple(w.shape), bool(data_gradient))
-    if plan is not None and w.is_contiguous():
-        kept = plan.lookup(key, w)
-        if kept is not None:
-            return kept
-    out = torch.empty(int(lib().vatl_winograd_weight_floats(cout, cin)), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_winograd_weight(_ptr(w.contiguous()), _ptr(out), cout, cin, int(data_gradient), _stream()), "vatl_pack_winograd_weight")
-    if plan is not None and w.is_contiguous():
-        pad = int(lib().vatl_winograd_cout_pad(cout))
-        plan.record(key, w, out, (4 if data_gradient else 3, cout, cin, 3, 3, pad, 1 if pad <= 32 else 2, ci, ()))
-    return out
-
-
-def pack_winograd_deconv_weight(w: torch.Tensor) -> torch.Tensor:
-    """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the four sub-pixel phase filters in the F(3x3,2x2) transform domain,
-    MFMA fragment order (csrc/conv_winograd.hip)."""
-    cin, cout = w.shape[:2]
-    if tuple(w.shape[2:]) != (4, 4):
-        raise VatlError("pack_winograd_deconv_weight: 4x4 filters only")
-    plan, key = getattr(_tls, "pack_plan", None), ("winograd_deconv", w.data_ptr(), tuple(w.shape))
-    if plan is not None and w.is_contiguous():
-        kept = plan.lookup(key, w)
-        if kept is not None:
-            return kept
-    out = torch.empty(int(lib().vatl_winograd_deconv_weight_floats(cout, cin)), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_winograd_deconv_weight(_ptr(w.contiguous()), _ptr(out), cout, cin, _stream()), "vatl_pack_winograd_deconv_weight")
-    if plan is not None and w.is_contiguous():
-        pad = int(lib().vatl_winograd_cout_pad(cout))
-        plan.record(key, w, out, (5, cout, cin, 4, 4, pad, 1 if pad <= 32 else 2, cout, ()))
-    return out
-
-
-def pack_winograd_deconv_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
-    """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the filters of its DATA gradient (a 4x4 / stride 2 conv over dz = four pixel
-    phases x 2x2 convolutions) in the F(3x3,2x2) transform domain."""
-    cin, cout = w.shape[:2]
-    if tuple(w.shape[2:]) != (4, 4):
-        raise VatlError("pack_winograd_deconv_dgrad_weight: 4x4 filters only")
-    plan, key = getattr(_tls, "pack_plan", None), ("winograd_deconv_dgrad", w.data_ptr(), tuple(w.shape))
-    if plan is not None and w.is_contiguous():
-        kept = plan.lookup(key, w)
-        if kept is not None:
-            return kept
-    out = torch.empty(int(lib().vatl_winograd_deconv_dgrad_weight_floats(cin, cout)), device=w.device, dtype=torch.float32)
-    _check(lib().vatl_pack_winograd_deconv_dgrad_weight(_ptr(w.contiguous()), _ptr(out), cin, cout, _stream()), "vatl_pack_winograd_deconv_dgrad_weight")
-    if plan is not None and w.is_contiguous():
-        pad = int(lib().vatl_winograd_cout_pad(cin))
-        plan.record(key, w, out, (6, cin, cout, 4, 4, pad, 1 if pad <= 32 else 2, cout, ()))
-    return out
-
-
-def deconv4x4s2_winograd_dgrad(dz, u_packed, cin: int, spec: "BnBwdSpec" = None, residual=None, out=None):
-    """dx (N,H,W,Cin) of ConvTranspose2d(4,2,1) from dz (N,2H,2W,Cout); with ``spec`` the epilogue masks the result with the consumer
-    layer's ReLU and appends the (sum g, sum g*xhat) row-block partials (conv2d_fwd_ex_bnbwd semantics)."""
-    n, h2, w2, cout = dz.shape
-    h, w = h2 // 2, w2 // 2
-    dx = out if out is not None else torch.empty((n, h, w, cin), device=dz.device, dtype=torch.float32)
-    if spec is None:
-        _check(lib().vatl_deconv4x4s2_winograd_dgrad(_ptr(dz), _ptr(u_packed), _ptr(residual), _ptr(dx), n, h, w, cin, cout, _stream()),
-               "vatl_deconv4x4s2_winograd_dgrad")
-        return dx
-    if dx.shape != spec.z.shape:
-        raise VatlError("deconv4x4s2_winograd_dgrad: the BatchNorm tensors must have the layout of the output")
-    used = C.c_int64(0)
-    c = spec.z.shape[-1]
-    need = (n * ((h + 2) // 3) * ((w + 2) // 3) + 31) // 32
-    if (spec.blocks + need) * c * 2 > spec.stats.numel():
-        raise VatlError("deconv4x4s2_winograd_dgrad: statistics buffer too small")
-    stats_ptr = spec.stats.data_ptr() + spec.blocks * c * 2 * 8
-    _check(lib().vatl_deconv4x4s2_winograd_dgrad_bnbwd(_ptr(dz), _ptr(u_packed), _ptr(residual), _ptr(dx), n, h, w, cin, cout, _ptr(spec.z),
-                                                       _ptr(spec.mask_y), _ptr(spec.scale), _ptr(spec.bias), _ptr(spec.mean), _ptr(spec.invstd),
-                                                       stats_ptr, C.addressof(used), _stream()), "vatl_deconv4x4s2_winograd_dgrad_bnbwd")
-    spec.blocks += used.value
-    return dx
-
-
-def deconv4x4s2_winograd_fwd(x, u_packed, scale, bias, cout: int, relu: bool, out=None):
-    """ConvTranspose2d(4,2,1) of an NHWC tensor through Winograd F(3x3, 2x2) on its four sub-pixel phases."""
-    n, h, w, cin = x.shape
-    y = out if out is not None else torch.empty((n, 2 * h, 2 * w, cout), device=x.device, dtype=torch.float32)
-    _check(lib().vatl_deconv4x4s2_winograd_fwd(_ptr(x), _ptr(u_packed), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
-           "vatl_deconv4x4s2_winograd_fwd")
-    return y
-
-
 def conv3x3_winograd_fwd(x, u_packed, scale, bias, cout: int, relu: bool, residual=None, out=None):
     """3x3 / stride 1 / pad 1 convolution of an NHWC tensor through Winograd F(2x2, 3x3)."""
     n, h, w, cin = x.shape
@@ -820,11 +746,47 @@ def conv3x3_winograd_fwd(x, u_packed, scale, bias, cout: int, relu: bool, residu
     return y
 
 
+def conv3x3_winograd_c32_supported(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    return bool(lib().vatl_conv3x3_winograd_c32_supported(n, h, w, cin, cout))
+
+
+def conv3x3_winograd_c32_fwd(x, u, scale, bias, relu: bool, residual=None, out=None):
+    """3x3 / stride 1 / pad 1, 32 -> 32 channels, NHWC, Winograd F(2x2,3x3) with wave-private tiles (csrc/winograd_c32.hip)."""
+    n, h, w, c = x.shape
+    y = out if out is not None else torch.empty_like(x)
+    assert x.is_contiguous() and y.is_contiguous() and (residual is None or (residual.is_contiguous() and residual.shape == x.shape))
+    _check(lib().vatl_conv3x3_winograd_c32_fwd(_ptr(x), _ptr(u), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, int(relu), _stream()),
+           "vatl_conv3x3_winograd_c32_fwd")
+    return y
+
+
+def conv3x3_winograd_f4_supported(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    return bool(lib().vatl_conv3x3_winograd_f4_supported(n, h, w, cin, cout))
+
+
+def conv3x3_winograd_f4_fwd(x, u, scale, bias, cout: int, relu: bool, residual=None, out=None):
+    """3x3 / stride 1 / pad 1 conv as Winograd F(4x4,3x3): x NHWC (N,H,W,Cin), H and W multiples of 4 -> (N,H,W,Cout)."""
+    n, h, w, cin = x.shape
+    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
+    _check(lib().vatl_conv3x3_winograd_f4_fwd(_ptr(x), _ptr(u), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
+           "vatl_conv3x3_winograd_f4_fwd")
+    return y
+
+
 def deconv4x4s2_fwd(x, w_packed, scale, bias, cout: int, relu: bool):
     n, h, w, cin = x.shape
     y = torch.empty((n, 2 * h, 2 * w, cout), device=x.device, dtype=torch.float32)
     _check(lib().vatl_deconv4x4s2_fwd(_ptr(x), _ptr(w_packed), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, cin, cout,
                                       w_packed.shape[1], int(relu), _stream()), "vatl_deconv4x4s2_fwd")
+    return y
+
+
+def deconv4x4s2_winograd_fwd(x, u_packed, scale, bias, cout: int, relu: bool, out=None):
+    """ConvTranspose2d(4,2,1) of an NHWC tensor through Winograd F(3x3, 2x2) on its four sub-pixel phases."""
+    n, h, w, cin = x.shape
+    y = out if out is not None else torch.empty((n, 2 * h, 2 * w, cout), device=x.device, dtype=torch.float32)
+    _check(lib().vatl_deconv4x4s2_winograd_fwd(_ptr(x), _ptr(u_packed), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
+           "vatl_deconv4x4s2_winograd_fwd")
     return y
 
 
@@ -866,6 +828,44 @@ def fuse_upsample_add(base, ups, relu: bool):
     return y
 
 
+# ----------------------------------------------------------------------------
+# scorers on (N,J,H,W) heat-maps and decoded poses
+# ----------------------------------------------------------------------------
+
+def decode(hm: torch.Tensor, bbox: torch.Tensor):
+    """-> coords (N,J,2) f32, maxvals (N,J) f32, idx (N,J) i32."""
+    n, j, h, w = hm.shape
+    coords = torch.empty((n, j, 2), device=hm.device, dtype=torch.float32)
+    maxv = torch.empty((n, j), device=hm.device, dtype=torch.float32)
+    idx = torch.empty((n, j), device=hm.device, dtype=torch.int32)
+    _check(lib().vatl_decode_argmax_affine(_ptr(hm), _ptr(bbox), _ptr(coords), _ptr(maxv), _ptr(idx, torch.int32), n, j, h, w, _stream()),
+           "vatl_decode_argmax_affine")
+    return coords, maxv, idx
+
+
+def decode_pose(hm: torch.Tensor, bbox: torch.Tensor):
+    """-> kpts (N,J,3) f32 rows (x, y, score), idx (N,J) i32, hp (N) = -sum of scores, pose_score (N) f64 = float32 mean + 1.25 max in float64 (numpy 1.23 promotion): the decode and the
+    per-item scores of ActiveLearning.py:304-314, 329-330 in two launches (no cat / neg / sum / max / mean kernels around them)."""
+    n, j, h, w = hm.shape
+    kpts = torch.empty((n, j, 3), device=hm.device, dtype=torch.float32)
+    idx = torch.empty((n, j), device=hm.device, dtype=torch.int32)
+    hp = torch.empty((n,), device=hm.device, dtype=torch.float32)
+    ps = torch.empty((n,), device=hm.device, dtype=torch.float64)
+    _check(lib().vatl_decode_pose(_ptr(hm), _ptr(bbox), _ptr(kpts), _ptr(idx, torch.int32), _ptr(hp), _ptr(ps, torch.float64), n, j, h, w, _stream()), "vatl_decode_pose")
+    return kpts, idx, hp, ps
+
+
+def decode_softargmax(hm: torch.Tensor, bbox: torch.Tensor, norm_type: str = "softmax"):
+    n, j, h, w = hm.shape
+    coords = torch.empty((n, j, 2), device=hm.device, dtype=torch.float32)
+    scores = torch.empty((n, j), device=hm.device, dtype=torch.float32)
+    code = {"softmax": 0, "sigmoid": 1, "divide_sum": 2}.get(norm_type)
+    if code is None:
+        raise NotImplementedError(norm_type)
+    _check(lib().vatl_decode_softargmax(_ptr(hm), _ptr(bbox), _ptr(coords), _ptr(scores), n, j, h, w, code, _stream()), "vatl_decode_softargmax")
+    return coords, scores
+
+
 def peaks5(hm: torch.Tensor, min_distance: int = 5):
     """(N,J,H,W) -> peak values (N,J,5), flat indices (N,J,5) int32 (-1 = none), counts (N,J) int32, MPE terms (N,J),
     Margin terms (N,J)   [skimage.feature.peak_local_max(min_distance, num_peaks=5) per plane]."""
@@ -886,6 +886,108 @@ def plane_entropy(hm: torch.Tensor) -> torch.Tensor:
     _check(lib().vatl_plane_entropy(_ptr(hm), _ptr(out), n, j, h, w, _stream()), "vatl_plane_entropy")
     return out
 
+
+def localpeak_mean(hm: torch.Tensor, order: float = 0.5):
+    """-> mean (N,) f32 (nan when no peak is kept), count (N,J) i32."""
+    n, j, h, w = hm.shape
+    mean = torch.empty(n, device=hm.device, dtype=torch.float32)
+    cnt = torch.empty((n, j), device=hm.device, dtype=torch.int32)
+    ws = torch.empty(2 * n * j, device=hm.device, dtype=torch.float64)
+    _check(lib().vatl_localpeak_mean(_ptr(hm), _ptr(mean), _ptr(cnt, torch.int32), _ptr(ws, torch.float64), n, j, h, w, order, _stream()),
+           "vatl_localpeak_mean")
+    return mean, cnt
+
+
+def localpeak_mask(hm: torch.Tensor, order: float = 0.5) -> torch.Tensor:
+    """hm (..., H, W) -> uint8 mask of kept local peaks, same shape."""
+    h, w = hm.shape[-2:]
+    planes = hm.numel() // (h * w)
+    mask = torch.empty(hm.shape, device=hm.device, dtype=torch.uint8)
+    _check(lib().vatl_localpeak_mask(_ptr(hm), _ptr(mask, torch.uint8), planes, h, w, order, _stream()), "vatl_localpeak_mask")
+    return mask
+
+
+def thc_pairs(a: torch.Tensor, b: torch.Tensor, norm: str = "L1") -> torch.Tensor:
+    """a, b (P,J,H,W) (views with a uniform item stride are fine) -> (P,) f32."""
+    p, j, h, w = a.shape
+    for t in (a, b):
+        if not t.is_cuda or t.dtype != torch.float32 or t[0].is_contiguous() is False:
+            raise VatlError("thc_pairs: fp32 device tensors with contiguous items required")
+    out = torch.empty(p, device=a.device, dtype=torch.float32)
+    sa = a.stride(0) if p > 1 else j * h * w
+    sb = b.stride(0) if p > 1 else j * h * w
+    _check(lib().vatl_thc_pairs(a.data_ptr(), b.data_ptr(), sa, sb, _ptr(out), p, j, h * w, {"L1": 1, "L2": 2}[norm], _stream()), "vatl_thc_pairs")
+    return out
+
+
+def thc_stream(hm: torch.Tensor, is_prev: torch.Tensor, is_next: torch.Tensor, norm: str = "L1") -> torch.Tensor:
+    """THC of an id-sorted, de-duplicated stream: neighbours are items i-1 / i+1."""
+    n = hm.shape[0]
+    thc = torch.empty(n, device=hm.device, dtype=torch.float32)
+    pair = thc_pairs(hm[:-1], hm[1:], norm) if n > 1 else None
+    _check(lib().vatl_thc_combine(_ptr(pair), _ptr(is_prev, torch.uint8), _ptr(is_next, torch.uint8), _ptr(thc), n, _stream()), "vatl_thc_combine")
+    return thc
+
+
+def tpc_stream(hm: torch.Tensor, bbox: torch.Tensor, cur_coords: torch.Tensor, is_prev: torch.Tensor, is_next: torch.Tensor) -> torch.Tensor:
+    """TPC of an id-sorted de-duplicated stream (neighbours = items i-1 / i+1, decoded with item i's box)."""
+    n, j = hm.shape[:2]
+    adj_prev = torch.zeros((n, j, 2), device=hm.device, dtype=torch.float32)
+    adj_next = torch.zeros((n, j, 2), device=hm.device, dtype=torch.float32)
+    if n > 1:
+        h, w = hm.shape[2:]
+        scratch = torch.empty((n - 1, j), device=hm.device, dtype=torch.float32)
+        _check(lib().vatl_decode_argmax_affine(hm[:-1].data_ptr(), bbox[1:].data_ptr(), adj_prev[1:].data_ptr(), _ptr(scratch), None,
+                                               n - 1, j, h, w, _stream()), "vatl_decode_argmax_affine")
+        _check(lib().vatl_decode_argmax_affine(hm[1:].data_ptr(), bbox[:-1].data_ptr(), adj_next[:-1].data_ptr(), _ptr(scratch), None,
+                                               n - 1, j, h, w, _stream()), "vatl_decode_argmax_affine")
+    out = torch.empty(n, device=hm.device, dtype=torch.float32)
+    _check(lib().vatl_tpc_stream(_ptr(cur_coords), _ptr(adj_prev), _ptr(adj_next), _ptr(bbox), _ptr(is_prev, torch.uint8),
+                                 _ptr(is_next, torch.uint8), _ptr(out), n, j, _stream()), "vatl_tpc_stream")
+    return out
+
+
+def pack_ae(state_dict, device) -> torch.Tensor:
+    parts = []
+    for half in ("encoder", "decoder"):
+        for i in (0, 2, 4, 6):
+            parts.append(state_dict[f"{half}.{i}.weight"].detach().reshape(-1).float())
+            parts.append(state_dict[f"{half}.{i}.bias"].detach().reshape(-1).float())
+    return torch.cat([p.to(device) for p in parts]).contiguous()
+
+
+def ae_forward(feat: torch.Tensor, ae_flat: torch.Tensor, d: int, z: int):
+    """feat (N,D) -> recon (N,D), mse (N,)."""
+    n = feat.shape[0]
+    recon = torch.empty((n, d), device=feat.device, dtype=torch.float32)
+    mse = torch.empty(n, device=feat.device, dtype=torch.float32)
+    _check(lib().vatl_ae_forward(_ptr(feat), _ptr(ae_flat), d, z, _ptr(recon), _ptr(mse), n, _stream()), "vatl_ae_forward")
+    return recon, mse
+
+
+def hybrid_ae_wpu(kpts: torch.Tensor, bbox: torch.Tensor, ae_flat: torch.Tensor, d: int, z: int, only38: bool = False):
+    """kpts (N,17,3), bbox (N,4) crop xyxy -> wpu (N,) f32, status (N,) i32."""
+    n = kpts.shape[0]
+    wpu = torch.empty(n, device=kpts.device, dtype=torch.float32)
+    status = torch.empty(n, device=kpts.device, dtype=torch.int32)
+    _check(lib().vatl_hybrid_ae_wpu(_ptr(kpts), _ptr(bbox), _ptr(ae_flat), d, z, int(only38), _ptr(wpu), _ptr(status, torch.int32), n, _stream()),
+           "vatl_hybrid_ae_wpu")
+    return wpu, status
+
+
+def hybrid_feature_f64(kpts: torch.Tensor, bbox_xywh: torch.Tensor):
+    """kpts (N,51) f64, bbox (N,4) f64 xywh -> feat (N,42) f64, status (N,) i32."""
+    n = kpts.shape[0]
+    feat = torch.empty((n, 42), device=kpts.device, dtype=torch.float64)
+    status = torch.empty(n, device=kpts.device, dtype=torch.int32)
+    _check(lib().vatl_hybrid_feature_f64(_ptr(kpts, torch.float64), _ptr(bbox_xywh, torch.float64), _ptr(feat, torch.float64),
+                                         _ptr(status, torch.int32), n, _stream()), "vatl_hybrid_feature_f64")
+    return feat, status
+
+
+# ----------------------------------------------------------------------------
+# evaluation and query selection
+# ----------------------------------------------------------------------------
 
 def oks(pred_kpts: torch.Tensor, gt_kpts: torch.Tensor, bbox_xywh: torch.Tensor) -> torch.Tensor:
     """pred (N,17,3) fp32, gt (N,51) float64, boxes (N,4) xywh float64 -> (N,) float64 OKS."""
@@ -915,159 +1017,8 @@ def kcenter_pick(min_dist, unc, a: float, b: float, selected: torch.Tensor, step
            "vatl_kcenter_pick")
 
 
-def upsample_nearest_bwd(dy, yact, shift: int):
-    """dy (N,H,W,C) [masked by yact > 0] -> block sums (N,H>>shift,W>>shift,C)."""
-    n, h, w, c = dy.shape
-    dz = torch.empty((n, h >> shift, w >> shift, c), device=dy.device, dtype=torch.float32)
-    _check(lib().vatl_upsample_nearest_bwd(_ptr(dy), _ptr(yact), _ptr(dz), n, h, w, c, shift, _stream()), "vatl_upsample_nearest_bwd")
-    return dz
-
-
-def gap_bwd(dy, hw: int):
-    n, c = dy.shape
-    dx = torch.empty((n, hw, c), device=dy.device, dtype=torch.float32)
-    _check(lib().vatl_gap_bwd(_ptr(dy), _ptr(dx), n, hw, c, _stream()), "vatl_gap_bwd")
-    return dx
-
-
 # ----------------------------------------------------------------------------
-# scorers on (N,J,H,W) heat-maps
-# ----------------------------------------------------------------------------
-
-def decode(hm: torch.Tensor, bbox: torch.Tensor):
-    """-> coords (N,J,2) f32, maxvals (N,J) f32, idx (N,J) i32."""
-    n, j, h, w = hm.shape
-    coords = torch.empty((n, j, 2), device=hm.device, dtype=torch.float32)
-    maxv = torch.empty((n, j), device=hm.device, dtype=torch.float32)
-    idx = torch.empty((n, j), device=hm.device, dtype=torch.int32)
-    _check(lib().vatl_decode_argmax_affine(_ptr(hm), _ptr(bbox), _ptr(coords), _ptr(maxv), _ptr(idx, torch.int32), n, j, h, w, _stream()),
-           "vatl_decode_argmax_affine")
-    return coords, maxv, idx
-
-
-def decode_pose(hm: torch.Tensor, bbox: torch.Tensor):
-    """-> kpts (N,J,3) f32 rows (x, y, score), idx (N,J) i32, hp (N) = -sum of scores, pose_score (N) f64 = float32 mean + 1.25 max in float64 (numpy 1.23 promotion): the decode and the
-    per-item scores of ActiveLearning.py:304-314, 329-330 in two launches (no cat / neg / sum / max / mean kernels around them)."""
-    n, j, h, w = hm.shape
-    kpts = torch.empty((n, j, 3), device=hm.device, dtype=torch.float32)
-    idx = torch.empty((n, j), device=hm.device, dtype=torch.int32)
-    hp = torch.empty((n,), device=hm.device, dtype=torch.float32)
-    ps = torch.empty((n,), device=hm.device, dtype=torch.float64)
-    _check(lib().vatl_decode_pose(_ptr(hm), _ptr(bbox), _ptr(kpts), _ptr(idx, torch.int32), _ptr(hp), _ptr(ps, torch.float64), n, j, h, w, _stream()), "vatl_decode_pose")
-    return kpts, idx, hp, ps
-
-
-def thc_pairs(a: torch.Tensor, b: torch.Tensor, norm: str = "L1") -> torch.Tensor:
-    """a, b (P,J,H,W) (views with a uniform item stride are fine) -> (P,) f32."""
-    p, j, h, w = a.shape
-    for t in (a, b):
-        if not t.is_cuda or t.dtype != torch.float32 or t[0].is_contiguous() is False:
-            raise VatlError("thc_pairs: fp32 device tensors with contiguous items required")
-    out = torch.empty(p, device=a.device, dtype=torch.float32)
-    sa = a.stride(0) if p > 1 else j * h * w
-    sb = b.stride(0) if p > 1 else j * h * w
-    _check(lib().vatl_thc_pairs(a.data_ptr(), b.data_ptr(), sa, sb, _ptr(out), p, j, h * w, {"L1": 1, "L2": 2}[norm], _stream()), "vatl_thc_pairs")
-    return out
-
-
-def thc_stream(hm: torch.Tensor, is_prev: torch.Tensor, is_next: torch.Tensor, norm: str = "L1") -> torch.Tensor:
-    """THC of an id-sorted, de-duplicated stream: neighbours are items i-1 / i+1."""
-    n = hm.shape[0]
-    thc = torch.empty(n, device=hm.device, dtype=torch.float32)
-    pair = thc_pairs(hm[:-1], hm[1:], norm) if n > 1 else None
-    _check(lib().vatl_thc_combine(_ptr(pair), _ptr(is_prev, torch.uint8), _ptr(is_next, torch.uint8), _ptr(thc), n, _stream()), "vatl_thc_combine")
-    return thc
-
-
-def localpeak_mean(hm: torch.Tensor, order: float = 0.5):
-    """-> mean (N,) f32 (nan when no peak is kept), count (N,J) i32."""
-    n, j, h, w = hm.shape
-    mean = torch.empty(n, device=hm.device, dtype=torch.float32)
-    cnt = torch.empty((n, j), device=hm.device, dtype=torch.int32)
-    ws = torch.empty(2 * n * j, device=hm.device, dtype=torch.float64)
-    _check(lib().vatl_localpeak_mean(_ptr(hm), _ptr(mean), _ptr(cnt, torch.int32), _ptr(ws, torch.float64), n, j, h, w, order, _stream()),
-           "vatl_localpeak_mean")
-    return mean, cnt
-
-
-def pack_ae(state_dict, device) -> torch.Tensor:
-    parts = []
-    for half in ("encoder", "decoder"):
-        for i in (0, 2, 4, 6):
-            parts.append(state_dict[f"{half}.{i}.weight"].detach().reshape(-1).float())
-            parts.append(state_dict[f"{half}.{i}.bias"].detach().reshape(-1).float())
-    return torch.cat([p.to(device) for p in parts]).contiguous()
-
-
-def hybrid_ae_wpu(kpts: torch.Tensor, bbox: torch.Tensor, ae_flat: torch.Tensor, d: int, z: int, only38: bool = False):
-    """kpts (N,17,3), bbox (N,4) crop xyxy -> wpu (N,) f32, status (N,) i32."""
-    n = kpts.shape[0]
-    wpu = torch.empty(n, device=kpts.device, dtype=torch.float32)
-    status = torch.empty(n, device=kpts.device, dtype=torch.int32)
-    _check(lib().vatl_hybrid_ae_wpu(_ptr(kpts), _ptr(bbox), _ptr(ae_flat), d, z, int(only38), _ptr(wpu), _ptr(status, torch.int32), n, _stream()),
-           "vatl_hybrid_ae_wpu")
-    return wpu, status
-
-
-def tpc_stream(hm: torch.Tensor, bbox: torch.Tensor, cur_coords: torch.Tensor, is_prev: torch.Tensor, is_next: torch.Tensor) -> torch.Tensor:
-    """TPC of an id-sorted de-duplicated stream (neighbours = items i-1 / i+1, decoded with item i's box)."""
-    n, j = hm.shape[:2]
-    adj_prev = torch.zeros((n, j, 2), device=hm.device, dtype=torch.float32)
-    adj_next = torch.zeros((n, j, 2), device=hm.device, dtype=torch.float32)
-    if n > 1:
-        h, w = hm.shape[2:]
-        scratch = torch.empty((n - 1, j), device=hm.device, dtype=torch.float32)
-        _check(lib().vatl_decode_argmax_affine(hm[:-1].data_ptr(), bbox[1:].data_ptr(), adj_prev[1:].data_ptr(), _ptr(scratch), None,
-                                               n - 1, j, h, w, _stream()), "vatl_decode_argmax_affine")
-        _check(lib().vatl_decode_argmax_affine(hm[1:].data_ptr(), bbox[:-1].data_ptr(), adj_next[:-1].data_ptr(), _ptr(scratch), None,
-                                               n - 1, j, h, w, _stream()), "vatl_decode_argmax_affine")
-    out = torch.empty(n, device=hm.device, dtype=torch.float32)
-    _check(lib().vatl_tpc_stream(_ptr(cur_coords), _ptr(adj_prev), _ptr(adj_next), _ptr(bbox), _ptr(is_prev, torch.uint8),
-                                 _ptr(is_next, torch.uint8), _ptr(out), n, j, _stream()), "vatl_tpc_stream")
-    return out
-
-
-def decode_softargmax(hm: torch.Tensor, bbox: torch.Tensor, norm_type: str = "softmax"):
-    n, j, h, w = hm.shape
-    coords = torch.empty((n, j, 2), device=hm.device, dtype=torch.float32)
-    scores = torch.empty((n, j), device=hm.device, dtype=torch.float32)
-    code = {"softmax": 0, "sigmoid": 1, "divide_sum": 2}.get(norm_type)
-    if code is None:
-        raise NotImplementedError(norm_type)
-    _check(lib().vatl_decode_softargmax(_ptr(hm), _ptr(bbox), _ptr(coords), _ptr(scores), n, j, h, w, code, _stream()), "vatl_decode_softargmax")
-    return coords, scores
-
-
-def ae_forward(feat: torch.Tensor, ae_flat: torch.Tensor, d: int, z: int):
-    """feat (N,D) -> recon (N,D), mse (N,)."""
-    n = feat.shape[0]
-    recon = torch.empty((n, d), device=feat.device, dtype=torch.float32)
-    mse = torch.empty(n, device=feat.device, dtype=torch.float32)
-    _check(lib().vatl_ae_forward(_ptr(feat), _ptr(ae_flat), d, z, _ptr(recon), _ptr(mse), n, _stream()), "vatl_ae_forward")
-    return recon, mse
-
-
-def hybrid_feature_f64(kpts: torch.Tensor, bbox_xywh: torch.Tensor):
-    """kpts (N,51) f64, bbox (N,4) f64 xywh -> feat (N,42) f64, status (N,) i32."""
-    n = kpts.shape[0]
-    feat = torch.empty((n, 42), device=kpts.device, dtype=torch.float64)
-    status = torch.empty(n, device=kpts.device, dtype=torch.int32)
-    _check(lib().vatl_hybrid_feature_f64(_ptr(kpts, torch.float64), _ptr(bbox_xywh, torch.float64), _ptr(feat, torch.float64),
-                                         _ptr(status, torch.int32), n, _stream()), "vatl_hybrid_feature_f64")
-    return feat, status
-
-
-def localpeak_mask(hm: torch.Tensor, order: float = 0.5) -> torch.Tensor:
-    """hm (..., H, W) -> uint8 mask of kept local peaks, same shape."""
-    h, w = hm.shape[-2:]
-    planes = hm.numel() // (h * w)
-    mask = torch.empty(hm.shape, device=hm.device, dtype=torch.uint8)
-    _check(lib().vatl_localpeak_mask(_ptr(hm), _ptr(mask, torch.uint8), planes, h, w, order, _stream()), "vatl_localpeak_mask")
-    return mask
-
-
-# ----------------------------------------------------------------------------
-# training-mode backbone ops (NHWC)
+# training-mode backbone ops (NHWC): forward
 # ----------------------------------------------------------------------------
 
 def conv2d_fwd_ex(x, w_packed, cout, r, s, stride, pad_y, pad_x, ho, wo, oh, ow, osy, osx, ooy, oox, out=None, residual=None,
@@ -1080,121 +1031,12 @@ def conv2d_fwd_ex(x, w_packed, cout, r, s, stride, pad_y, pad_x, ho, wo, oh, ow,
     return y
 
 
-class BnBwdSpec:
-    """What a data-gradient launch needs to run the reduction pass of the consumer layer's BatchNorm backward in its
-    epilogue: z (the consumer's conv output), its ReLU mask source (mask_y, or (scale, bias) to recompute it from z, or
-    neither) and the saved batch statistics.  ``stats`` / ``blocks`` collect the partial sums of one or more launches."""
-
-    def __init__(self, z, mean, invstd, mask_y=None, scale=None, bias=None):
-        self.z, self.mean, self.invstd, self.mask_y, self.scale, self.bias = z, mean, invstd, mask_y, scale, bias
-        c = z.shape[-1]
-        cap = int(lib().vatl_conv_stats_row_blocks(z.numel() // c, 1)) + 8     # + a partial tile per parity launch
-        self.stats = torch.empty(cap * c * 2, device=z.device, dtype=torch.float64)
-        self.blocks = 0
-
-
-def conv2d_fwd_ex_bnbwd(x, w_packed, cout, r, s, stride, pad_y, pad_x, ho, wo, oh, ow, osy, osx, ooy, oox, spec: BnBwdSpec, out=None, residual=None):
-    """conv2d_fwd_ex whose epilogue masks the result with the consumer layer's ReLU and appends the (sum g, sum g*xhat) row-block
-    partials to ``spec`` (several launches — the parity launches of a strided conv's data gradient — append one after another)."""
-    n, h, w, cin = x.shape
-    y = out if out is not None else torch.empty((n, oh, ow, cout), device=x.device, dtype=torch.float32)
-    if y.shape != spec.z.shape:
-        raise VatlError("conv2d_fwd_ex_bnbwd: the BatchNorm tensors must have the layout of the output")
-    used = C.c_int64(0)
-    c = spec.z.shape[-1]
-    stats_ptr = spec.stats.data_ptr() + spec.blocks * c * 2 * 8
-    need = int(lib().vatl_conv_stats_row_blocks(n * ho * wo, 1))
-    if (spec.blocks + need) * c * 2 > spec.stats.numel():
-        raise VatlError("conv2d_fwd_ex_bnbwd: statistics buffer too small")
-    _check(lib().vatl_conv2d_fwd_ex_bnbwd(_ptr(x), _ptr(w_packed), _ptr(residual), _ptr(y), n, h, w, cin, cout, w_packed.shape[0], r, s, stride, pad_y,
-                                          pad_x, ho, wo, oh, ow, osy, osx, ooy, oox, _ptr(spec.z), _ptr(spec.mask_y), _ptr(spec.scale), _ptr(spec.bias),
-                                          _ptr(spec.mean), _ptr(spec.invstd), stats_ptr, C.addressof(used), _stream()), "vatl_conv2d_fwd_ex_bnbwd")
-    spec.blocks += used.value
-    return y
-
-
-def bn_bwd_from_stats(spec: BnBwdSpec, g, gamma, dgamma=None, dbeta=None):
-    """Finish the BatchNorm backward whose reduction ran in the data-gradient epilogue: -> dz, dgamma, dbeta."""
-    z = spec.z
+def scale_bias_act(z, scale, bias, residual=None, relu=True):
     c = z.shape[-1]
-    m = z.numel() // c
-    dz = torch.empty_like(z)
-    dgamma = dgamma if dgamma is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    dbeta = dbeta if dbeta is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    coef = torch.empty(3 * c, device=z.device, dtype=torch.float32)
-    _check(lib().vatl_bn_bwd_from_stats(_ptr(spec.stats, torch.float64), spec.blocks, _ptr(g), _ptr(z), _ptr(gamma), _ptr(spec.mean), _ptr(spec.invstd),
-                                        _ptr(dz), _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _stream()), "vatl_bn_bwd_from_stats")
-    return dz, dgamma, dbeta
-
-
-def pack_dgrad_weight(w: torch.Tensor, taps, cout_k: int | None = None) -> torch.Tensor:
-    """(Cout,Cin,R,S) -> [CinPad][len(taps)][CoutK] with out[c][t][n] = w[n][c][taps[t]]."""
-    cout, cin, r, s = w.shape
-    cinpad = conv_cout_pad(cin)
-    cout_k = cout_k or cout
-    taps = [(int(a), int(b)) for a, b in taps]
-    plan, key = getattr(_tls, "pack_plan", None), ("dgrad", w.data_ptr(), tuple(w.shape), tuple(taps), cout_k)
-    if plan is not None and w.is_contiguous() and len(taps) <= 16:
-        kept = plan.lookup(key, w)
-        if kept is not None:
-            return kept
-    out = torch.empty((cinpad, len(taps), cout_k), device=w.device, dtype=torch.float32)
-    if plan is not None and w.is_contiguous() and len(taps) <= 16:
-        plan.record(key, w, out, (1, cout, cin, r, s, cinpad, cout_k, len(taps), tuple(taps)))
-    tr = (C.c_int * len(taps))(*[t[0] for t in taps])
-    ts = (C.c_int * len(taps))(*[t[1] for t in taps])
-    _check(lib().vatl_pack_dgrad_weight(_ptr(w.contiguous()), _ptr(out), cout, cin, r, s, cinpad, cout_k, len(taps),
-                                        C.cast(tr, C.c_void_p), C.cast(ts, C.c_void_p), _stream()), "vatl_pack_dgrad_weight")
-    return out
-
-
-def conv2d_wgrad(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: int, out=None) -> torch.Tensor:
-    """x NHWC (N,H,W,Cin or 4 for the stem), dz NHWC (N,Ho,Wo,CoutG) -> dw (Cout,Cin,R,S) (written into ``out`` when
-    given: a slice of the flat gradient arena)."""
-    n, h, w, _ = x.shape
-    dw = out if out is not None else torch.empty((cout, cin, r, s), device=x.device, dtype=torch.float32)
-    if dw.numel() != cout * cin * r * s:
-        raise VatlError("conv2d_wgrad: out has the wrong size")
-    m = n * dz.shape[1] * dz.shape[2]
-    ws = torch.empty(int(lib().vatl_conv2d_wgrad_workspace_floats(cout, cin, r, s, m)), device=x.device, dtype=torch.float32)
-    _check(lib().vatl_conv2d_wgrad(_ptr(x), _ptr(dz), _ptr(dw), _ptr(ws), n, h, w, cin, cout, dz.shape[3], r, s, stride, pad, _stream()),
-           "vatl_conv2d_wgrad")
-    return dw
-
-
-def conv3x3_winograd_wgrad(x, dz, out=None) -> torch.Tensor:
-    """Weight gradient of a 3x3 / stride 1 / pad 1 conv on the Winograd route: x (N,H,W,Cin), dz (N,H,W,Cout) -> dw (Cout,Cin,3,3)."""
-    n, h, w, cin = x.shape
-    cout = dz.shape[3]
-    dw = out if out is not None else torch.empty((cout, cin, 3, 3), device=x.device, dtype=torch.float32)
-    if dw.numel() != cout * cin * 9:
-        raise VatlError("conv3x3_winograd_wgrad: out has the wrong size")
-    ws = torch.empty(int(lib().vatl_conv3x3_winograd_wgrad_workspace_floats(cout, cin, n, h, w)), device=x.device, dtype=torch.float32)
-    _check(lib().vatl_conv3x3_winograd_wgrad(_ptr(x), _ptr(dz), _ptr(dw), _ptr(ws), n, h, w, cin, cout, _stream()), "vatl_conv3x3_winograd_wgrad")
-    return dw
-
-
-def deconv4x4s2_winograd_wgrad(x, dy, out=None) -> torch.Tensor:
-    """Weight gradient of ConvTranspose2d(4,2,1) on the Winograd route: x (N,H,W,Cin), dy (N,2H,2W,Cout) -> dw (Cin,Cout,4,4)."""
-    n, h, w, cin = x.shape
-    cout = dy.shape[3]
-    dw = out if out is not None else torch.empty((cin, cout, 4, 4), device=x.device, dtype=torch.float32)
-    if dw.numel() != cin * cout * 16:
-        raise VatlError("deconv4x4s2_winograd_wgrad: out has the wrong size")
-    ws = torch.empty(int(lib().vatl_deconv4x4s2_winograd_wgrad_workspace_floats(cin, cout, n, h, w)), device=x.device, dtype=torch.float32)
-    _check(lib().vatl_deconv4x4s2_winograd_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), n, h, w, cin, cout, _stream()), "vatl_deconv4x4s2_winograd_wgrad")
-    return dw
-
-
-def deconv4x4s2_wgrad(x, dy, out=None) -> torch.Tensor:
-    n, h, w, cin = x.shape
-    cout = dy.shape[3]
-    dw = out if out is not None else torch.empty((cin, cout, 4, 4), device=x.device, dtype=torch.float32)
-    if dw.numel() != cin * cout * 16:
-        raise VatlError("deconv4x4s2_wgrad: out has the wrong size")
-    ws = torch.empty(int(lib().vatl_deconv4x4s2_wgrad_workspace_floats(cin, cout, n * h * w)), device=x.device, dtype=torch.float32)
-    _check(lib().vatl_deconv4x4s2_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), n, h, w, cin, cout, _stream()), "vatl_deconv4x4s2_wgrad")
-    return dw
+    y = torch.empty_like(z)
+    _check(lib().vatl_scale_bias_act(_ptr(z), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), z.numel() // c, c, int(relu), _stream()),
+           "vatl_scale_bias_act")
+    return y
 
 
 def _col_ws(m: int, c: int, device):
@@ -1220,61 +1062,42 @@ def _bn_finalize(stats, nblk, m, c, bn_args, device):
     return outs
 
 
+def _stats_fwd(fn: str, x, w_packed, z_shape, row_blocks: int, dims, bn_args=None):
+    """The training forwards that take the statistics of z in the conv epilogue: allocate z and the float64 (sum, sum^2) partials of
+    the ``row_blocks`` row blocks the launch may write, run ``fn(x, w, z, partials, &used, *dims, stream)``.  -> z, partials, row
+    blocks written; with ``bn_args`` = (gamma, beta, running_mean, running_var, momentum, eps) the partials are finalized instead:
+    -> [z, save_mean, save_invstd, scale, bias], running stats updated in place."""
+    cout = z_shape[-1]
+    z = torch.empty(z_shape, device=x.device, dtype=torch.float32)
+    stats = torch.empty(int(row_blocks) * cout * 2, device=x.device, dtype=torch.float64)
+    used = C.c_int64(0)
+    _check(getattr(lib(), fn)(_ptr(x), _ptr(w_packed), _ptr(z), _ptr(stats, torch.float64), C.addressof(used), *dims, _stream()), fn)
+    if bn_args is None:
+        return z, stats, used.value
+    return [z] + _bn_finalize(stats, used.value, z.numel() // cout, cout, bn_args, x.device)
+
+
 def conv2d_fwd_bnstats(x, w_packed, cout: int, r: int, s: int, stride: int, pad: int, gamma, beta, running_mean, running_var,
                        momentum: float, eps: float):
     """Training forward: z = conv(x) with the BatchNorm batch statistics taken in the conv epilogue.
     -> z, save_mean, save_invstd, scale, bias; running stats updated in place."""
     n, h, w, cin = x.shape
     ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
-    z = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
-    m = n * ho * wo
-    stats = torch.empty(int(lib().vatl_conv_stats_row_blocks(m, 1)) * cout * 2, device=x.device, dtype=torch.float64)
-    used = C.c_int64(0)
-    _check(lib().vatl_conv2d_fwd_stats(_ptr(x), _ptr(w_packed), _ptr(z), _ptr(stats, torch.float64), C.addressof(used), n, h, w, cin, cout,
-                                       w_packed.shape[0], r, s, stride, pad, _stream()), "vatl_conv2d_fwd_stats")
-    return [z] + _bn_finalize(stats, used.value, m, cout, (gamma, beta, running_mean, running_var, momentum, eps), x.device)
+    return _stats_fwd("vatl_conv2d_fwd_stats", x, w_packed, (n, ho, wo, cout), lib().vatl_conv_stats_row_blocks(n * ho * wo, 1),
+                      (n, h, w, cin, cout, w_packed.shape[0], r, s, stride, pad), (gamma, beta, running_mean, running_var, momentum, eps))
+
+
+def deconv4x4s2_fwd_bnstats(x, w_packed, cout: int, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+    n, h, w, cin = x.shape
+    return _stats_fwd("vatl_deconv4x4s2_fwd_stats", x, w_packed, (n, 2 * h, 2 * w, cout), lib().vatl_conv_stats_row_blocks(n * h * w, 4),
+                      (n, h, w, cin, cout, w_packed.shape[1]), (gamma, beta, running_mean, running_var, momentum, eps))
 
 
 def conv3x3_winograd_fwd_stats(x, u_packed, cout: int):
     """Training forward of a 3x3 / stride-1 layer through Winograd: z = conv(x) and the row-block (sum, sum^2) partials of z.
     -> z, stats (float64), row blocks written."""
     n, h, w, cin = x.shape
-    z = torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
-    stats = torch.empty(int(lib().vatl_winograd_stats_row_blocks(n, h, w)) * cout * 2, device=x.device, dtype=torch.float64)
-    used = C.c_int64(0)
-    _check(lib().vatl_conv3x3_winograd_fwd_stats(_ptr(x), _ptr(u_packed), _ptr(z), _ptr(stats, torch.float64), C.addressof(used), n, h, w, cin,
-                                                 cout, _stream()), "vatl_conv3x3_winograd_fwd_stats")
-    return z, stats, used.value
-
-
-def conv3x3_winograd_fwd_bnbwd(x, u_packed, cout: int, spec: "BnBwdSpec", out=None, residual=None):
-    """conv2d_fwd_ex_bnbwd for the 3x3 / stride-1 data gradients on the Winograd route (u_packed: data-gradient packing)."""
-    n, h, w, cin = x.shape
-    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
-    if y.shape != spec.z.shape:
-        raise VatlError("conv3x3_winograd_fwd_bnbwd: the BatchNorm tensors must have the layout of the output")
-    used = C.c_int64(0)
-    c = spec.z.shape[-1]
-    need = int(lib().vatl_winograd_stats_row_blocks(n, h, w))
-    if (spec.blocks + need) * c * 2 > spec.stats.numel():
-        raise VatlError("conv3x3_winograd_fwd_bnbwd: statistics buffer too small")
-    stats_ptr = spec.stats.data_ptr() + spec.blocks * c * 2 * 8
-    _check(lib().vatl_conv3x3_winograd_fwd_bnbwd(_ptr(x), _ptr(u_packed), _ptr(residual), _ptr(y), n, h, w, cin, cout, _ptr(spec.z), _ptr(spec.mask_y),
-                                                 _ptr(spec.scale), _ptr(spec.bias), _ptr(spec.mean), _ptr(spec.invstd), stats_ptr, C.addressof(used),
-                                                 _stream()), "vatl_conv3x3_winograd_fwd_bnbwd")
-    spec.blocks += used.value
-    return y
-
-
-def deconv4x4s2_winograd_fwd_bnstats(x, u_packed, cout: int, gamma, beta, running_mean, running_var, momentum: float, eps: float):
-    """deconv4x4s2_fwd_bnstats on the Winograd route: -> z, save_mean, save_invstd, scale, bias; running stats updated in place."""
-    n, h, w, cin = x.shape
-    z = torch.empty((n, 2 * h, 2 * w, cout), device=x.device, dtype=torch.float32)
-    stats = torch.empty(int(lib().vatl_winograd_deconv_stats_row_blocks(n, h, w)) * cout * 2, device=x.device, dtype=torch.float64)
-    used = C.c_int64(0)
-    _check(lib().vatl_deconv4x4s2_winograd_fwd_stats(_ptr(x), _ptr(u_packed), _ptr(z), _ptr(stats, torch.float64), C.addressof(used), n, h, w, cin,
-                                                     cout, _stream()), "vatl_deconv4x4s2_winograd_fwd_stats")
-    return [z] + _bn_finalize(stats, used.value, z.numel() // cout, cout, (gamma, beta, running_mean, running_var, momentum, eps), x.device)
+    return _stats_fwd("vatl_conv3x3_winograd_fwd_stats", x, u_packed, (n, h, w, cout), lib().vatl_winograd_stats_row_blocks(n, h, w), (n, h, w, cin, cout))
 
 
 def conv3x3_winograd_fwd_bnstats(x, u_packed, cout: int, gamma, beta, running_mean, running_var, momentum: float, eps: float):
@@ -1283,58 +1106,18 @@ def conv3x3_winograd_fwd_bnstats(x, u_packed, cout: int, gamma, beta, running_me
     return [z] + _bn_finalize(stats, used, z.numel() // cout, cout, (gamma, beta, running_mean, running_var, momentum, eps), x.device)
 
 
-def deconv4x4s2_fwd_bnstats(x, w_packed, cout: int, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+def conv3x3_winograd_f4_fwd_bnstats(x, u, cout: int, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+    """conv3x3_winograd_fwd_bnstats on the F(4x4,3x3) route: -> z, save_mean, save_invstd, scale, bias; running stats updated in place."""
     n, h, w, cin = x.shape
-    z = torch.empty((n, 2 * h, 2 * w, cout), device=x.device, dtype=torch.float32)
-    stats = torch.empty(int(lib().vatl_conv_stats_row_blocks(n * h * w, 4)) * cout * 2, device=x.device, dtype=torch.float64)
-    used = C.c_int64(0)
-    _check(lib().vatl_deconv4x4s2_fwd_stats(_ptr(x), _ptr(w_packed), _ptr(z), _ptr(stats, torch.float64), C.addressof(used), n, h, w, cin, cout,
-                                            w_packed.shape[1], _stream()), "vatl_deconv4x4s2_fwd_stats")
-    return [z] + _bn_finalize(stats, used.value, 4 * n * h * w, cout, (gamma, beta, running_mean, running_var, momentum, eps), x.device)
+    return _stats_fwd("vatl_conv3x3_winograd_f4_fwd_stats", x, u, (n, h, w, cout), lib().vatl_winograd_f4_stats_row_blocks(n, h, w), (n, h, w, cin, cout),
+                      (gamma, beta, running_mean, running_var, momentum, eps))
 
 
-def bn_train_bwd_relu(dy, scale, bias, z, gamma, save_mean, save_invstd, dgamma=None, dbeta=None):
-    """Backward of Conv+BN+ReLU without a skip input; the ReLU mask is recomputed from z. -> dz, dgamma, dbeta."""
-    c = z.shape[-1]
-    m = z.numel() // c
-    dz = torch.empty_like(z)
-    dgamma = dgamma if dgamma is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    dbeta = dbeta if dbeta is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    coef = torch.empty(3 * c, device=z.device, dtype=torch.float32)
-    _check(lib().vatl_bn_train_bwd_relu(_ptr(dy), _ptr(scale), _ptr(bias), _ptr(z), _ptr(gamma), _ptr(save_mean), _ptr(save_invstd), _ptr(dz),
-                                        _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _ptr(_col_ws(m, c, z.device), torch.float64), _stream()),
-           "vatl_bn_train_bwd_relu")
-    return dz, dgamma, dbeta
-
-
-def scale_bias_act(z, scale, bias, residual=None, relu=True):
-    c = z.shape[-1]
-    y = torch.empty_like(z)
-    _check(lib().vatl_scale_bias_act(_ptr(z), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), z.numel() // c, c, int(relu), _stream()),
-           "vatl_scale_bias_act")
-    return y
-
-
-def bn_train_bwd(dy, y, z, gamma, save_mean, save_invstd, want_g: bool = False, dgamma=None, dbeta=None):
-    """-> dz, g (or None), dgamma, dbeta."""
-    c = z.shape[-1]
-    m = z.numel() // c
-    dz = torch.empty_like(z)
-    g = torch.empty_like(z) if want_g else None
-    dgamma = dgamma if dgamma is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    dbeta = dbeta if dbeta is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    coef = torch.empty(3 * c, device=z.device, dtype=torch.float32)
-    _check(lib().vatl_bn_train_bwd(_ptr(dy), _ptr(y), _ptr(z), _ptr(gamma), _ptr(save_mean), _ptr(save_invstd), _ptr(dz), _ptr(g),
-                                   _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _ptr(_col_ws(m, c, z.device), torch.float64), _stream()),
-           "vatl_bn_train_bwd")
-    return dz, g, dgamma, dbeta
-
-
-def maxpool3x3s2_bwd(x, dy):
-    n, h, w, c = x.shape
-    dx = torch.empty_like(x)
-    _check(lib().vatl_maxpool3x3s2_bwd(_ptr(x), _ptr(dy), _ptr(dx), n, h, w, c, _stream()), "vatl_maxpool3x3s2_bwd")
-    return dx
+def deconv4x4s2_winograd_fwd_bnstats(x, u_packed, cout: int, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+    """deconv4x4s2_fwd_bnstats on the Winograd route: -> z, save_mean, save_invstd, scale, bias; running stats updated in place."""
+    n, h, w, cin = x.shape
+    return _stats_fwd("vatl_deconv4x4s2_winograd_fwd_stats", x, u_packed, (n, 2 * h, 2 * w, cout), lib().vatl_winograd_deconv_stats_row_blocks(n, h, w),
+                      (n, h, w, cin, cout), (gamma, beta, running_mean, running_var, momentum, eps))
 
 
 def maxpool3x3s2_fwd_idx(x):
@@ -1355,18 +1138,208 @@ def maxpool3x3s2_fwd_idx_affine(z, scale, bias):
     return y, idx
 
 
+# ----------------------------------------------------------------------------
+# training-mode backbone ops: data gradients with the BatchNorm-backward epilogue
+# ----------------------------------------------------------------------------
+
+class BnBwdSpec:
+    """What a data-gradient launch needs to run the reduction pass of the consumer layer's BatchNorm backward in its
+    epilogue: z (the consumer's conv output), its ReLU mask source (mask_y, or (scale, bias) to recompute it from z, or
+    neither) and the saved batch statistics.  ``stats`` / ``blocks`` collect the partial sums of one or more launches."""
+
+    def __init__(self, z, mean, invstd, mask_y=None, scale=None, bias=None):
+        self.z, self.mean, self.invstd, self.mask_y, self.scale, self.bias = z, mean, invstd, mask_y, scale, bias
+        c = z.shape[-1]
+        cap = int(lib().vatl_conv_stats_row_blocks(z.numel() // c, 1)) + 8     # + a partial tile per parity launch
+        self.stats = torch.empty(cap * c * 2, device=z.device, dtype=torch.float64)
+        self.blocks = 0
+
+    def window(self, need: int, who: str) -> int:
+        """Address of the free tail of ``stats`` for a launch of ``who`` that may write ``need`` more row blocks (2 doubles per
+        channel each) — raises when they do not fit: this is the only guard in front of that launch's device writes."""
+        c = self.z.shape[-1]
+        if (self.blocks + need) * c * 2 > self.stats.numel():
+            raise VatlError(f"{who}: statistics buffer too small")
+        return self.stats.data_ptr() + self.blocks * c * 2 * 8
+
+    def advance(self, used: C.c_int64):
+        """The launch that was given ``window()`` wrote this many row blocks."""
+        self.blocks += used.value
+
+
+def _bnbwd_tail(spec: BnBwdSpec, y, need: int, who: str):
+    """-> (used, the eight trailing arguments of a *_bnbwd entry point before the stream: z, mask_y, scale, bias, mean, invstd, the
+    statistics window, &used) for a launch of ``who`` that writes ``y`` and at most ``need`` row blocks of partials."""
+    if y.shape != spec.z.shape:
+        raise VatlError(f"{who}: the BatchNorm tensors must have the layout of the output")
+    used = C.c_int64(0)
+    return used, (_ptr(spec.z), _ptr(spec.mask_y), _ptr(spec.scale), _ptr(spec.bias), _ptr(spec.mean), _ptr(spec.invstd),
+                  spec.window(need, who), C.addressof(used))
+
+
+def conv2d_fwd_ex_bnbwd(x, w_packed, cout, r, s, stride, pad_y, pad_x, ho, wo, oh, ow, osy, osx, ooy, oox, spec: BnBwdSpec, out=None, residual=None):
+    """conv2d_fwd_ex whose epilogue masks the result with the consumer layer's ReLU and appends the (sum g, sum g*xhat) row-block
+    partials to ``spec`` (several launches — the parity launches of a strided conv's data gradient — append one after another)."""
+    n, h, w, cin = x.shape
+    y = out if out is not None else torch.empty((n, oh, ow, cout), device=x.device, dtype=torch.float32)
+    used, tail = _bnbwd_tail(spec, y, int(lib().vatl_conv_stats_row_blocks(n * ho * wo, 1)), "conv2d_fwd_ex_bnbwd")
+    _check(lib().vatl_conv2d_fwd_ex_bnbwd(_ptr(x), _ptr(w_packed), _ptr(residual), _ptr(y), n, h, w, cin, cout, w_packed.shape[0], r, s, stride, pad_y,
+                                          pad_x, ho, wo, oh, ow, osy, osx, ooy, oox, *tail, _stream()), "vatl_conv2d_fwd_ex_bnbwd")
+    spec.advance(used)
+    return y
+
+
+def conv3x3_winograd_fwd_bnbwd(x, u_packed, cout: int, spec: "BnBwdSpec", out=None, residual=None):
+    """conv2d_fwd_ex_bnbwd for the 3x3 / stride-1 data gradients on the Winograd route (u_packed: data-gradient packing)."""
+    n, h, w, cin = x.shape
+    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
+    used, tail = _bnbwd_tail(spec, y, int(lib().vatl_winograd_stats_row_blocks(n, h, w)), "conv3x3_winograd_fwd_bnbwd")
+    _check(lib().vatl_conv3x3_winograd_fwd_bnbwd(_ptr(x), _ptr(u_packed), _ptr(residual), _ptr(y), n, h, w, cin, cout, *tail, _stream()),
+           "vatl_conv3x3_winograd_fwd_bnbwd")
+    spec.advance(used)
+    return y
+
+
+def conv3x3_winograd_f4_fwd_bnbwd(x, u, cout: int, spec: "BnBwdSpec", out=None, residual=None):
+    """conv3x3_winograd_fwd_bnbwd on the F(4x4,3x3) route (u: data-gradient packing)."""
+    n, h, w, cin = x.shape
+    y = out if out is not None else torch.empty((n, h, w, cout), device=x.device, dtype=torch.float32)
+    used, tail = _bnbwd_tail(spec, y, int(lib().vatl_winograd_f4_stats_row_blocks(n, h, w)), "conv3x3_winograd_f4_fwd_bnbwd")
+    _check(lib().vatl_conv3x3_winograd_f4_fwd_bnbwd(_ptr(x), _ptr(u), _ptr(residual), _ptr(y), n, h, w, cin, cout, *tail, _stream()),
+           "vatl_conv3x3_winograd_f4_fwd_bnbwd")
+    spec.advance(used)
+    return y
+
+
+def deconv4x4s2_winograd_dgrad(dz, u_packed, cin: int, spec: "BnBwdSpec" = None, residual=None, out=None):
+    """dx (N,H,W,Cin) of ConvTranspose2d(4,2,1) from dz (N,2H,2W,Cout); with ``spec`` the epilogue masks the result with the consumer
+    layer's ReLU and appends the (sum g, sum g*xhat) row-block partials (conv2d_fwd_ex_bnbwd semantics)."""
+    n, h2, w2, cout = dz.shape
+    h, w = h2 // 2, w2 // 2
+    dx = out if out is not None else torch.empty((n, h, w, cin), device=dz.device, dtype=torch.float32)
+    if spec is None:
+        _check(lib().vatl_deconv4x4s2_winograd_dgrad(_ptr(dz), _ptr(u_packed), _ptr(residual), _ptr(dx), n, h, w, cin, cout, _stream()),
+               "vatl_deconv4x4s2_winograd_dgrad")
+        return dx
+    # one grid of F(3x3,2x2) tiles over (N,H,W): the transposed conv's forward statistics count four phases of exactly this grid
+    used, tail = _bnbwd_tail(spec, dx, int(lib().vatl_winograd_deconv_stats_row_blocks(n, h, w)) // 4, "deconv4x4s2_winograd_dgrad")
+    _check(lib().vatl_deconv4x4s2_winograd_dgrad_bnbwd(_ptr(dz), _ptr(u_packed), _ptr(residual), _ptr(dx), n, h, w, cin, cout, *tail, _stream()),
+           "vatl_deconv4x4s2_winograd_dgrad_bnbwd")
+    spec.advance(used)
+    return dx
+
+
+# ----------------------------------------------------------------------------
+# training-mode backbone ops: weight gradients
+# ----------------------------------------------------------------------------
+
+def _grad_out(who: str, out, shape, ws_floats: int, device):
+    """-> (dw, workspace) of a weight-gradient launch: ``out`` (a slice of the flat gradient arena; any shape with the right element
+    count) or a fresh tensor of ``shape``, and the launch's float workspace."""
+    dw = out if out is not None else torch.empty(shape, device=device, dtype=torch.float32)
+    if dw.numel() != shape[0] * shape[1] * shape[2] * shape[3]:
+        raise VatlError(f"{who}: out has the wrong size")
+    return dw, torch.empty(int(ws_floats), device=device, dtype=torch.float32)
+
+
+def conv2d_wgrad(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: int, out=None) -> torch.Tensor:
+    """x NHWC (N,H,W,Cin or 4 for the stem), dz NHWC (N,Ho,Wo,CoutG) -> dw (Cout,Cin,R,S) (written into ``out`` when
+    given: a slice of the flat gradient arena)."""
+    n, h, w, _ = x.shape
+    m = n * dz.shape[1] * dz.shape[2]
+    dw, ws = _grad_out("conv2d_wgrad", out, (cout, cin, r, s), lib().vatl_conv2d_wgrad_workspace_floats(cout, cin, r, s, m), x.device)
+    _check(lib().vatl_conv2d_wgrad(_ptr(x), _ptr(dz), _ptr(dw), _ptr(ws), n, h, w, cin, cout, dz.shape[3], r, s, stride, pad, _stream()),
+           "vatl_conv2d_wgrad")
+    return dw
+
+
+def conv3x3_winograd_wgrad(x, dz, out=None) -> torch.Tensor:
+    """Weight gradient of a 3x3 / stride 1 / pad 1 conv on the Winograd route: x (N,H,W,Cin), dz (N,H,W,Cout) -> dw (Cout,Cin,3,3)."""
+    n, h, w, cin = x.shape
+    cout = dz.shape[3]
+    dw, ws = _grad_out("conv3x3_winograd_wgrad", out, (cout, cin, 3, 3), lib().vatl_conv3x3_winograd_wgrad_workspace_floats(cout, cin, n, h, w), x.device)
+    _check(lib().vatl_conv3x3_winograd_wgrad(_ptr(x), _ptr(dz), _ptr(dw), _ptr(ws), n, h, w, cin, cout, _stream()), "vatl_conv3x3_winograd_wgrad")
+    return dw
+
+
+def deconv4x4s2_winograd_wgrad(x, dy, out=None) -> torch.Tensor:
+    """Weight gradient of ConvTranspose2d(4,2,1) on the Winograd route: x (N,H,W,Cin), dy (N,2H,2W,Cout) -> dw (Cin,Cout,4,4)."""
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    dw, ws = _grad_out("deconv4x4s2_winograd_wgrad", out, (cin, cout, 4, 4), lib().vatl_deconv4x4s2_winograd_wgrad_workspace_floats(cin, cout, n, h, w), x.device)
+    _check(lib().vatl_deconv4x4s2_winograd_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), n, h, w, cin, cout, _stream()), "vatl_deconv4x4s2_winograd_wgrad")
+    return dw
+
+
+def deconv4x4s2_wgrad(x, dy, out=None) -> torch.Tensor:
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    dw, ws = _grad_out("deconv4x4s2_wgrad", out, (cin, cout, 4, 4), lib().vatl_deconv4x4s2_wgrad_workspace_floats(cin, cout, n * h * w), x.device)
+    _check(lib().vatl_deconv4x4s2_wgrad(_ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), n, h, w, cin, cout, _stream()), "vatl_deconv4x4s2_wgrad")
+    return dw
+
+
+# ----------------------------------------------------------------------------
+# training-mode backbone ops: BatchNorm and element-wise backward passes
+# ----------------------------------------------------------------------------
+
+def _bn_bwd_outs(z, dgamma, dbeta):
+    """-> dz, dgamma, dbeta (the given arena slices, or fresh), and the kernels' 3C coefficient scratch."""
+    c = z.shape[-1]
+    return (torch.empty_like(z), dgamma if dgamma is not None else torch.empty(c, device=z.device, dtype=torch.float32),
+            dbeta if dbeta is not None else torch.empty(c, device=z.device, dtype=torch.float32), torch.empty(3 * c, device=z.device, dtype=torch.float32))
+
+
+def bn_bwd_from_stats(spec: BnBwdSpec, g, gamma, dgamma=None, dbeta=None):
+    """Finish the BatchNorm backward whose reduction ran in the data-gradient epilogue: -> dz, dgamma, dbeta."""
+    z = spec.z
+    c = z.shape[-1]
+    m = z.numel() // c
+    dz, dgamma, dbeta, coef = _bn_bwd_outs(z, dgamma, dbeta)
+    _check(lib().vatl_bn_bwd_from_stats(_ptr(spec.stats, torch.float64), spec.blocks, _ptr(g), _ptr(z), _ptr(gamma), _ptr(spec.mean), _ptr(spec.invstd),
+                                        _ptr(dz), _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _stream()), "vatl_bn_bwd_from_stats")
+    return dz, dgamma, dbeta
+
+
+def bn_train_bwd_relu(dy, scale, bias, z, gamma, save_mean, save_invstd, dgamma=None, dbeta=None):
+    """Backward of Conv+BN+ReLU without a skip input; the ReLU mask is recomputed from z. -> dz, dgamma, dbeta."""
+    c = z.shape[-1]
+    m = z.numel() // c
+    dz, dgamma, dbeta, coef = _bn_bwd_outs(z, dgamma, dbeta)
+    _check(lib().vatl_bn_train_bwd_relu(_ptr(dy), _ptr(scale), _ptr(bias), _ptr(z), _ptr(gamma), _ptr(save_mean), _ptr(save_invstd), _ptr(dz),
+                                        _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _ptr(_col_ws(m, c, z.device), torch.float64), _stream()),
+           "vatl_bn_train_bwd_relu")
+    return dz, dgamma, dbeta
+
+
+def bn_train_bwd(dy, y, z, gamma, save_mean, save_invstd, want_g: bool = False, dgamma=None, dbeta=None):
+    """-> dz, g (or None), dgamma, dbeta."""
+    c = z.shape[-1]
+    m = z.numel() // c
+    dz, dgamma, dbeta, coef = _bn_bwd_outs(z, dgamma, dbeta)
+    g = torch.empty_like(z) if want_g else None
+    _check(lib().vatl_bn_train_bwd(_ptr(dy), _ptr(y), _ptr(z), _ptr(gamma), _ptr(save_mean), _ptr(save_invstd), _ptr(dz), _ptr(g),
+                                   _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _ptr(_col_ws(m, c, z.device), torch.float64), _stream()),
+           "vatl_bn_train_bwd")
+    return dz, g, dgamma, dbeta
+
+
 def bn_train_bwd_relu_pool(dpool, idx, scale, bias, z, gamma, save_mean, save_invstd, dgamma=None, dbeta=None):
     """Backward of Conv+BN+ReLU+MaxPool(3,2,1) from the POOLED output's gradient (the full-resolution gradient is gathered on
     the fly, never stored). -> dz, dgamma, dbeta."""
     n, h, w, c = z.shape
-    dz = torch.empty_like(z)
-    dgamma = dgamma if dgamma is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    dbeta = dbeta if dbeta is not None else torch.empty(c, device=z.device, dtype=torch.float32)
-    coef = torch.empty(3 * c, device=z.device, dtype=torch.float32)
+    dz, dgamma, dbeta, coef = _bn_bwd_outs(z, dgamma, dbeta)
     _check(lib().vatl_bn_train_bwd_relu_pool(_ptr(dpool), _ptr(idx, torch.uint8), _ptr(scale), _ptr(bias), _ptr(z), _ptr(gamma), _ptr(save_mean),
                                              _ptr(save_invstd), _ptr(dz), _ptr(dgamma), _ptr(dbeta), n, h, w, c, _ptr(coef),
                                              _ptr(_col_ws(n * h * w, c, z.device), torch.float64), _stream()), "vatl_bn_train_bwd_relu_pool")
     return dz, dgamma, dbeta
+
+
+def maxpool3x3s2_bwd(x, dy):
+    n, h, w, c = x.shape
+    dx = torch.empty_like(x)
+    _check(lib().vatl_maxpool3x3s2_bwd(_ptr(x), _ptr(dy), _ptr(dx), n, h, w, c, _stream()), "vatl_maxpool3x3s2_bwd")
+    return dx
 
 
 def maxpool3x3s2_bwd_idx(dy, idx, in_hw):
@@ -1381,6 +1354,21 @@ def pixelunshuffle2(x):
     y = torch.empty((n, h2 // 2, w2 // 2, c4 * 4), device=x.device, dtype=torch.float32)
     _check(lib().vatl_pixelunshuffle2(_ptr(x), _ptr(y), n, h2 // 2, w2 // 2, c4 * 4, _stream()), "vatl_pixelunshuffle2")
     return y
+
+
+def upsample_nearest_bwd(dy, yact, shift: int):
+    """dy (N,H,W,C) [masked by yact > 0] -> block sums (N,H>>shift,W>>shift,C)."""
+    n, h, w, c = dy.shape
+    dz = torch.empty((n, h >> shift, w >> shift, c), device=dy.device, dtype=torch.float32)
+    _check(lib().vatl_upsample_nearest_bwd(_ptr(dy), _ptr(yact), _ptr(dz), n, h, w, c, shift, _stream()), "vatl_upsample_nearest_bwd")
+    return dz
+
+
+def gap_bwd(dy, hw: int):
+    n, c = dy.shape
+    dx = torch.empty((n, hw, c), device=dy.device, dtype=torch.float32)
+    _check(lib().vatl_gap_bwd(_ptr(dy), _ptr(dx), n, hw, c, _stream()), "vatl_gap_bwd")
+    return dx
 
 
 def se_bwd_gate(dy, y, u, gate):
