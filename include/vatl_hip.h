@@ -525,6 +525,24 @@ int vatl_crop_warp_affine(const uint8_t* arena, const int64_t* src_off, const in
 int vatl_ae_train_step(float* ae, float* m, float* v, const float* feat, int B, int D, int z, double lr, double beta1, double beta2,
                        double eps, int step, float* loss_or_null, void* stream);
 
+/* The same network at pre-training batch sizes (scripts/wholebodyAE_train.py:110-184: 10 000 rows a step), any N >= 1, D and z in
+ * 1..64.  Both calls are two launches (block partials, then a finish) without host synchronisation and without floating-point
+ * atomics: every block sums a contiguous range of items in item order, the finish adds the block partials in block order in
+ * double.  The item ranges are a function of N alone, so a call gives the same bits on every device and every run.  Activations
+ * are recomputed with vatl_ae_forward's operation order (the ReLU masks are the forward pass's).
+ * workspace: vatl_ae_grad_workspace_floats(N, D, z) floats (host-only query; 0 for arguments out of range). */
+int64_t vatl_ae_grad_workspace_floats(int N, int D, int z);
+/* loss.backward() through the auto-encoder: feat (N,D) the input of the forward pass, dy (N,D) the gradient w.r.t. its output
+ * -> grad (P floats, packed like ae: W0,b0,...,W7,b7) and, when dx_or_null is given, the gradient w.r.t. feat (N,D). */
+int vatl_ae_backward(const float* feat, const float* dy, const float* ae, int D, int z, int N, float* grad, float* dx_or_null,
+                     float* workspace, void* stream);
+/* One whole training step on feat (N,D): forward, MSELoss(output, input), backward and the optimiser update of ae / m / v in place.
+ * decoupled = 1: torch.optim.AdamW (the pre-training script, weight_decay 0.01); decoupled = 0: torch.optim.Adam (weight_decay is
+ * an L2 term; retrain_AE passes 0).  `step` is the 1-based step count; loss (1 float, before the update) may be NULL. */
+int vatl_ae_train_step_large(float* ae, float* m, float* v, const float* feat, int N, int D, int z, double lr, double beta1,
+                             double beta2, double eps, double weight_decay, int step, int decoupled, float* loss_or_null,
+                             float* workspace, void* stream);
+
 /* torch.optim.AdamW step on one flat fp32 span (decoupled weight decay);
  * hyper-parameters are doubles like the Python floats torch derives its
  * per-step scalars from; `step` is the 1-based step count. */

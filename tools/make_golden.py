@@ -263,6 +263,93 @@ def gen_scorers(ref: str, out: str):
     print("scorers.npz written")
 
 
+# ----------------------------------------------------------------------------
+# Wholebody pre-training data set (Whole_body_AE/Whole_body_hybrid.py)
+# ----------------------------------------------------------------------------
+
+WHOLEBODY_SEED = 3180
+WHOLEBODY_TYPES = {"Posetrack21": ("PoseTrack21", 2), "JRDB2022": ("jrdb-pose", 3)}     # type -> (annotation folder under data/, id digits kept)
+
+
+def wholebody_annotations(dataset_type: str, n: int = 40):
+    """Seeded synthetic people: `id`, `image_id`, `bbox` (x, y, w, h), `keypoints` (x, y, score) * 17.  Every fifth person has no visible
+    key-point (skipped by the data set), the ids are not in ann_id order, and people 3 and 7 share the id digits the ann_id keeps."""
+    r = np.random.RandomState(WHOLEBODY_SEED + len(dataset_type))
+    digits = WHOLEBODY_TYPES[dataset_type][1]
+    ids = r.permutation(10 ** digits)[:n] + 10 ** digits * r.randint(1, 50, n)
+    ids[7] = ids[3] + 10 ** digits                                   # same trailing digits, another person
+    ids[n - 2] = ids[n - 2] // 10 ** digits * 10 ** digits + 10 ** digits - 3       # the last kept person is not the first in ann_id order
+    image_ids = r.permutation(n) * 7 + (10005830000 if dataset_type == "Posetrack21" else 1200)
+    anns = []
+    for k in range(n):
+        x, y, w, h = r.uniform(50, 900), r.uniform(50, 500), r.uniform(40, 200), r.uniform(120, 400)
+        kp = np.zeros((17, 3))
+        kp[:, 0] = np.round(x + r.uniform(0, 1, 17) * w, 2)
+        kp[:, 1] = np.round(y + r.uniform(0, 1, 17) * h, 2)
+        kp[:, 2] = 0.0 if k % 5 == 4 else (r.uniform(0, 1, 17) > 0.25).astype(np.float64)
+        if k % 5 != 4:
+            kp[r.randint(17), 2] = 1.0
+        anns.append({"id": int(ids[k]), "image_id": int(image_ids[k]), "bbox": [round(x, 2), round(y, 2), round(w, 2), round(h, 2)],
+                     "keypoints": kp.reshape(-1).tolist()})
+    return anns
+
+
+def gen_wholebody(ref: str, out: str):
+    """The reference's Wholebody class and compute_hybrid on a seeded annotation list, for both dataset types.  The class is run in a
+    temporary working directory (it reads and caches under ./data); through its aliased item dict every element it returns is the
+    LAST kept annotation, which `ref_item0_is_last_kept` records."""
+    import contextlib
+    import io
+    import json
+    import tempfile
+    try:
+        import tqdm  # noqa: F401  (imported by the reference module's self-test block)
+    except ImportError:
+        sys.modules["tqdm"] = types.ModuleType("tqdm")
+    pkg = types.ModuleType("active_learning"); pkg.__path__ = [os.path.join(ref, "active_learning")]
+    sub = types.ModuleType("active_learning.Whole_body_AE"); sub.__path__ = [os.path.join(ref, "active_learning", "Whole_body_AE")]
+    sys.modules["active_learning"] = pkg
+    sys.modules["active_learning.Whole_body_AE"] = sub
+    hf = load_by_path("active_learning.Whole_body_AE.hybrid_feature", os.path.join(ref, "active_learning/Whole_body_AE/hybrid_feature.py"))
+    wb = load_by_path("active_learning.Whole_body_AE.Whole_body_hybrid", os.path.join(ref, "active_learning/Whole_body_AE/Whole_body_hybrid.py"))
+    res = {"seed": np.int64(WHOLEBODY_SEED)}
+    cwd = os.getcwd()
+    for dtype, (folder, _) in WHOLEBODY_TYPES.items():
+        anns = wholebody_annotations(dtype)
+        kept = [a for a in anns if sum(a["keypoints"][2::3]) != 0]
+        hyb = np.full((len(anns), 42), np.nan)
+        for k, a in enumerate(anns):
+            if sum(a["keypoints"][2::3]) != 0:
+                hyb[k] = hf.compute_hybrid(a["bbox"], np.array(a["keypoints"]))
+        res[f"{dtype}_id"] = np.array([a["id"] for a in anns], np.int64)
+        res[f"{dtype}_image_id"] = np.array([a["image_id"] for a in anns], np.int64)
+        res[f"{dtype}_bbox"] = np.array([a["bbox"] for a in anns], np.float64)
+        res[f"{dtype}_keypoints"] = np.array([a["keypoints"] for a in anns], np.float64)
+        res[f"{dtype}_hybrid"] = hyb
+        name = "000000_integrated_train.json" if dtype == "Posetrack21" else "integrated_train.json"
+        for kp_direct, tag in ((True, "direct"), (False, "hybrid")):
+            with tempfile.TemporaryDirectory() as td:
+                os.makedirs(os.path.join(td, "data", folder, "activelearning", "train"))
+                with open(os.path.join(td, "data", folder, "activelearning", "train", name), "w") as f:
+                    json.dump({"annotations": anns}, f)
+                os.chdir(td)
+                try:
+                    with contextlib.redirect_stdout(io.StringIO()):
+                        ds = wb.Wholebody(mode="train", kp_direct=kp_direct, dataset_type=dtype)
+                        item0 = ds[0].numpy()
+                    cache_type = "PoseTrack21" if dtype == "Posetrack21" else dtype
+                    assert os.path.isfile(os.path.join("data", cache_type, "activelearning", "hybrid_feature", "train", name + ".npy"))
+                finally:
+                    os.chdir(cwd)
+            res[f"{dtype}_ref_len"] = np.int64(len(ds))
+            res[f"{dtype}_ref_item0_{tag}"] = item0
+        last = kept[-1]
+        res[f"{dtype}_ref_item0_is_last_kept"] = np.bool_(np.array_equal(res[f"{dtype}_ref_item0_direct"], np.array(last["keypoints"], np.float32)))
+        assert res[f"{dtype}_ref_item0_is_last_kept"] and int(res[f"{dtype}_ref_len"]) == len(kept)
+        print("wholebody", dtype, len(anns), "people,", len(kept), "kept")
+    np.savez_compressed(os.path.join(out, "wholebody.npz"), **res)
+
+
 def _extract_methods(path: str, names):
     """Compile selected ``def``s of class ActiveLearning out of the reference file
     *in memory* (the class itself cannot be imported here: skimage/seaborn/umap/...
@@ -867,6 +954,8 @@ def main():
         gen_fastpose_r152(EasyDict, a.out)
     if a.only in ("", "widepin"):
         gen_widepin(EasyDict, a.out)
+    if a.only in ("", "wholebody"):
+        gen_wholebody(a.ref, a.out)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,4 @@
+from .AutoEncoder import WholeBodyAE
+from .Whole_body_hybrid import Wholebody
+
+__all__ = ["WholeBodyAE", "Wholebody"]

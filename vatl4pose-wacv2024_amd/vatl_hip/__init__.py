@@ -144,6 +144,9 @@ SIGNATURES = {
     "vatl_gaussian_targets": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "vatl_crop_warp_affine": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _p]),
     "vatl_ae_train_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _d, _i, _p, _p]),
+    "vatl_ae_grad_workspace_floats": (_i64, [_i, _i, _i]),
+    "vatl_ae_backward": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "vatl_ae_train_step_large": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _d, _d, _i, _i, _p, _p, _p]),
     "vatl_adamw_step": (_i, [_p, _p, _p, _p, _i64, _d, _d, _d, _d, _d, _i, _p]),
     "vatl_oks": (_i, [_p, _p, _p, _p, _i, _p]),
     "vatl_cosine_rowsum": (_i, [_p, _i64, _i, _p, _p, _p]),
@@ -956,10 +959,10 @@ def pack_ae(state_dict, device) -> torch.Tensor:
     return torch.cat([p.to(device) for p in parts]).contiguous()
 
 
-def ae_forward(feat: torch.Tensor, ae_flat: torch.Tensor, d: int, z: int):
-    """feat (N,D) -> recon (N,D), mse (N,)."""
+def ae_forward(feat: torch.Tensor, ae_flat: torch.Tensor, d: int, z: int, want_recon: bool = True):
+    """feat (N,D) -> recon (N,D) (None without ``want_recon``), mse (N,)."""
     n = feat.shape[0]
-    recon = torch.empty((n, d), device=feat.device, dtype=torch.float32)
+    recon = torch.empty((n, d), device=feat.device, dtype=torch.float32) if want_recon else None
     mse = torch.empty(n, device=feat.device, dtype=torch.float32)
     _check(lib().vatl_ae_forward(_ptr(feat), _ptr(ae_flat), d, z, _ptr(recon), _ptr(mse), n, _stream()), "vatl_ae_forward")
     return recon, mse
@@ -1466,6 +1469,37 @@ def ae_train_step(ae_flat, m, v, feat, d: int, z: int, step: int, lr: float, bet
     loss = torch.empty((), device=feat.device, dtype=torch.float32)
     _check(lib().vatl_ae_train_step(_ptr(ae_flat), _ptr(m), _ptr(v), _ptr(feat), feat.shape[0], d, z, lr, betas[0], betas[1], eps, step,
                                     _ptr(loss), _stream()), "vatl_ae_train_step")
+    return loss
+
+
+def ae_grad_workspace(n: int, d: int, z: int, device) -> torch.Tensor:
+    """Block-partial workspace of ``ae_backward`` / ``ae_train_step_large`` for a batch of ``n`` rows (reusable across calls of that shape)."""
+    floats = int(lib().vatl_ae_grad_workspace_floats(n, d, z))
+    if floats <= 0:
+        raise VatlError(f"auto-encoder batch {n} x {d} (z = {z}) is out of range: N >= 1, widths in 1..64")
+    return torch.empty(floats, device=device, dtype=torch.float32)
+
+
+def ae_backward(feat, dy, ae_flat, d: int, z: int, need_dx: bool = False, workspace=None):
+    """Gradients of the packed WholeBodyAE for upstream gradients dy (N, d) at the input feat (N, d): (grad (P,), dx (N, d) or None)."""
+    n = feat.shape[0]
+    ws = workspace if workspace is not None else ae_grad_workspace(n, d, z, feat.device)
+    grad = torch.empty_like(ae_flat)
+    dx = torch.empty((n, d), device=feat.device, dtype=torch.float32) if need_dx else None
+    _check(lib().vatl_ae_backward(_ptr(feat), _ptr(dy), _ptr(ae_flat), d, z, n, _ptr(grad), _ptr(dx), _ptr(ws), _stream()), "vatl_ae_backward")
+    return grad, dx
+
+
+def ae_train_step_large(ae_flat, m, v, feat, d: int, z: int, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                        weight_decay: float = 0.01, decoupled: bool = True, workspace=None, loss=None):
+    """One AdamW (``decoupled``) or Adam step of the packed WholeBodyAE on feat (N, d), any N; returns the loss (0-dim tensor, or ``loss``
+    when the caller gives a 1-element tensor to write into)."""
+    n = feat.shape[0]
+    ws = workspace if workspace is not None else ae_grad_workspace(n, d, z, feat.device)
+    if loss is None:
+        loss = torch.empty((), device=feat.device, dtype=torch.float32)
+    _check(lib().vatl_ae_train_step_large(_ptr(ae_flat), _ptr(m), _ptr(v), _ptr(feat), n, d, z, lr, betas[0], betas[1], eps, weight_decay, step,
+                                          int(bool(decoupled)), _ptr(loss), _ptr(ws), _stream()), "vatl_ae_train_step_large")
     return loss
 
 
