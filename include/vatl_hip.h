@@ -590,6 +590,36 @@ int vatl_kcenter_update(const float* emb, int64_t n, int D, const int32_t* cente
 int vatl_kcenter_pick(const double* min_dist_or_null, double* unc_or_null, double a, double b, int32_t* selected_dev, int step,
                       int64_t n, void* stream);
 
+/* K-Means / weighted filters (ActiveLearning.py:553-582, 593-611): scikit-learn's KMeans(n_clusters=k, random_state=318) — k-means++
+ * seeding, one Lloyd run, float64 — restated on the device (csrc/kmeans.hip).  The host owns the stop rule and the random draws
+ * (they depend on the seed, n, k and the weights only); every entry point works in caller-provided memory and sums in a fixed order.
+ *   prepare  emb (n, D) fp32 -> xc (n, D) centred float64, mean (D), tol[0] = mean(var(xc, axis=0)) * 1e-4.  workspace: D doubles.
+ *   seed     k-means++ on xc: first centre first_index, then per centre `trials` candidates from rand_dev ((k-1) * trials uniform
+ *            draws) by searchsorted on the prefix sums of weight * closest distance; the candidate with the smallest potential is
+ *            adopted.  2k launches, no host round trip.  indices_dev (k).  tie_flag_dev[0] (zeroed by the caller) becomes 1 when a
+ *            candidate with another index came within 1e-9 relative of a winner's potential (or the winner's was 0): scikit-learn's
+ *            choice is then decided by its rounding.  Not flagged: a draw within rounding (~1e-13 relative) of a prefix-sum entry,
+ *            where searchsorted's side is decided by the summation order (about 1e-13 per draw).  trials <= 16; workspace: vatl_kmeans_seed_workspace_doubles(n, trials).
+ *   assign   labels[i] = first arg-min_j |c_j|^2 - 2 x_i.c_j on v_mfma_f64_16x16x4_f64; D % 16 == 0.  status[0] = 1.0 when a label
+ *            differs from labels_prev_or_null (NULL: always), else 0.0; status[2] = 0.0.  workspace: k doubles.
+ *   update   centers_new[j] = weighted mean of cluster j's members (a cluster without weight keeps its centre and sets
+ *            status[2] = 1.0); status[1] = sum |centers_new - centers|^2.  workspace: vatl_kmeans_update_workspace_doubles(D, k).
+ *   finish   representatives[j] = the member of cluster j with the smallest |emb_i - (c_j + mean)|^2 (lowest index among members
+ *            within 1e-9 relative of it; -1: no member); inertia[0] = sum_i w_i |xc_i - c_label(i)|^2.  workspace: 2n doubles.
+ * All: 1 <= k <= n. */
+int vatl_kmeans_prepare(const float* emb, int64_t n, int D, double* xc, double* mean, double* tol, double* workspace, void* stream);
+int64_t vatl_kmeans_seed_workspace_doubles(int64_t n, int trials);
+int vatl_kmeans_seed(const double* xc, const double* weight, int64_t n, int D, int k, int first_index, const double* rand_dev, int trials,
+                     int32_t* indices_dev, int32_t* tie_flag_dev, double* workspace, void* stream);
+int vatl_kmeans_assign(const double* xc, const double* centers, int64_t n, int D, int k, const int32_t* labels_prev_or_null, int32_t* labels,
+                       double* status, double* workspace, void* stream);
+int64_t vatl_kmeans_update_workspace_doubles(int D, int k);
+int vatl_kmeans_update(const double* xc, const double* weight, const int32_t* labels, const double* centers, int64_t n, int D, int k,
+                       double* centers_new, double* status, double* workspace, void* stream);
+int vatl_kmeans_finish(const float* emb, const double* xc, const double* mean, const double* weight, const double* centers,
+                       const int32_t* labels, int64_t n, int D, int k, int32_t* representatives, double* inertia, double* workspace,
+                       void* stream);
+
 /* ---- Winograd F(2x2, 3x3) route of the 3x3 / stride 1 / pad 1 layers (csrc/conv_winograd.hip) ------------------------------------
  * Replaces, for those layers, what the reference runs as torch.nn.Conv2d(k=3, s=1, p=1) inside Bottleneck / BasicBlock
  * (alphapose/models/layers/Resnet.py:52-78 conv2, alphapose/models/hrnet.py:24-56) — the reference's cuDNN picks the same algorithm

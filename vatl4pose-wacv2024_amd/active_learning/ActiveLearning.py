@@ -10,8 +10,9 @@ Same entry points as the reference class — ``ActiveLearning(cfg, opt)``, ``eva
 
 In scope: uncertainty None | HP | TPC | THC* (THC_L1, THC_L2, ...: always the L1 norm, ActiveLearning.py:346) | *WPU* (WPU,
 WPU_hybrid, WPU_raw: the reference matches these by substring, :371, and always takes the hybrid feature, :372) | THC+WPU |
-MPE | Margin | Entropy; representativeness None | Influence | Random; filter None | Random | Diversity | Coreset (device
-kernels, active_learning/query.py) and weighted | K-Means (sklearn on the host, exactly like the reference).  COCO mAP /
+MPE | Margin | Entropy; representativeness None | Influence | Random; filter None | Random | Diversity | Coreset | weighted |
+K-Means (device kernels, active_learning/query.py; the two clustering filters restate scikit-learn's seeded KMeans and hand a
+round back to it on the host only where its own answer hangs on rounding: ``query_path`` says which ran).  COCO mAP /
 OSPA evaluation, plots and the dead VL4Pose branch stay out.
 
 Multi-GPU: one process per GPU (active_learning/distributed.py).  Under torchrun every rank runs the driver; as one plain
@@ -147,6 +148,7 @@ class ActiveLearning:
         self.percentage, self.performance, self.performance_ann = [], [], []
         self.ospa_list, self.ospa_list_ann, self.combine_weight, self.uncertainty_mean, self.moksQ_list = [], [], [], [], []
         self.query_list_list, self.uncertainty_dict, self.influence_dict = {}, {}, {}
+        self.query_path = {}                                           # round -> which path clustered (weighted / K-Means filters)
         self.spearmanr_list, self.corr_list = [], []
         self.true_labeled_dict, self.false_labeled_dict, self.true_unlabeled_dict, self.false_unlabeled_dict = {}, {}, {}, {}
         self.actual_finish = self.finished_minerror = self.finished_oursc = 100
@@ -470,21 +472,22 @@ class ActiveLearning:
             else:
                 mode = "fixed" if getattr(self.opt, "fixed_lambda", False) else "moks"
             query = Q.coreset_selection(fvecs, self.labeled_id, unc_list, self.query_size, mode, self.moks_queried, self.unc_lambda)
-        else:                                                          # "weighted" / "K-Means": sklearn on the host, like the reference
-            emb = fvecs[torch.as_tensor(candidates, device=self.device)].double().cpu().numpy()
+        else:                                                          # "weighted" / "K-Means": scikit-learn's seeded run, on the device
+            emb = fvecs[torch.as_tensor(candidates, device=self.device)]
             if self.filter == "weighted":
-                _, first = np.unique(emb, axis=0, return_index=True)   # drop duplicate embeddings
-                emb = emb[first]
+                emb, first = Q.unique_rows(emb)                        # np.unique(emb, axis=0, return_index=True): drop duplicate embeddings
                 cand = [candidates[i] for i in first]
                 weight = (1 + self.w_unc * combine_weight * np.array([score_of[c] for c in candidates]))[first]
                 if nun <= self.query_size:
                     self.query_size = nun
-                self.query_size = min(self.query_size, len(emb))
-                query, _ = Q.kmeans_queries(emb, cand, self.query_size, weight)
+                self.query_size = min(self.query_size, len(cand))
+                picked = Q.kmeans_queries(emb, cand, self.query_size, weight)
             else:
                 if nun < self.query_size:
                     self.query_size = nun
-                query, _ = Q.kmeans_queries(emb, candidates, self.query_size)
+                picked = Q.kmeans_queries(emb, candidates, self.query_size)
+            query = picked[0]
+            self.query_path[f"Round{self.round_cnt}"] = {"path": picked.path, "reason": picked.reason, "n_iter": picked.n_iter}
 
         # Random representativeness / Random filter / the first k-center pick draw from the process-local numpy RNG: every
         # rank adopts rank 0's selection, or the ranks' labeled sets (and with them the fine-tune collectives) would diverge

@@ -152,6 +152,13 @@ SIGNATURES = {
     "vatl_cosine_rowsum": (_i, [_p, _i64, _i, _p, _p, _p]),
     "vatl_kcenter_update": (_i, [_p, _i64, _i, _p, _i, _p, _i, _p]),
     "vatl_kcenter_pick": (_i, [_p, _p, _d, _d, _p, _i, _i64, _p]),
+    "vatl_kmeans_prepare": (_i, [_p, _i64, _i, _p, _p, _p, _p, _p]),
+    "vatl_kmeans_seed_workspace_doubles": (_i64, [_i64, _i]),
+    "vatl_kmeans_seed": (_i, [_p, _p, _i64, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
+    "vatl_kmeans_assign": (_i, [_p, _p, _i64, _i, _i, _p, _p, _p, _p, _p]),
+    "vatl_kmeans_update_workspace_doubles": (_i64, [_i, _i]),
+    "vatl_kmeans_update": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
+    "vatl_kmeans_finish": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
     "vatl_adamw_step_multi": (_i, [_p, _i, _i64, _d, _d, _d, _d, _d, _i, _p]),
     "vatl_adam_step": (_i, [_p, _p, _p, _p, _i64, _d, _d, _d, _d, _d, _i, _p]),
     "vatl_sgd_step": (_i, [_p, _p, _p, _i64, _d, _d, _d, _i, _p]),
@@ -1018,6 +1025,64 @@ def kcenter_update(emb, centers: torch.Tensor, min_dist: torch.Tensor, first: bo
 def kcenter_pick(min_dist, unc, a: float, b: float, selected: torch.Tensor, step: int, n: int):
     _check(lib().vatl_kcenter_pick(_ptr(min_dist, torch.float64), _ptr(unc, torch.float64), a, b, _ptr(selected, torch.int32), step, n, _stream()),
            "vatl_kcenter_pick")
+
+
+def _f64(t):
+    return _ptr(t, torch.float64)
+
+
+def _i32(t):
+    return _ptr(t, torch.int32)
+
+
+def kmeans_prepare(emb: torch.Tensor):
+    """(n, D) fp32 -> centred float64 copy (n, D), column means (D), tol (1): mean(var(X, axis=0)) * 1e-4."""
+    n, d = emb.shape
+    xc = torch.empty((n, d), device=emb.device, dtype=torch.float64)
+    mean = torch.empty(d, device=emb.device, dtype=torch.float64)
+    tol = torch.empty(1, device=emb.device, dtype=torch.float64)
+    ws = torch.empty(max(d, 1), device=emb.device, dtype=torch.float64)
+    _check(lib().vatl_kmeans_prepare(_ptr(emb), n, d, _f64(xc), _f64(mean), _f64(tol), _f64(ws), _stream()), "vatl_kmeans_prepare")
+    return xc, mean, tol
+
+
+def kmeans_seed(xc: torch.Tensor, weight: torch.Tensor, k: int, first_index: int, draws: torch.Tensor, trials: int) -> torch.Tensor:
+    """k-means++ on the centred rows with the host's random draws ((k-1) * trials doubles on the device).  Returns int32 (k + 1):
+    the k seeding indices, then the tie flag."""
+    n, d = xc.shape
+    out = torch.zeros(k + 1, device=xc.device, dtype=torch.int32)
+    ws = torch.empty(max(int(lib().vatl_kmeans_seed_workspace_doubles(n, trials)), 1), device=xc.device, dtype=torch.float64)
+    _check(lib().vatl_kmeans_seed(_f64(xc), _f64(weight), n, d, k, first_index, _f64(draws), trials, _i32(out), out.data_ptr() + 4 * k, _f64(ws),
+                                  _stream()), "vatl_kmeans_seed")
+    return out
+
+
+def kmeans_assign(xc, centers, labels_prev, labels, status, workspace):
+    """labels <- nearest centre (f64 MFMA); status[0] <- 1.0 when a label differs from labels_prev (None: always)."""
+    _check(lib().vatl_kmeans_assign(_f64(xc), _f64(centers), xc.shape[0], xc.shape[1], centers.shape[0], _i32(labels_prev), _i32(labels), _f64(status),
+                                    _f64(workspace), _stream()), "vatl_kmeans_assign")
+
+
+def kmeans_update_workspace_doubles(d: int, k: int) -> int:
+    return int(lib().vatl_kmeans_update_workspace_doubles(d, k))
+
+
+def kmeans_update(xc, weight, labels, centers, centers_new, status, workspace):
+    """centers_new <- weighted cluster means; status[1] <- total squared shift, status[2] <- 1.0 when a cluster has no weight."""
+    _check(lib().vatl_kmeans_update(_f64(xc), _f64(weight), _i32(labels), _f64(centers), xc.shape[0], xc.shape[1], centers.shape[0], _f64(centers_new),
+                                    _f64(status), _f64(workspace), _stream()), "vatl_kmeans_update")
+
+
+def kmeans_finish(emb, xc, mean, weight, centers, labels) -> tuple[torch.Tensor, torch.Tensor]:
+    """-> (representatives int32 (k): per cluster the member nearest its centre, -1 without members; inertia float64 (1))."""
+    n, d = xc.shape
+    k = centers.shape[0]
+    reps = torch.empty(k, device=xc.device, dtype=torch.int32)
+    inertia = torch.empty(1, device=xc.device, dtype=torch.float64)
+    ws = torch.empty(2 * n, device=xc.device, dtype=torch.float64)
+    _check(lib().vatl_kmeans_finish(_ptr(emb), _f64(xc), _f64(mean), _f64(weight), _f64(centers), _i32(labels), n, d, k, _i32(reps), _f64(inertia),
+                                    _f64(ws), _stream()), "vatl_kmeans_finish")
+    return reps, inertia
 
 
 # ----------------------------------------------------------------------------
