@@ -562,6 +562,22 @@ int64_t vatl_adamw_multi_block_elems(void);
 int vatl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int step, void* stream);
 
+/* vatl_adam_step for a whole parameter group in one launch: the table of vatl_adamw_step_multi (rows of {p, g, m, v, numel,
+ * first_block}, blocks of vatl_adamw_multi_block_elems() elements).  Any element count; base pointers need only be 4-byte
+ * aligned (16-byte aligned rows take the float4 path).  The same bits per element as vatl_adam_step. */
+int vatl_adam_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, int step, void* stream);
+
+/* torch.optim.RMSprop step with momentum 0, not centered (posetrack_train.py:157-158): g' = g + wd*p;
+ * sq = alpha*sq + (1-alpha)*g'*g'; p -= lr*g' / (sqrt(sq) + eps).  One flat fp32 span, any count, 4-byte aligned. */
+int vatl_rmsprop_step(float* p, const float* g, float* sq, int64_t n, double lr, double alpha, double eps, double weight_decay,
+                      void* stream);
+
+/* The same for a parameter group in one launch: the table layout above, the v column holds sq, the m column is unused (may be 0).
+ * The same bits per element as vatl_rmsprop_step. */
+int vatl_rmsprop_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double alpha, double eps,
+                            double weight_decay, void* stream);
+
 /* torch.optim.SGD step with momentum (dampening 0, no Nesterov), ActiveLearning.py:220-221
  * (momentum 0.9, weight_decay 5e-4): g' = g + wd*p; buf = g' on step 1, momentum*buf + g' after;
  * p -= lr*buf. */

@@ -699,6 +699,73 @@ def gen_wellcond(EasyDict, out: str):
     np.savez_compressed(os.path.join(out, "wellcond_step.npz"), **res)
 
 
+PRETRAIN_SEEDS = (301, 311)                 # crops of step s: seed 301 + s; targets and masks: 311 + s
+PRETRAIN_HW = (128, 96)                     # the reference's modules and the build's trainers both take it (a quarter of the 256x192 work)
+PRETRAIN_STEPS, PRETRAIN_BATCH, PRETRAIN_LR = 3, 4, 1e-3
+
+
+def gen_pretrain(EasyDict, out: str):
+    """Three pre-training steps (scripts/posetrack_train.py `train()`: forward, 0.5 * MSE of the masked tensors, calc_accuracy,
+    zero_grad / backward / torch.optim.Adam(lr=1e-3).step()) of the reference's SimplePose-R50 at B = 4 on 128x96 crops, one fresh
+    batch per step.  Weights as in `gen_wellcond` (the build's default initialisation under WELLCOND_SEED, loaded strict=True);
+    inputs from oracle/synth.py seeds.  Stored: the three losses and accuracies, bn1.running_mean and 512 sampled values of every
+    10th parameter tensor and of the head after step 3 — and the same quantities from the same steps in float64 (oracle graph),
+    i.e. how far the reference's own fp32 arithmetic is from exact."""
+    import subprocess
+    import tempfile
+    from alphapose.models import builder                         # the reference's
+    from alphapose.utils.metrics import calc_accuracy            # the reference's
+    from oracle import nets
+    H, W = PRETRAIN_HW
+    hm = (H // 4, W // 4)
+    c = WELLCOND_MODELS["simplepose"]
+    preset = EasyDict({"TYPE": "simple", "SIGMA": 2, "NUM_JOINTS": 17, "IMAGE_SIZE": [H, W], "HEATMAP_SIZE": list(hm)})
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, "sd.pt")
+        child = (f"import sys, torch; sys.path[:0] = [{ROOT!r}, {os.path.join(ROOT, 'vatl4pose-wacv2024_amd')!r}]\n"
+                 "from alphapose.models import builder; from alphapose.utils.config import edict\n"
+                 f"torch.manual_seed({WELLCOND_SEED}); m = builder.build_sppe(edict({c!r}), preset_cfg=edict({dict(preset)!r}))\n"
+                 f"torch.save(m.state_dict(), {path!r})\n")
+        subprocess.run([sys.executable, "-c", child], check=True)
+        sd = torch.load(path)
+    batches = []
+    for s in range(PRETRAIN_STEPS):
+        labels, masks = synth.gaussian_targets(PRETRAIN_BATCH, seed=PRETRAIN_SEEDS[1] + s, hw=hm)
+        batches.append((synth.crops(PRETRAIN_BATCH, seed=PRETRAIN_SEEDS[0] + s, hw=PRETRAIN_HW), labels, masks))
+    res = {"batch": np.int64(PRETRAIN_BATCH), "steps": np.int64(PRETRAIN_STEPS), "seed": np.int64(WELLCOND_SEED), "lr": np.float64(PRETRAIN_LR),
+           "hw": np.asarray(PRETRAIN_HW, np.int64), "crop_seed": np.int64(PRETRAIN_SEEDS[0]), "target_seed": np.int64(PRETRAIN_SEEDS[1])}
+    ref32 = builder.build_sppe(EasyDict(c), preset_cfg=preset)
+    ref32.load_state_dict(sd, strict=True)
+    ref64 = nets.SimplePoseRef(50)
+    ref64.load_state_dict(sd, strict=True)
+    ref64 = ref64.double()
+    params = [k for k, _ in ref32.named_parameters()]
+    res["wsum"] = np.float64(sum(float(p.detach().double().abs().sum()) for p in ref32.parameters()))
+    picked = list(dict.fromkeys([k for i, k in enumerate(params) if i % 10 == 0] + [params[-2], params[-1]]))
+    for tag, m, dt in (("f32", ref32, torch.float32), ("f64", ref64, torch.float64)):
+        m.train()
+        adam = torch.optim.Adam(m.parameters(), lr=PRETRAIN_LR)
+        losses, accs = [], []
+        for x, labels, masks in batches:
+            x, t, w = (torch.from_numpy(a).to(dt) for a in (x, labels, masks))
+            outp = m(x.requires_grad_())                         # (the script asks for the input gradient too: same parameter gradients)
+            loss = 0.5 * torch.nn.MSELoss()(outp * w, t * w)
+            accs.append(float(calc_accuracy(outp * w, t * w)))
+            losses.append(float(loss.item()))
+            adam.zero_grad()
+            loss.backward()
+            adam.step()
+        res[f"loss_{tag}"], res[f"acc_{tag}"] = np.asarray(losses, np.float64), np.asarray(accs, np.float64)
+        res[f"bn1_running_mean_{tag}"] = m.preact.bn1.running_mean.detach().numpy().copy()
+        named = dict(m.named_parameters())
+        for k in picked:
+            ii = _sample_idx(named[k].numel(), "pt" + k, 512)
+            res[f"idx::{k}"] = ii.astype(np.int32)
+            res[f"param_{tag}::{k}"] = named[k].detach().reshape(-1)[ii].numpy().copy()
+        print("pretrain", tag, losses, accs)
+    np.savez_compressed(os.path.join(out, "pose_pretrain.npz"), **res)
+
+
 def gen_hostaug(out: str):
     """Host-side augmentation arithmetic of the reference's SimpleTransform, called unbound on seeded joints:
     half_body_transform (simple_transform.py:253-304, one np.random.randn() draw each) and _integral_target_generator
@@ -946,6 +1013,8 @@ def main():
         gen_crop(a.out)
     if a.only in ("", "wellcond"):
         gen_wellcond(EasyDict, a.out)
+    if a.only in ("", "pretrain"):
+        gen_pretrain(EasyDict, a.out)
     if a.only in ("", "hostaug"):
         gen_hostaug(a.out)
     if a.only in ("", "peaks"):

@@ -3,7 +3,8 @@
 ``AdamW`` has torch.optim.AdamW's constructor and param-group semantics (the reference builds
 three groups with lr x{10, 1, 5}); ``step()`` is one ``vatl_adamw_step_multi`` launch per parameter group
 (a device table of tensor pointers) instead of torch's element-wise kernels.  ``lr`` is read from the group at every step, so
-``torch.optim.lr_scheduler.ExponentialLR`` works on it unchanged.
+``torch.optim.lr_scheduler.ExponentialLR`` works on it unchanged.  ``Adam`` and ``RMSprop`` (the two optimisers of the pose-network
+pre-training script, posetrack_train.py:155-158) step the same way: one launch per (group, step).
 """
 from __future__ import annotations
 
@@ -60,7 +61,47 @@ class Adam(AdamW):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
 
     _kernel = staticmethod(vh.adam_step)
-    _multi = None                                  # per-tensor launches (the reference's default optimiser is AdamW)
+    _multi = staticmethod(vh.adam_step_multi)      # one launch per parameter group, the per-tensor kernel's bits
+
+
+class RMSprop(torch.optim.Optimizer):
+    """torch.optim.RMSprop with its defaults (posetrack_train.py:157-158): momentum 0, not centered; weight decay is an L2 term."""
+
+    def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False):
+        if lr < 0 or eps < 0 or weight_decay < 0 or alpha < 0:
+            raise ValueError("invalid RMSprop hyper-parameters")
+        if momentum != 0 or centered:
+            raise ValueError("RMSprop: only momentum=0, centered=False (torch's defaults) have a kernel")
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            items = []
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["square_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["step"] += 1
+                items.append((p, p.grad.contiguous(), st["square_avg"]))
+            if not items:
+                continue
+            if all(t[0].is_contiguous() for t in items):  # the update has no step-dependent scalar: one launch per group
+                vh.rmsprop_step_multi([t[0].data for t in items], [t[1] for t in items], [t[2] for t in items], group["lr"], group["alpha"],
+                                      group["eps"], group["weight_decay"])
+            else:
+                for p, g, sq in items:
+                    vh.rmsprop_step(p.data, g, sq, group["lr"], group["alpha"], group["eps"], group["weight_decay"])
+            for p, *_ in items:
+                torch.autograd.graph.increment_version(p)
+        return loss
 
 
 class SGD(torch.optim.Optimizer):

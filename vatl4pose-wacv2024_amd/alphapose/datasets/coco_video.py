@@ -123,20 +123,38 @@ class _CocoVideo(FrameVideo):
                         "keypoint": [0.0] * (self.num_joints * 3), "id": -1, "ann_id": -1, "track_id": -1})
         return out
 
+    # The host frame cache: at most FRAME_CACHE decoded frames, least recently used first out.  Everything that puts a frame in goes
+    # through cache_frames, so the bound holds whoever decoded it (this thread on a miss, or a consumer that decodes ahead).
+
+    def cache_frames(self, frames):
+        """Take decoded frames {path: (H, W, 3) uint8} into the cache (as most recently used) and evict down to FRAME_CACHE."""
+        for path, img in frames.items():
+            self._decoded[path] = img
+            self._decoded.move_to_end(path)
+        while len(self._decoded) > self.FRAME_CACHE:
+            self._decoded.popitem(last=False)
+
+    def reserve_frame_cache(self, n_frames):
+        """Make room for ``n_frames`` frames at least (a consumer that decodes a batch ahead holds two batches' frames)."""
+        self.FRAME_CACHE = max(int(self.FRAME_CACHE), int(n_frames))
+
+    def uncached_frames(self, idxs):
+        """Paths of the items' frames that are not in the cache now (each path once)."""
+        paths = (self._labels[int(i)]["frame"] for i in idxs)
+        return [p for p in OrderedDict.fromkeys(paths) if p not in self._decoded]
+
+    def _frame(self, path):
+        img = self._decoded.get(path)
+        if img is None:
+            img = _read_rgb(path)
+            self.cache_frames({path: img})
+        else:
+            self._decoded.move_to_end(path)
+        return img
+
     def _frames_for(self, keys):
         uniq = list(OrderedDict.fromkeys(keys))
-        frames = []
-        for path in uniq:
-            img = self._decoded.get(path)
-            if img is None:
-                img = _read_rgb(path)
-                self._decoded[path] = img
-                while len(self._decoded) > self.FRAME_CACHE:
-                    self._decoded.popitem(last=False)
-            else:
-                self._decoded.move_to_end(path)
-            frames.append(img)
-        return FrameArena(frames), {path: k for k, path in enumerate(uniq)}
+        return FrameArena([self._frame(path) for path in uniq]), {path: k for k, path in enumerate(uniq)}
 
 
 @DATASET.register_module

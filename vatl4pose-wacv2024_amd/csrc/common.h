@@ -54,6 +54,10 @@ __attribute__((visibility("hidden"))) int conv3x3_halo_try(const float* x, const
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// Elements per block of the multi-tensor optimiser launches (256 threads x 8 float4), train.hip and optim_multi.hip alike: the
+// `first_block` column of their shared device table is built from it (vatl_adamw_multi_block_elems).
+constexpr int kOptBlock = 8192;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // 64-lane butterfly reductions (wave = 64 on CDNA)

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) void gaussian_target_kernel(const float* __res
 // counts, all int64); a block updates kAdamBlock consecutive elements of ONE tensor, found by bisection over first_block — so a
 // 8.4 M-element deconv weight and a 64-element BatchNorm bias in the same group both get blocks in proportion to their size
 // (the first version gave every tensor the same <= 64 blocks: the 10.5 M-parameter deconv group ran at 1.9 TB/s on 64 CUs).
-constexpr int kAdamBlock = 8192;                  // elements per block: 256 threads x 8 float4
+constexpr int kAdamBlock = kOptBlock;             // elements per block (common.h)
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const long long* __restrict__ table, int n_tensors, float decay, float omb1, float b2,
                                                           float omb2, float bc2s, float eps, float step_size) {
     __shared__ int st;

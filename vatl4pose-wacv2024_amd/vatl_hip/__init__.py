@@ -161,6 +161,9 @@ SIGNATURES = {
     "vatl_kmeans_finish": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]),
     "vatl_adamw_step_multi": (_i, [_p, _i, _i64, _d, _d, _d, _d, _d, _i, _p]),
     "vatl_adam_step": (_i, [_p, _p, _p, _p, _i64, _d, _d, _d, _d, _d, _i, _p]),
+    "vatl_adam_step_multi": (_i, [_p, _i, _i64, _d, _d, _d, _d, _d, _i, _p]),
+    "vatl_rmsprop_step": (_i, [_p, _p, _p, _i64, _d, _d, _d, _d, _p]),
+    "vatl_rmsprop_step_multi": (_i, [_p, _i, _i64, _d, _d, _d, _d, _p]),
     "vatl_sgd_step": (_i, [_p, _p, _p, _i64, _d, _d, _d, _i, _p]),
 }
 
@@ -1609,16 +1612,15 @@ class ChecksumTable:
 _adamw_tables = {}                                   # (device, pointers...) -> (device table, total blocks): the pointers of a group do not change
 
 
-def adamw_step_multi(params, grads, ms, vs, step: int, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8):
-    """One launch for a list of tensors sharing hyper-parameters and step count."""
-    if not params:
-        return
+def _multi_table(what, params, grads, ms, vs):
+    """The device table of a multi-tensor optimiser launch: rows of {p, g, m, v, numel, first_block} (``ms`` None: the m column is 0)."""
     key = [params[0].device.index]
-    for p_, g_, m_, v_ in zip(params, grads, ms, vs):
-        for t in (p_, g_, m_, v_):
+    for k, (p_, g_, v_) in enumerate(zip(params, grads, vs)):
+        m_ = ms[k] if ms is not None else None
+        for t in (p_, g_, v_) + (() if m_ is None else (m_,)):
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise VatlError("adamw_step_multi needs contiguous fp32 device tensors")
-        key += [p_.data_ptr(), g_.data_ptr(), m_.data_ptr(), v_.data_ptr(), p_.numel()]
+                raise VatlError(f"{what} needs contiguous fp32 device tensors")
+        key += [p_.data_ptr(), g_.data_ptr(), 0 if m_ is None else m_.data_ptr(), v_.data_ptr(), p_.numel()]
     key = tuple(key)
     hit = _adamw_tables.get(key)
     if hit is None:                                  # built and uploaded once per (group, storage): no per-step host-to-device copy
@@ -1631,9 +1633,39 @@ def adamw_step_multi(params, grads, ms, vs, step: int, lr: float, weight_decay: 
         if len(_adamw_tables) > 64:
             _adamw_tables.clear()
         hit = _adamw_tables[key] = (torch.tensor(rows, dtype=torch.int64).to(params[0].device), blocks)
-    table, blocks = hit
+    return hit
+
+
+def adamw_step_multi(params, grads, ms, vs, step: int, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8):
+    """One launch for a list of tensors sharing hyper-parameters and step count."""
+    if not params:
+        return
+    table, blocks = _multi_table("adamw_step_multi", params, grads, ms, vs)
     _check(lib().vatl_adamw_step_multi(_ptr(table, torch.int64), len(params), blocks, lr, betas[0], betas[1], eps, weight_decay, step, _stream()),
            "vatl_adamw_step_multi")
+
+
+def adam_step_multi(params, grads, ms, vs, step: int, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
+    """``adam_step`` (L2 weight decay) for a list of tensors in one launch; the same bits as the per-tensor calls."""
+    if not params:
+        return
+    table, blocks = _multi_table("adam_step_multi", params, grads, ms, vs)
+    _check(lib().vatl_adam_step_multi(_ptr(table, torch.int64), len(params), blocks, lr, betas[0], betas[1], eps, weight_decay, step, _stream()),
+           "vatl_adam_step_multi")
+
+
+def rmsprop_step(p, g, sq, lr: float, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0.0):
+    """torch.optim.RMSprop (momentum 0, not centered) on one contiguous tensor; ``sq`` is the running square average."""
+    _check(lib().vatl_rmsprop_step(_ptr(p), _ptr(g), _ptr(sq), p.numel(), lr, alpha, eps, weight_decay, _stream()), "vatl_rmsprop_step")
+
+
+def rmsprop_step_multi(params, grads, sqs, lr: float, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0.0):
+    """``rmsprop_step`` for a list of tensors in one launch; the same bits as the per-tensor calls."""
+    if not params:
+        return
+    table, blocks = _multi_table("rmsprop_step_multi", params, grads, None, sqs)
+    _check(lib().vatl_rmsprop_step_multi(_ptr(table, torch.int64), len(params), blocks, lr, alpha, eps, weight_decay, _stream()),
+           "vatl_rmsprop_step_multi")
 
 
 def adam_step(p, g, m, v, step: int, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
