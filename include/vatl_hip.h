@@ -543,7 +543,11 @@ int vatl_ae_train_step_large(float* ae, float* m, float* v, const float* feat, i
                              double beta2, double eps, double weight_decay, int step, int decoupled, float* loss_or_null,
                              float* workspace, void* stream);
 
-/* torch.optim.AdamW step on one flat fp32 span (decoupled weight decay);
+/* The element-wise optimisers (csrc/optim.hip).  All of them run ONE update function, opt_update<KIND>, whose every product-sum is
+ * written out (fused or not) in the source, so an element's bits do not depend on the entry point, the path (float4 or scalar), the
+ * launch shape or the compiler: a multi entry gives the bits of its per-tensor entry, and tests/golden/optim_bits.npz pins them.
+ *
+ * torch.optim.AdamW step on one flat fp32 span (decoupled weight decay);
  * hyper-parameters are doubles like the Python floats torch derives its
  * per-step scalars from; `step` is the 1-based step count. */
 int vatl_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
@@ -552,7 +556,8 @@ int vatl_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, dou
 /* The same update for a whole parameter group in one launch: table_dev = n_tensors rows of {p, g, m, v, numel, first_block}
  * (device pointers, the element count, and the running sum of ceil(numel / vatl_adamw_multi_block_elems()) over the preceding
  * rows — all int64, resident on the device); total_blocks = that sum over all rows.  Every tensor shares the hyper-parameters
- * and the step count; tensors get blocks in proportion to their size.  Arithmetic per element identical to vatl_adamw_step. */
+ * and the step count; tensors get blocks in proportion to their size.  Any element count; base pointers need only be 4-byte
+ * aligned (16-byte aligned rows take the float4 path).  The same bits per element as vatl_adamw_step (opt_update<OPT_ADAMW>). */
 int vatl_adamw_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double beta1, double beta2, double eps,
                           double weight_decay, int step, void* stream);
 int64_t vatl_adamw_multi_block_elems(void);
@@ -564,7 +569,7 @@ int vatl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, doub
 
 /* vatl_adam_step for a whole parameter group in one launch: the table of vatl_adamw_step_multi (rows of {p, g, m, v, numel,
  * first_block}, blocks of vatl_adamw_multi_block_elems() elements).  Any element count; base pointers need only be 4-byte
- * aligned (16-byte aligned rows take the float4 path).  The same bits per element as vatl_adam_step. */
+ * aligned (16-byte aligned rows take the float4 path).  The same bits per element as vatl_adam_step (opt_update<OPT_ADAM>). */
 int vatl_adam_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double beta1, double beta2, double eps,
                          double weight_decay, int step, void* stream);
 
@@ -574,7 +579,7 @@ int vatl_rmsprop_step(float* p, const float* g, float* sq, int64_t n, double lr,
                       void* stream);
 
 /* The same for a parameter group in one launch: the table layout above, the v column holds sq, the m column is unused (may be 0).
- * The same bits per element as vatl_rmsprop_step. */
+ * The same bits per element as vatl_rmsprop_step (opt_update<OPT_RMSPROP>). */
 int vatl_rmsprop_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double alpha, double eps,
                             double weight_decay, void* stream);
 

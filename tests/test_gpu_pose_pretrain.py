@@ -1,4 +1,4 @@
-"""Pose-network pre-training on the device (alphapose/pretrain.py) and its one-launch optimiser steps (csrc/optim_multi.hip)."""
+"""Pose-network pre-training on the device (alphapose/pretrain.py); its one-launch optimiser steps (csrc/optim.hip) are in test_gpu_optim.py."""
 import json
 import os
 import random
@@ -25,95 +25,6 @@ def vh():
 def _preset(hw=(256, 192)):
     from alphapose.utils.config import edict
     return edict({"TYPE": "simple", "SIGMA": 2, "NUM_JOINTS": 17, "IMAGE_SIZE": list(hw), "HEATMAP_SIZE": [hw[0] // 4, hw[1] // 4]})
-
-
-def _optimiser_tensors(vh, seed):
-    """Parameters around the multi kernel's block size, a conv weight, and a view whose base is only 4-byte aligned."""
-    E = int(vh.lib().vatl_adamw_multi_block_elems())
-    r = np.random.RandomState(seed)
-    shapes = [(1,), (17,), (E - 1,), (E,), (E + 1,), (2 * E + 3,), (64, 32, 3, 3)]
-    ps = [torch.nn.Parameter(to_dev(r.standard_normal(s).astype(np.float32))) for s in shapes]
-    buf = to_dev(r.standard_normal(1100).astype(np.float32))
-    view = torch.nn.Parameter(buf[1:1 + 1001])
-    assert view.data_ptr() % 16 == 4 and view.is_contiguous()
-    ps.append(view)
-    skipped = torch.nn.Parameter(to_dev(r.standard_normal(33).astype(np.float32)))       # never gets a gradient
-    return E, r, ps, skipped
-
-
-def _grads_like(r, ps, misalign):
-    """Fresh gradients; the one of the 4-byte-aligned parameter is itself a view at a 4-byte-aligned base."""
-    gs = []
-    for k, p in enumerate(ps):
-        g = r.standard_normal(tuple(p.shape)).astype(np.float32)
-        if k == misalign:
-            holder = to_dev(np.concatenate([np.zeros(3, np.float32), g.reshape(-1)]))
-            gs.append(holder[3:].view(p.shape))
-        else:
-            gs.append(to_dev(g))
-    return gs
-
-
-@pytest.mark.parametrize("wd", [0.0, 0.01])
-def test_adam_multi_equals_per_tensor_bit_for_bit(vh, wd):
-    """`vatl_adam_step_multi` behind optim.Adam against `vatl_adam_step` tensor by tensor: the same bits after 3 steps, for sizes around
-    the block size, an unaligned base and a parameter without gradient; every stepped parameter's version counter moved."""
-    from active_learning.optim import Adam
-    E, r, ps, skipped = _optimiser_tensors(vh, 23)
-    qs = [p.detach().clone() for p in ps]                                      # (clones are 16-byte aligned: the per-tensor kernel's contract)
-    ms, vs = [torch.zeros_like(q) for q in qs], [torch.zeros_like(q) for q in qs]
-    before = skipped.detach().clone()
-    opt = Adam(ps + [skipped], lr=1e-3, weight_decay=wd)
-    assert Adam._multi is not None
-    for step in range(1, 4):
-        gs = _grads_like(r, ps, misalign=len(ps) - 1)
-        for p, g in zip(ps, gs):
-            p.grad = g
-        opt.step()
-        for q, g, m, v in zip(qs, gs, ms, vs):
-            vh.adam_step(q, g.clone(), m, v, step, 1e-3, wd)
-    for p, q, m, v in zip(ps, qs, ms, vs):
-        assert torch.equal(p.detach(), q) and p._version > 0, tuple(p.shape)
-        assert torch.equal(opt.state[p]["exp_avg"], m) and torch.equal(opt.state[p]["exp_avg_sq"], v)
-    assert torch.equal(skipped.detach(), before) and skipped not in opt.state
-
-
-def _rmsprop_f64(p, g, sq, lr, alpha, eps, wd):
-    g = g + wd * p
-    sq = alpha * sq + (1 - alpha) * g * g
-    return p - lr * g / (np.sqrt(sq) + eps), sq
-
-
-def test_rmsprop_multi_equals_per_tensor_and_torch(vh):
-    """`vatl_rmsprop_step_multi` behind optim.RMSprop: the same bits as `vatl_rmsprop_step` per tensor, and 4 steps against
-    torch.optim.RMSprop on the CPU (lr 1e-3, weight_decay 5e-4) at the Adam test's bar, rtol 2e-5 / atol 1e-6.  The distance of
-    torch's own fp32 result from a float64 restatement of the same steps is recorded beside ours (measured: 3.3e-7 both)."""
-    from active_learning.optim import RMSprop
-    E, r, ps, skipped = _optimiser_tensors(vh, 29)
-    lr, wd = 1e-3, 5e-4
-    qs = [p.detach().clone() for p in ps]
-    sqs = [torch.zeros_like(q) for q in qs]
-    ts = [torch.nn.Parameter(p.detach().cpu().clone()) for p in ps]
-    f64 = [(p.detach().cpu().double().numpy(), np.zeros(tuple(p.shape))) for p in ps]
-    opt, topt = RMSprop(ps + [skipped], lr=lr, weight_decay=wd), torch.optim.RMSprop(ts, lr=lr, weight_decay=wd)
-    for step in range(1, 5):
-        gs = _grads_like(r, ps, misalign=len(ps) - 1)
-        for p, t, g in zip(ps, ts, gs):
-            p.grad, t.grad = g, g.cpu().clone()
-        opt.step(); topt.step()
-        for q, g, sq in zip(qs, gs, sqs):
-            vh.rmsprop_step(q, g, sq, lr, weight_decay=wd)
-        f64 = [_rmsprop_f64(p64, g.cpu().double().numpy(), s64, lr, 0.99, 1e-8, wd) for (p64, s64), g in zip(f64, gs)]
-    ours_worst = torch_worst = 0.0
-    for p, q, sq, t, (p64, _) in zip(ps, qs, sqs, ts, f64):
-        assert torch.equal(p.detach(), q) and torch.equal(opt.state[p]["square_avg"], sq) and p._version > 0, tuple(p.shape)
-        got, want = p.detach().cpu().numpy(), t.detach().numpy()
-        ours_worst = max(ours_worst, float(np.abs(got - p64).max()))
-        torch_worst = max(torch_worst, float(np.abs(want - p64).max()))
-        np.testing.assert_allclose(got, want, rtol=2e-5, atol=1e-6)
-    print(f"rmsprop after 4 steps, max abs distance from float64: ours {ours_worst:.3e}, torch fp32 {torch_worst:.3e}")
-    record("rmsprop_step", ours_vs_f64=ours_worst, torch_fp32_vs_f64=torch_worst)
-    assert skipped not in opt.state
 
 
 def _fixed_batches(sizes=(4, 4, 3), hw=(256, 192), seed=400):

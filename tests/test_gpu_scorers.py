@@ -197,28 +197,6 @@ def test_masked_mse_and_adamw(vh):
     np.testing.assert_allclose(dp.cpu().numpy(), p, rtol=2e-5, atol=1e-6)                      # vs the numpy oracle
 
 
-def test_adam_and_sgd_steps(vh):
-    """ActiveLearning.py:220-223: the two other optimisers the reference can be configured with."""
-    from active_learning.optim import SGD, Adam
-    r = np.random.RandomState(5)
-    n = 70001
-    p0 = r.standard_normal(n).astype(np.float32)
-    a, m, v = p0.copy(), np.zeros(n, np.float32), np.zeros(n, np.float32)
-    b, buf = p0.copy(), np.zeros(n, np.float32)
-    da = torch.nn.Parameter(to_dev(p0)); ds = torch.nn.Parameter(to_dev(p0))
-    oa, os_ = Adam([da], lr=2.5e-4), SGD([ds], lr=2.5e-4, momentum=0.9, weight_decay=0.0005)
-    for step in range(1, 5):
-        g = r.standard_normal(n).astype(np.float32)
-        da.grad = to_dev(g); ds.grad = to_dev(g)
-        oa.step(); os_.step()
-        a, m, v = scorers.adam_step(a, g, m, v, step, 2.5e-4)
-        b, buf = scorers.sgd_step(b, g, buf, step, 2.5e-4, 0.9, 0.0005)
-    record("adam_step", rel=rel_err(da.detach().cpu().numpy(), a)); record("sgd_step", rel=rel_err(ds.detach().cpu().numpy(), b))
-    np.testing.assert_allclose(da.detach().cpu().numpy(), a, rtol=2e-5, atol=1e-6)
-    np.testing.assert_allclose(ds.detach().cpu().numpy(), b, rtol=2e-6, atol=1e-7)
-    assert da._version > 0 and ds._version > 0           # plan caches key on the version counter
-
-
 def test_empty_and_ragged_batches(vh):
     """Edge cases: empty streams return empty results, a 1-item stream has no neighbours, odd sizes work."""
     d = dev()
@@ -333,27 +311,6 @@ def test_decode_with_nan_and_inf_entries(vh):
         assert np.array_equal(m[n][ok], d["maxvals"][ok, 0])
         np.testing.assert_allclose(c[n], d["coords"], rtol=1e-6, atol=1e-4)
     assert i[0, 2] == 10 * 48 + 7 and i[0, 5] == 33 * 48 + 21 and i[1, 0] == 0 and i[1, 4] == 63 * 48 + 47
-
-
-def test_multi_tensor_adamw_equals_per_tensor(vh):
-    """One launch per parameter group (`vatl_adamw_step_multi`) against the per-tensor kernel: same bits, odd sizes and
-    unaligned tails included; the optimizer class uses it and bumps every parameter's version counter."""
-    from active_learning.optim import AdamW
-    r = np.random.RandomState(17)
-    sizes = [(64,), (17,), (256, 64, 3, 3), (1001,), (5, 7), (2048, 512, 1, 1)]
-    ps = [torch.nn.Parameter(to_dev(r.standard_normal(s).astype(np.float32))) for s in sizes]
-    qs = [p.detach().clone() for p in ps]
-    ms, vs = [torch.zeros_like(q) for q in qs], [torch.zeros_like(q) for q in qs]
-    opt = AdamW([{"params": ps[:2], "lr": 2.5e-3}, {"params": ps[2:], "lr": 2.5e-4}], weight_decay=0.7)
-    for step in range(1, 4):
-        gs = [to_dev(r.standard_normal(s).astype(np.float32)) for s in sizes]
-        for p, g in zip(ps, gs):
-            p.grad = g
-        opt.step()
-        for k, (q, g, m, v) in enumerate(zip(qs, gs, ms, vs)):
-            vh.adamw_step(q, g, m, v, step, 2.5e-3 if k < 2 else 2.5e-4, 0.7)
-    for p, q in zip(ps, qs):
-        assert torch.equal(p.detach(), q) and p._version > 0
 
 
 @pytest.mark.parametrize("hw", [(64, 48), (96, 72), (32, 24), (10, 7)])

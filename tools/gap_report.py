@@ -3,7 +3,7 @@
 
     python tools/gap_report.py <..._kernel_trace.csv> [steps]
 
-Takes the dispatches between the first and the last `adamw_multi_kernel` launch of the trace (whole optimizer steps),
+Takes the dispatches between the first and the last `opt_multi_kernel` launch of the trace (whole optimizer steps),
 and prints per step: wall time, union of kernel intervals (busy), idle time, the number of launches, the idle time
 split by gap size, and kernel time by category (conv fwd+dgrad / wgrad / BatchNorm + element-wise / micro-launches
 shorter than 15 us / optimizer / other).
@@ -18,7 +18,7 @@ def category(name: str) -> str:
         return "wgrad"
     if "conv_igemm" in name or "gemm1x1" in name or "conv3x3_halo" in name or "streamk" in name or "winograd_kernel" in name or "winograd_persist_kernel" in name or "stem_pool_kernel" in name or "bottleneck_chain_kernel" in name or "conv1x1_rows_kernel" in name or "conv1x1_rows256_kernel" in name or "winograd_c32_kernel" in name or "winograd_f4_kernel" in name:
         return "conv_fwd_dgrad"
-    if "adamw" in name or "adam_" in name or "sgd" in name:
+    if "opt_multi_kernel" in name or "opt_flat_kernel" in name or "adamw" in name:      # (adamw_*: traces older than csrc/optim.hip)
         return "optimizer"
     for k in ("bn_", "scale_bias", "col_reduce", "maxpool", "relu", "nchw", "se_", "pixel", "fuse_up", "col_sum", "hw_reduce", "masked_mse", "mse_finish"):
         if k in name:
@@ -32,7 +32,7 @@ def main():
     path = sys.argv[1]
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    opt = [i for i, r in enumerate(rows) if "adamw_multi_kernel" in r["Kernel_Name"] or "adam_step" in r["Kernel_Name"]]
+    opt = [i for i, r in enumerate(rows) if "opt_multi_kernel" in r["Kernel_Name"]]
     if len(opt) < 2:
         sys.exit("need at least two optimizer steps in the trace")
     # optimizer launches come in groups (one per parameter group, a pointer-table copy between them): a step ends with the last

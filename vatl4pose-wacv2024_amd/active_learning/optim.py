@@ -13,14 +13,15 @@ import torch
 import vatl_hip as vh
 
 
-class AdamW(torch.optim.Optimizer):
-    _kernel = staticmethod(vh.adamw_step)
-    _multi = staticmethod(vh.adamw_step_multi)     # one launch per parameter group (161 tensors for SimplePose-R50)
+class _Stepper(torch.optim.Optimizer):
+    """The step loop the optimisers share; a subclass names its state buffers, its per-tensor call and, if it has one, its multi call."""
+    _buffers = ()                                  # state keys, in the order of the calls' buffer arguments
+    _kernel = None                                 # (p, g, *buffers, *hyper): one tensor
+    _multi = None                                  # (params, grads, *buffer lists, *hyper): one launch; None: one launch per tensor
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
-            raise ValueError("invalid AdamW hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def _hyper(self, group, step):
+        """The arguments of ``_kernel`` / ``_multi`` after the tensors."""
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -36,22 +37,36 @@ class AdamW(torch.optim.Optimizer):
                 st = self.state[p]
                 if not st:
                     st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                    for name in self._buffers:
+                        st[name] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["step"] += 1
-                batch.setdefault(st["step"], []).append((p, p.grad.contiguous(), st["exp_avg"], st["exp_avg_sq"]))
+                batch.setdefault(st["step"], []).append((p, p.grad.contiguous()) + tuple(st[name] for name in self._buffers))
             for step, items in batch.items():
+                hyper = self._hyper(group, step)
                 if self._multi is not None and all(t[0].is_contiguous() for t in items):
-                    self._multi([t[0].data for t in items], [t[1] for t in items], [t[2] for t in items], [t[3] for t in items], step,
-                                group["lr"], group["weight_decay"], group["betas"], group["eps"])
+                    self._multi([t[0].data for t in items], *([t[k] for t in items] for k in range(1, 2 + len(self._buffers))), *hyper)
                 else:
-                    for p, g, m, v in items:
-                        self._kernel(p.data, g, m, v, step, group["lr"], group["weight_decay"], group["betas"], group["eps"])
+                    for p, *rest in items:
+                        self._kernel(p.data, *rest, *hyper)
                 # the in-place update went through the C ABI: bump the version counters ourselves, the
                 # inference plans key their packed-weight caches on them
                 for p, *_ in items:
                     torch.autograd.graph.increment_version(p)
         return loss
+
+
+class AdamW(_Stepper):
+    _buffers = ("exp_avg", "exp_avg_sq")
+    _kernel = staticmethod(vh.adamw_step)
+    _multi = staticmethod(vh.adamw_step_multi)     # one launch per parameter group (161 tensors for SimplePose-R50)
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("invalid AdamW hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _hyper(self, group, step):
+        return step, group["lr"], group["weight_decay"], group["betas"], group["eps"]
 
 
 class Adam(AdamW):
@@ -64,8 +79,11 @@ class Adam(AdamW):
     _multi = staticmethod(vh.adam_step_multi)      # one launch per parameter group, the per-tensor kernel's bits
 
 
-class RMSprop(torch.optim.Optimizer):
+class RMSprop(_Stepper):
     """torch.optim.RMSprop with its defaults (posetrack_train.py:157-158): momentum 0, not centered; weight decay is an L2 term."""
+    _buffers = ("square_avg",)
+    _kernel = staticmethod(vh.rmsprop_step)
+    _multi = staticmethod(vh.rmsprop_step_multi)
 
     def __init__(self, params, lr=1e-2, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, centered=False):
         if lr < 0 or eps < 0 or weight_decay < 0 or alpha < 0:
@@ -74,60 +92,19 @@ class RMSprop(torch.optim.Optimizer):
             raise ValueError("RMSprop: only momentum=0, centered=False (torch's defaults) have a kernel")
         super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for group in self.param_groups:
-            items = []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["square_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] += 1
-                items.append((p, p.grad.contiguous(), st["square_avg"]))
-            if not items:
-                continue
-            if all(t[0].is_contiguous() for t in items):  # the update has no step-dependent scalar: one launch per group
-                vh.rmsprop_step_multi([t[0].data for t in items], [t[1] for t in items], [t[2] for t in items], group["lr"], group["alpha"],
-                                      group["eps"], group["weight_decay"])
-            else:
-                for p, g, sq in items:
-                    vh.rmsprop_step(p.data, g, sq, group["lr"], group["alpha"], group["eps"], group["weight_decay"])
-            for p, *_ in items:
-                torch.autograd.graph.increment_version(p)
-        return loss
+    def _hyper(self, group, step):                 # the update has no step-dependent scalar
+        return group["lr"], group["alpha"], group["eps"], group["weight_decay"]
 
 
-class SGD(torch.optim.Optimizer):
-    """torch.optim.SGD with momentum as the reference configures it (ActiveLearning.py:220-221)."""
+class SGD(_Stepper):
+    """torch.optim.SGD with momentum as the reference configures it (ActiveLearning.py:220-221); one launch per tensor."""
+    _buffers = ("momentum_buffer",)
+    _kernel = staticmethod(vh.sgd_step)
 
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
         if lr < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError("invalid SGD hyper-parameters")
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        for group in self.param_groups:
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["step"] += 1
-                vh.sgd_step(p.data, p.grad.contiguous(), st["momentum_buffer"], st["step"], group["lr"], group["momentum"],
-                            group["weight_decay"])
-                torch.autograd.graph.increment_version(p)
-        return loss
+    def _hyper(self, group, step):
+        return step, group["lr"], group["momentum"], group["weight_decay"]

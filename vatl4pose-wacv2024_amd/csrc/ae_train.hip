@@ -156,8 +156,8 @@ __global__ __launch_bounds__(256) void ae_grad_partial_kernel(const float* __res
 }
 
 // MODE 0: grad[pi] = sum of the block partials.  MODE 1: torch.optim.Adam (l2 = weight_decay, decay = 1) or torch.optim.AdamW
-// (l2 = 0, decay = 1 - lr * weight_decay) on ae / am / av with that gradient; per element the arithmetic of opt_elem<0> / adamw_kernel
-// (train.hip).  Block 0 also reduces the loss.
+// (l2 = 0, decay = 1 - lr * weight_decay) on ae / am / av with that gradient; per element the formulas of opt_update<OPT_ADAM> /
+// <OPT_ADAMW> (optim.hip), in plain C++ here: this kernel's contraction is the compiler's.  Block 0 also reduces the loss.
 template <int MODE>
 __global__ __launch_bounds__(256) void ae_grad_finish_kernel(const float* __restrict__ part, const float* __restrict__ lossp, int nblk, int P,
                                                              float* __restrict__ grad, float* __restrict__ ae, float* __restrict__ am,

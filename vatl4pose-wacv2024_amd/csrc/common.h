@@ -55,8 +55,8 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Elements per block of the multi-tensor optimiser launches (256 threads x 8 float4), train.hip and optim_multi.hip alike: the
-// `first_block` column of their shared device table is built from it (vatl_adamw_multi_block_elems).
+// Elements per block of the optimiser launches (256 threads x 8 float4), optim.hip: the `first_block` column of the multi-tensor
+// device table is built from it (vatl_adamw_multi_block_elems).
 constexpr int kOptBlock = 8192;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -1,6 +1,5 @@
-// Fine-tune step pieces that are pure HBM streams:
+// Fine-tune step pieces: the losses, the Gaussian targets and the one-block WholeBodyAE step (the optimisers are in optim.hip)
 //   masked MSE forward+backward   ActiveLearning.py:669  (0.5 * MSELoss(out*m, tgt*m))
-//   AdamW update                  ActiveLearning.py:224-228, :673
 #include "common.h"
 
 namespace vatl {
@@ -40,85 +39,6 @@ __global__ __launch_bounds__(256) void mse_finish_kernel(const double* __restric
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) *loss = (float)((part[0] + part[1] + part[2] + part[3]) * half_inv_numel);
-}
-
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, long long n, float decay, float omb1, float b2, float omb2,
-                                                    float bc2s, float eps, float step_size) {
-    const long long n4 = n >> 2;
-    for (long long q = blockIdx.x * 256LL + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
-        f32x4 P = *reinterpret_cast<f32x4*>(p + 4 * q);
-        const f32x4 G = *reinterpret_cast<const f32x4*>(g + 4 * q);
-        f32x4 M = *reinterpret_cast<f32x4*>(m + 4 * q);
-        f32x4 V = *reinterpret_cast<f32x4*>(v + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            P[e] = P[e] * decay;
-            M[e] = M[e] + (G[e] - M[e]) * omb1;
-            V[e] = V[e] * b2 + G[e] * G[e] * omb2;
-            P[e] = P[e] - step_size * (M[e] / (sqrtf(V[e]) / bc2s + eps));
-        }
-        *reinterpret_cast<f32x4*>(p + 4 * q) = P;
-        *reinterpret_cast<f32x4*>(m + 4 * q) = M;
-        *reinterpret_cast<f32x4*>(v + 4 * q) = V;
-    }
-    if (blockIdx.x == 0) {
-        for (long long i = 4 * n4 + threadIdx.x; i < n; i += 256) {
-            float P = p[i] * decay;
-            const float G = g[i];
-            const float M = m[i] + (G - m[i]) * omb1;
-            const float V = v[i] * b2 + G * G * omb2;
-            P = P - step_size * (M / (sqrtf(V) / bc2s + eps));
-            p[i] = P; m[i] = M; v[i] = V;
-        }
-    }
-}
-
-// torch.optim.Adam (L2 decay folded into the gradient) and torch.optim.SGD (momentum, dampening 0, no Nesterov)
-// ActiveLearning.py:220-223.  MODE 0 = Adam, 1 = SGD first step (buf = g), 2 = SGD later steps (buf = mu*buf + g).
-template <int MODE>
-__device__ __forceinline__ void opt_elem(float& P, float G, float& M, float& V, float wd, float omb1, float b2, float omb2, float bc2s,
-                                         float eps, float step_size) {
-    G = G + wd * P;
-    if (MODE == 0) {
-        M = M + (G - M) * omb1;
-        V = V * b2 + G * G * omb2;
-        P = P - step_size * (M / (sqrtf(V) / bc2s + eps));
-    } else {
-        M = (MODE == 1) ? G : M * b2 + G;          // b2 carries the momentum for SGD
-        P = P - step_size * M;
-    }
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void opt_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, long long n, float wd, float omb1, float b2, float omb2,
-                                                  float bc2s, float eps, float step_size) {
-    const long long n4 = n >> 2;
-    for (long long q = blockIdx.x * 256LL + threadIdx.x; q < n4; q += (long long)gridDim.x * 256) {
-        f32x4 P = *reinterpret_cast<f32x4*>(p + 4 * q);
-        const f32x4 G = *reinterpret_cast<const f32x4*>(g + 4 * q);
-        f32x4 M = *reinterpret_cast<f32x4*>(m + 4 * q);
-        f32x4 V = {0.f, 0.f, 0.f, 0.f};
-        if (MODE == 0) V = *reinterpret_cast<f32x4*>(v + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float pe = P[e], me = M[e], ve = V[e];
-            opt_elem<MODE>(pe, G[e], me, ve, wd, omb1, b2, omb2, bc2s, eps, step_size);
-            P[e] = pe; M[e] = me; V[e] = ve;
-        }
-        *reinterpret_cast<f32x4*>(p + 4 * q) = P;
-        *reinterpret_cast<f32x4*>(m + 4 * q) = M;
-        if (MODE == 0) *reinterpret_cast<f32x4*>(v + 4 * q) = V;
-    }
-    if (blockIdx.x == 0) {
-        for (long long i = 4 * n4 + threadIdx.x; i < n; i += 256) {
-            float P = p[i], M = m[i], V = (MODE == 0) ? v[i] : 0.f;
-            opt_elem<MODE>(P, g[i], M, V, wd, omb1, b2, omb2, bc2s, eps, step_size);
-            p[i] = P; m[i] = M;
-            if (MODE == 0) v[i] = V;
-        }
-    }
 }
 
 // --------------------------------------------------------------------------
@@ -335,65 +255,6 @@ __global__ __launch_bounds__(256) void gaussian_target_kernel(const float* __res
     }
 }
 
-// Multi-tensor AdamW: one launch per parameter group instead of one per tensor (161 tensors for SimplePose-R50).
-// table[t] = {p, g, m, v, n, first_block} (device pointers, element count and the running sum of the preceding tensors' block
-// counts, all int64); a block updates kAdamBlock consecutive elements of ONE tensor, found by bisection over first_block — so a
-// 8.4 M-element deconv weight and a 64-element BatchNorm bias in the same group both get blocks in proportion to their size
-// (the first version gave every tensor the same <= 64 blocks: the 10.5 M-parameter deconv group ran at 1.9 TB/s on 64 CUs).
-constexpr int kAdamBlock = kOptBlock;             // elements per block (common.h)
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const long long* __restrict__ table, int n_tensors, float decay, float omb1, float b2,
-                                                          float omb2, float bc2s, float eps, float step_size) {
-    __shared__ int st;
-    if (threadIdx.x == 0) {
-        int lo = 0, hi = n_tensors - 1;
-        const long long b = blockIdx.x;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (table[6 * (long long)mid + 5] <= b) lo = mid; else hi = mid - 1;
-        }
-        st = lo;
-    }
-    __syncthreads();
-    const long long* row = table + 6 * (long long)st;
-    float* __restrict__ p = reinterpret_cast<float*>(row[0]);
-    const float* __restrict__ g = reinterpret_cast<const float*>(row[1]);
-    float* __restrict__ m = reinterpret_cast<float*>(row[2]);
-    float* __restrict__ v = reinterpret_cast<float*>(row[3]);
-    const long long n = row[4];
-    const long long e0 = ((long long)blockIdx.x - row[5]) * kAdamBlock;
-    const long long e1 = e0 + kAdamBlock < n ? e0 + kAdamBlock : n;
-    const bool vec = ((row[0] | row[1] | row[2] | row[3]) & 15) == 0;          // e0 is a multiple of 4
-    long long done = e0;
-    if (vec) {
-        const long long q1 = e1 >> 2;
-        for (long long q = (e0 >> 2) + threadIdx.x; q < q1; q += 256) {
-            f32x4 P = *reinterpret_cast<f32x4*>(p + 4 * q);
-            const f32x4 G = *reinterpret_cast<const f32x4*>(g + 4 * q);
-            f32x4 M = *reinterpret_cast<f32x4*>(m + 4 * q);
-            f32x4 V = *reinterpret_cast<f32x4*>(v + 4 * q);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                P[e] = P[e] * decay;
-                M[e] = M[e] + (G[e] - M[e]) * omb1;
-                V[e] = V[e] * b2 + G[e] * G[e] * omb2;
-                P[e] = P[e] - step_size * (M[e] / (sqrtf(V[e]) / bc2s + eps));
-            }
-            *reinterpret_cast<f32x4*>(p + 4 * q) = P;
-            *reinterpret_cast<f32x4*>(m + 4 * q) = M;
-            *reinterpret_cast<f32x4*>(v + 4 * q) = V;
-        }
-        done = q1 << 2;
-    }
-    for (long long i = done + threadIdx.x; i < e1; i += 256) {
-        float P = p[i] * decay;
-        const float G = g[i];
-        const float M = m[i] + (G - m[i]) * omb1;
-        const float V = v[i] * b2 + G * G * omb2;
-        P = P - step_size * (M / (sqrtf(V) / bc2s + eps));
-        p[i] = P; m[i] = M; v[i] = V;
-    }
-}
-
 }  // namespace vatl
 
 using namespace vatl;
@@ -415,55 +276,6 @@ extern "C" int vatl_masked_mse_fwd_bwd(const float* out, const float* target, co
     hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const double*>(partial), blocks, loss,
                        0.5 / (double)numel);
     return check_launch("masked_mse_fwd_bwd");
-}
-
-extern "C" int vatl_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                               double eps, double weight_decay, int step, void* stream) {
-    if (!p || !g || !m || !v) return fail(VATL_EINVAL, "adamw_step: null pointer");
-    if (step < 1) return fail(VATL_EINVAL, "adamw_step: step is 1-based");
-    if (n <= 0) return 0;
-    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return fail(VATL_EINVAL, "adamw_step: spans must be 16-byte aligned");
-    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
-    long long blocks = (n / 4 + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n,
-                       (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                       (float)sqrt(bc2), (float)eps, (float)(lr / bc1));
-    return check_launch("adamw_step");
-}
-
-static unsigned opt_blocks(int64_t n) {
-    long long blocks = (n / 4 + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
-extern "C" int vatl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
-                              double eps, double weight_decay, int step, void* stream) {
-    if (!p || !g || !m || !v) return fail(VATL_EINVAL, "adam_step: null pointer");
-    if (step < 1) return fail(VATL_EINVAL, "adam_step: step is 1-based");
-    if (n <= 0) return 0;
-    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return fail(VATL_EINVAL, "adam_step: spans must be 16-byte aligned");
-    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
-    hipLaunchKernelGGL(opt_kernel<0>, dim3(opt_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n, (float)weight_decay,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(lr / bc1));
-    return check_launch("adam_step");
-}
-
-extern "C" int vatl_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double weight_decay, int step,
-                             void* stream) {
-    if (!p || !g || !buf) return fail(VATL_EINVAL, "sgd_step: null pointer");
-    if (step < 1) return fail(VATL_EINVAL, "sgd_step: step is 1-based");
-    if (n <= 0) return 0;
-    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) return fail(VATL_EINVAL, "sgd_step: spans must be 16-byte aligned");
-    if (step == 1)
-        hipLaunchKernelGGL(opt_kernel<1>, dim3(opt_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, (float*)nullptr, (long long)n,
-                           (float)weight_decay, 0.f, (float)momentum, 0.f, 1.f, 0.f, (float)lr);
-    else
-        hipLaunchKernelGGL(opt_kernel<2>, dim3(opt_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, buf, (float*)nullptr, (long long)n,
-                           (float)weight_decay, 0.f, (float)momentum, 0.f, 1.f, 0.f, (float)lr);
-    return check_launch("sgd_step");
 }
 
 extern "C" int vatl_l1_joint_regression_fwd_bwd(const float* hm, const float* gt_joints, const float* gt_joints_vis, float* grad, float* loss,
@@ -504,18 +316,3 @@ extern "C" int vatl_gaussian_targets(const float* joints_xy, const float* vis, f
                        (double)in_h / (double)H, (double)in_w / (double)W, sigma);   // the reference divides x by stride[0] = in_h / H (:130)
     return check_launch("gaussian_targets");
 }
-
-extern "C" int vatl_adamw_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double beta1, double beta2, double eps,
-                                     double weight_decay, int step, void* stream) {
-    if (n_tensors <= 0) return 0;
-    if (!table_dev) return fail(VATL_EINVAL, "adamw_step_multi: null table");
-    if (step < 1) return fail(VATL_EINVAL, "adamw_step_multi: step is 1-based");
-    if (total_blocks <= 0 || total_blocks > 0x7FFFFFFF) return fail(VATL_EINVAL, "adamw_step_multi: total_blocks %lld out of range", (long long)total_blocks);
-    const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const long long*>(table_dev), n_tensors, (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1), (float)beta2,
-                       (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(lr / bc1));
-    return check_launch("adamw_step_multi");
-}
-
-extern "C" int64_t vatl_adamw_multi_block_elems(void) { return kAdamBlock; }

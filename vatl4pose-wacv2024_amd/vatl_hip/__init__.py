@@ -1609,7 +1609,7 @@ class ChecksumTable:
         return out
 
 
-_adamw_tables = {}                                   # (device, pointers...) -> (device table, total blocks): the pointers of a group do not change
+_opt_tables = {}                                     # (device, pointers...) -> (device table, total blocks): the pointers of a group do not change
 
 
 def _multi_table(what, params, grads, ms, vs):
@@ -1622,7 +1622,7 @@ def _multi_table(what, params, grads, ms, vs):
                 raise VatlError(f"{what} needs contiguous fp32 device tensors")
         key += [p_.data_ptr(), g_.data_ptr(), 0 if m_ is None else m_.data_ptr(), v_.data_ptr(), p_.numel()]
     key = tuple(key)
-    hit = _adamw_tables.get(key)
+    hit = _opt_tables.get(key)
     if hit is None:                                  # built and uploaded once per (group, storage): no per-step host-to-device copy
         be = int(lib().vatl_adamw_multi_block_elems())
         rows, blocks = [], 0
@@ -1630,28 +1630,28 @@ def _multi_table(what, params, grads, ms, vs):
             p_, g_, m_, v_, n = key[1 + 5 * k:6 + 5 * k]
             rows.append((p_, g_, m_, v_, n, blocks))
             blocks += (n + be - 1) // be
-        if len(_adamw_tables) > 64:
-            _adamw_tables.clear()
-        hit = _adamw_tables[key] = (torch.tensor(rows, dtype=torch.int64).to(params[0].device), blocks)
+        if len(_opt_tables) > 64:
+            _opt_tables.clear()
+        hit = _opt_tables[key] = (torch.tensor(rows, dtype=torch.int64).to(params[0].device), blocks)
     return hit
+
+
+def _step_multi(what, params, grads, ms, vs, *scalars):
+    """One ``vatl_<what>`` launch over the table of the lists (nothing to do for empty lists)."""
+    if not params:
+        return
+    table, blocks = _multi_table(what, params, grads, ms, vs)
+    _check(getattr(lib(), "vatl_" + what)(_ptr(table, torch.int64), len(params), blocks, *scalars, _stream()), "vatl_" + what)
 
 
 def adamw_step_multi(params, grads, ms, vs, step: int, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8):
     """One launch for a list of tensors sharing hyper-parameters and step count."""
-    if not params:
-        return
-    table, blocks = _multi_table("adamw_step_multi", params, grads, ms, vs)
-    _check(lib().vatl_adamw_step_multi(_ptr(table, torch.int64), len(params), blocks, lr, betas[0], betas[1], eps, weight_decay, step, _stream()),
-           "vatl_adamw_step_multi")
+    _step_multi("adamw_step_multi", params, grads, ms, vs, lr, betas[0], betas[1], eps, weight_decay, step)
 
 
 def adam_step_multi(params, grads, ms, vs, step: int, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
     """``adam_step`` (L2 weight decay) for a list of tensors in one launch; the same bits as the per-tensor calls."""
-    if not params:
-        return
-    table, blocks = _multi_table("adam_step_multi", params, grads, ms, vs)
-    _check(lib().vatl_adam_step_multi(_ptr(table, torch.int64), len(params), blocks, lr, betas[0], betas[1], eps, weight_decay, step, _stream()),
-           "vatl_adam_step_multi")
+    _step_multi("adam_step_multi", params, grads, ms, vs, lr, betas[0], betas[1], eps, weight_decay, step)
 
 
 def rmsprop_step(p, g, sq, lr: float, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0.0):
@@ -1661,11 +1661,7 @@ def rmsprop_step(p, g, sq, lr: float, alpha: float = 0.99, eps: float = 1e-8, we
 
 def rmsprop_step_multi(params, grads, sqs, lr: float, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0.0):
     """``rmsprop_step`` for a list of tensors in one launch; the same bits as the per-tensor calls."""
-    if not params:
-        return
-    table, blocks = _multi_table("rmsprop_step_multi", params, grads, None, sqs)
-    _check(lib().vatl_rmsprop_step_multi(_ptr(table, torch.int64), len(params), blocks, lr, alpha, eps, weight_decay, _stream()),
-           "vatl_rmsprop_step_multi")
+    _step_multi("rmsprop_step_multi", params, grads, None, sqs, lr, alpha, eps, weight_decay)
 
 
 def adam_step(p, g, m, v, step: int, lr: float, weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8):
