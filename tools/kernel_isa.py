@@ -7,8 +7,9 @@
 ``dump`` compiles every csrc/*.hip of TREE (a checkout of this repository) device-only with that tree's own build.py
 FLAGS, unbundles the gfx950 code object and records, per kernel symbol, a hash of its disassembly (address column and
 the ``// addr: bytes <sym+off>`` trailers stripped; branch operands are pc-relative, so a kernel reads the same
-wherever it sits in its code object; objdump's ``...`` for the zero padding behind a function is dropped: it depends on
-what the linker placed next, not on the kernel) and its entry of the amdhsa.kernels note.  The key is the mangled kernel name,
+wherever it sits in its code object; objdump's ``...`` for the zero padding behind a function, the ``s_nop 0`` padding
+behind the last one and the pc-relative address of a constant table are dropped: they depend on what the linker placed next
+to the kernel, not on the kernel) and its entry of the amdhsa.kernels note.  The key is the mangled kernel name,
 not the file, so a kernel that moved between files compares against itself.  ``compare`` prints every kernel that is
 missing, new or different and exits non-zero if there is one.
 """
@@ -34,6 +35,18 @@ def _out(*cmd: str) -> str:
     return subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
 
 
+def _position_free(lines: list) -> list:
+    """Drops what depends on where the kernel sits in its code object: the ``s_nop 0`` run that pads the end of the last function, and the
+    literal of the ``s_add_u32`` / ``s_addc_u32`` pair behind an ``s_getpc_b64`` (the pc-relative address of a constant table)."""
+    while lines and lines[-1] == "s_nop 0":
+        lines.pop()
+    for i, ln in enumerate(lines):
+        if ln.startswith("s_getpc_b64"):
+            for j in range(i + 1, min(i + 3, len(lines))):
+                lines[j] = re.sub(r"^(s_addc?_u32 s\d+, s\d+), (0x[0-9a-f]+|-?\d+)$", r"\1, <pcrel>", lines[j])
+    return lines
+
+
 def _kernels_of(src: str, flags: list, hipcc: str, tmp: str) -> dict:
     base = os.path.join(tmp, os.path.basename(src)[:-4])
     _out(hipcc, *flags, "--offload-device-only", "-c", src, "-o", base + ".o")
@@ -48,7 +61,7 @@ def _kernels_of(src: str, flags: list, hipcc: str, tmp: str) -> dict:
     for head in re.split(r"\n(?=[0-9a-f]{16} <)", _out(os.path.join(LLVM, "llvm-objdump"), "-d", "--no-show-raw-insn", base + ".co")):
         m = re.match(r"[0-9a-f]{16} <(.+)>:\n", head)
         if m and m.group(1) in notes:
-            text[m.group(1)] = [ln.split("//")[0].strip() for ln in head[m.end():].splitlines() if ln.strip() not in ("", "...")]
+            text[m.group(1)] = _position_free([ln.split("//")[0].strip() for ln in head[m.end():].splitlines() if ln.strip() not in ("", "...")])
     return {k: {"file": os.path.basename(src), "insns": len(text[k]), "isa_sha256": hashlib.sha256("\n".join(text[k]).encode()).hexdigest(),
                 **notes[k]} for k in notes}
 

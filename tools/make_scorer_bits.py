@@ -1,0 +1,41 @@
+"""Writes tests/golden/scorer_bits.npz: the bits the PARENT commit's library gives for the cases of tests/scorer_cases.py.
+
+    VATL_HIP_LIB=/path/to/parent/libvatl_hip.so python tools/make_scorer_bits.py <parent commit hash> [out.npz]
+
+Run on the MI355X against a library built from the commit BEFORE a change to the scorer kernels (csrc/decode.hip, localpeak.hip,
+heatmap_criteria.hip, pose_feature.hip, scorer_common.h), never against the tree's own library: the fixture exists so that a change
+of their arithmetic — a compiler upgrade, an edit — shows as a failure of tests/test_gpu_scorer_bits.py.  The parent library can be
+cross-compiled on a host without a GPU (git worktree add ../parent <hash>; python ../parent/vatl4pose-wacv2024_amd/build.py) and carried
+to the GPU box.  The hash is stored as given (`parent_commit`): the tool cannot tell which commit a library was built from, so it is
+the word of whoever ran it, as in make_optim_bits.py.  Outputs only: float32 / float64 as uint32 / uint64 bit patterns, masks as packed bits, integers raw.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "vatl4pose-wacv2024_amd")]
+
+if not os.environ.get("VATL_HIP_LIB"):
+    sys.exit("make_scorer_bits: set VATL_HIP_LIB to the parent commit's libvatl_hip.so (see the docstring)")
+if len(sys.argv) < 2:
+    sys.exit(__doc__)
+
+import vatl_hip as vh  # noqa: E402
+from tests.scorer_cases import CASES, GOLDEN, run  # noqa: E402
+
+
+def main():
+    out = {"parent_commit": np.array(sys.argv[1])}
+    for name in CASES:
+        got = run(vh, name)
+        out.update(got)
+        print(name, {k.rsplit(".", 1)[1]: (v.dtype.name, v.shape) for k, v in got.items()})
+    path = sys.argv[2] if len(sys.argv) > 2 else GOLDEN
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes,", len(CASES), "cases, library", vh.LIB_PATH)
+
+
+if __name__ == "__main__":
+    main()

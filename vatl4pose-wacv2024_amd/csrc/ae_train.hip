@@ -3,7 +3,7 @@
 //   vatl_ae_train_step_large   forward + MSELoss(output, input) + backward + Adam / AdamW      script lines 147-152
 // Two launches each, no host synchronisation, no floating-point atomics:
 //   1. ae_grad_partial_kernel: block k takes a contiguous range of items, 64 at a time (one item per lane).  It recomputes the forward
-//      pass in LDS with ae_forward_kernel's operation order (scorers2.hip: acc = bias, then fmaf over k ascending), so the ReLU masks are
+//      pass in LDS with ae_forward_kernel's operation order (pose_feature.hip: acc = bias, then fmaf over k ascending), so the ReLU masks are
 //      the ones the forward pass produced, forms the deltas layer by layer, and every thread sums ITS parameters over the items in item
 //      order.  The block's sums go to partial[k][P], its squared-error sum to the P-th column block.
 //   2. ae_grad_finish_kernel: one thread per parameter adds the block partials in block order in double, then writes the gradient

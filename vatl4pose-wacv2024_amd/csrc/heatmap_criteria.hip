@@ -1,11 +1,93 @@
-// Third group of scorers: the heat-map criteria beside HP
-//   MPE / Margin  compute_mpe / compute_margin    ActiveLearning.py:762-788  (skimage.feature.peak_local_max(min_distance=5,
+// Heat-map criteria beside HP, each reading the (N,J,H,W) fp32 heat-maps once:
+//   THC           compute_thc + neighbour rule     active_learning/ActiveLearning.py:345-363, 747-760
+//   TPC           compute_tpc + neighbour rule     ActiveLearning.py:333-344, 736-745
+//   MPE / Margin  compute_mpe / compute_margin     ActiveLearning.py:762-788  (skimage.feature.peak_local_max(min_distance=5,
 //                                                  num_peaks=5) + scipy softmax / entropy)
 //   Entropy       compute_entropy                  ActiveLearning.py:790-796  (scipy.stats.entropy of the flattened map)
-// One block per (item, joint) plane; the plane lives in LDS.
-#include "common.h"
+#include "scorer_common.h"
 
 namespace vatl {
+
+// --------------------------------------------------------------------------
+// THC: one block per pair of heat-map stacks (J*H*W floats each)
+// --------------------------------------------------------------------------
+template <int NORM>
+__global__ __launch_bounds__(256) void thc_pairs_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                        long long sa, long long sb, float* __restrict__ out, int J, int n) {
+    const float* pa = a + (long long)blockIdx.x * sa;
+    const float* pb = b + (long long)blockIdx.x * sb;
+    const int tid = threadIdx.x;
+    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
+    const int n4 = n >> 2;
+    for (int q = tid; q < n4; q += 256) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(pa + 4 * q);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(pb + 4 * q);
+        const float d0 = x[0] - y[0], d1 = x[1] - y[1], d2 = x[2] - y[2], d3 = x[3] - y[3];
+        if (NORM == 1) { acc0 += fabsf(d0); acc1 += fabsf(d1); acc2 += fabsf(d2); acc3 += fabsf(d3); }
+        else           { acc0 += d0 * d0;   acc1 += d1 * d1;   acc2 += d2 * d2;   acc3 += d3 * d3; }
+    }
+    for (int q = 4 * n4 + tid; q < n; q += 256) {
+        const float d = pa[q] - pb[q];
+        acc0 += NORM == 1 ? fabsf(d) : d * d;
+    }
+    __shared__ double part[4];
+    block4_put(part, wave_sum((double)acc0 + (double)acc1 + (double)acc2 + (double)acc3));
+    __syncthreads();
+    if (tid == 0) out[blockIdx.x] = (float)(block4_sum(part) / (double)J);
+}
+
+__global__ void thc_combine_kernel(const float* __restrict__ pair, const uint8_t* __restrict__ is_prev,
+                                   const uint8_t* __restrict__ is_next, float* __restrict__ thc, int N) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const bool hp = is_prev[i] != 0 && i > 0, hn = is_next[i] != 0 && i < N - 1;
+    float t = 0.f;
+    if (hp) t += pair[i - 1];
+    if (hn) t += pair[i];
+    if (hp != hn) t *= 2.f;                                     // exactly one neighbour: doubled
+    thc[i] = t;
+}
+
+// --------------------------------------------------------------------------
+// TPC: one thread per item.  adj_prev[i] / adj_next[i] are the neighbours' heat-maps
+// decoded with item i's box (vatl_decode_argmax_affine on shifted views).
+// --------------------------------------------------------------------------
+__device__ __forceinline__ int moved_joints(const float* a, const float* b, int J, double thresh) {
+    int c = 0;
+    for (int j = 0; j < J; ++j) {
+        const float dx = a[2 * j] - b[2 * j], dy = a[2 * j + 1] - b[2 * j + 1];
+        const float d = sqrtf(dx * dx + dy * dy);             // np.linalg.norm on float32 rows
+        c += ((double)d > thresh) ? 1 : 0;
+    }
+    return c;
+}
+
+__global__ void tpc_stream_kernel(const float* __restrict__ cur, const float* __restrict__ adj_prev, const float* __restrict__ adj_next,
+                                  const float* __restrict__ bbox, const uint8_t* __restrict__ is_prev, const uint8_t* __restrict__ is_next,
+                                  float* __restrict__ tpc, int N, int J) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const double w = (double)bbox[4 * i + 2] - (double)bbox[4 * i + 0], h = (double)bbox[4 * i + 3] - (double)bbox[4 * i + 1];
+    const double thresh = 0.01 * sqrt(w * h);
+    const bool hp = is_prev[i] != 0 && i > 0, hn = is_next[i] != 0 && i < N - 1;
+    int t = 0;
+    if (hp) t += moved_joints(cur + (long long)i * J * 2, adj_prev + (long long)i * J * 2, J, thresh);
+    if (hn) t += moved_joints(cur + (long long)i * J * 2, adj_next + (long long)i * J * 2, J, thresh);
+    if (hp != hn) t *= 2;
+    tpc[i] = (float)t;
+}
+
+// --------------------------------------------------------------------------
+// peaks5 with MPE and Margin: one block (or one wave) per plane
+// --------------------------------------------------------------------------
+// arg-max of per-thread (value, index) pairs over the block, to every thread; sval / sidx are free again on return
+__device__ __forceinline__ void block_argmax_reduce(float& bv, int& bi, float* sval, int* sidx) {
+    wave_argmax<false>(bv, bi);
+    block4_put(sval, bv); block4_put(sidx, bi);
+    __syncthreads();
+    block4_argmax<false>(sval, sidx, bv, bi);
+    __syncthreads();
+}
 
 // Block-wide arg-max over (value desc, index asc); -inf entries never win.  Returns the flat index or -1.
 __device__ __forceinline__ int block_argmax(const float* v, int n, float* sval, int* sidx, float& best_val) {
@@ -14,25 +96,31 @@ __device__ __forceinline__ int block_argmax(const float* v, int n, float* sval, 
         const float x = v[i];
         if (x > bv) { bv = x; bi = i; }                        // strided scan keeps the lowest index among equals per thread
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if ((threadIdx.x & 63) == 0) { sval[threadIdx.x >> 6] = bv; sidx[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    bv = sval[0]; bi = sidx[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-        if (sval[w] > bv || (sval[w] == bv && sidx[w] < bi)) { bv = sval[w]; bi = sidx[w]; }
-    __syncthreads();
+    block_argmax_reduce(bv, bi, sval, sidx);
     best_val = bv;
     return bv == -INFINITY ? -1 : bi;
 }
 
+// a plane's peaks and its MPE and Margin terms (one thread)
+__device__ __forceinline__ void store_peaks5(float* peak_val, int32_t* peak_idx, int32_t* npeaks,
+                                             float* mpe, float* margin, long long plane, const float* pv, const int* pi, int n) {
+    npeaks[plane] = n;
+    for (int k = 0; k < 5; ++k) { peak_val[plane * 5 + k] = k < n ? pv[k] : 0.f; peak_idx[plane * 5 + k] = k < n ? pi[k] : -1; }
+    float e = 0.f;
+    if (n > 0) {                                            // entropy(softmax(peaks)), float32 like scipy on a float32 array
+        float ex[5], s = 0.f;
+        for (int k = 0; k < n; ++k) { ex[k] = expf(pv[k] - pv[0]); s += ex[k]; }
+        float q[5], qs = 0.f;
+        for (int k = 0; k < n; ++k) { q[k] = ex[k] / s; qs += q[k]; }
+        for (int k = 0; k < n; ++k) { const float p = q[k] / qs; e += p > 0.f ? -p * logf(p) : 0.f; }
+    }
+    mpe[plane] = e;
+    margin[plane] = n > 1 ? fabsf(pv[0] - pv[1]) : 0.f;
+}
+
 // peak_local_max(plane, min_distance = D, num_peaks = 5): (2D+1)^2 maximum filter with replicated edges, strictly
 // above the plane minimum, D-wide border excluded, greedy spacing (Chebyshev distance < D rejected) in descending
-// intensity / ascending index order, first five kept.  Also the per-plane MPE and Margin terms.
+// intensity / ascending index order, first five kept.  Also the per-plane MPE and Margin terms.  The plane lives in LDS.
 __global__ __launch_bounds__(256) void peaks5_kernel(const float* __restrict__ hm, float* __restrict__ peak_val, int32_t* __restrict__ peak_idx,
                                                      int32_t* __restrict__ npeaks, float* __restrict__ mpe, float* __restrict__ margin,
                                                      int H, int W, int D) {
@@ -44,8 +132,7 @@ __global__ __launch_bounds__(256) void peaks5_kernel(const float* __restrict__ h
     const float* src = hm + (long long)blockIdx.x * HW;
     float mn = INFINITY;
     for (int i = threadIdx.x; i < HW; i += 256) { const float v = src[i]; img[i] = v; mn = fminf(mn, v); }
-    mn = -wave_max(-mn);
-    if ((threadIdx.x & 63) == 0) sval[threadIdx.x >> 6] = mn;
+    block4_put(sval, -wave_max(-mn));
     __syncthreads();
     mn = fminf(fminf(sval[0], sval[1]), fminf(sval[2], sval[3]));
     __syncthreads();
@@ -103,24 +190,10 @@ __global__ __launch_bounds__(256) void peaks5_kernel(const float* __restrict__ h
     const int nc = ccount;
     float pv[5]; int pi[5]; int n = 0;
     if (nc <= CAP) {
-        for (int k = 0; k < 5; ++k) {                            // block_argmax orders by (value desc, flat index asc): slot order is irrelevant
+        for (int k = 0; k < 5; ++k) {                            // ordered by (value desc, flat index asc): slot order is irrelevant
             float bv = -INFINITY; int bi = 0x7FFFFFFF;
-            for (int t = threadIdx.x; t < nc; t += 256) {
-                const float x = cval[t]; const int xi = cidx[t];
-                if (x > bv || (x == bv && xi < bi)) { bv = x; bi = xi; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
-            if ((threadIdx.x & 63) == 0) { sval[threadIdx.x >> 6] = bv; sidx[threadIdx.x >> 6] = bi; }
-            __syncthreads();
-            bv = sval[0]; bi = sidx[0];
-#pragma unroll
-            for (int w = 1; w < 4; ++w)
-                if (sval[w] > bv || (sval[w] == bv && sidx[w] < bi)) { bv = sval[w]; bi = sidx[w]; }
-            __syncthreads();
+            for (int t = threadIdx.x; t < nc; t += 256) argmax_merge<false>(bv, bi, cval[t], cidx[t]);
+            block_argmax_reduce(bv, bi, sval, sidx);
             if (bv == -INFINITY) break;
             pv[n] = bv; pi[n] = bi; ++n;
             const int by = bi / W, bx = bi - by * W;
@@ -145,47 +218,27 @@ __global__ __launch_bounds__(256) void peaks5_kernel(const float* __restrict__ h
             __syncthreads();
         }
     }
-    if (threadIdx.x == 0) {
-        const long long o = (long long)blockIdx.x;
-        npeaks[o] = n;
-        for (int k = 0; k < 5; ++k) { peak_val[o * 5 + k] = k < n ? pv[k] : 0.f; peak_idx[o * 5 + k] = k < n ? pi[k] : -1; }
-        float e = 0.f;
-        if (n > 0) {                                            // entropy(softmax(peaks)), float32 like scipy on a float32 array
-            float ex[5], s = 0.f;
-            for (int k = 0; k < n; ++k) { ex[k] = expf(pv[k] - pv[0]); s += ex[k]; }
-            float q[5], qs = 0.f;
-            for (int k = 0; k < n; ++k) { q[k] = ex[k] / s; qs += q[k]; }
-            for (int k = 0; k < n; ++k) { const float p = q[k] / qs; e += p > 0.f ? -p * logf(p) : 0.f; }
-        }
-        mpe[o] = e;
-        margin[o] = n > 1 ? fabsf(pv[0] - pv[1]) : 0.f;
-    }
+    if (threadIdx.x == 0) store_peaks5(peak_val, peak_idx, npeaks, mpe, margin, (long long)blockIdx.x, pv, pi, n);
 }
 
 // The same function for the shipped heat-map size (64 x 48) and min_distance (5: ActiveLearning.py:773,784) with ONE WAVE per
-// plane and no LDS / block barriers: lane = row, the row's 48 values live in registers.  Row pass of the 11 x 11 maximum
-// filter: in registers (clipped window = replicated edges).  Column pass: the window [y-5, y+5] is the union of a backward run
-// (y-5..y) and a forward run (y..y+5), each built by doubling from lane shuffles (6 per column, out-of-range rows contribute
-// -inf).  Candidates stay in registers; the greedy selection is five rounds of a per-lane scan + wave arg-max (value
-// descending, flat index ascending — the order of the block kernel) + in-register suppression.  The block kernel above spent
-// its time in 17 barriers and an LDS compaction per plane (1300 us per 4096 items = 0.65 TB/s; this kernel: 437 us = 1.96 TB/s).
+// plane and no block barriers: lane = row, the row's 48 values live in registers.  The 11 x 11 maximum filter is two in-register
+// passes of the doubling scheme (windows of 2, 4, 8, then 8 + 4 overlapping = 11: 4 max operations per pixel and pass instead of
+// 10), the COLUMN pass on a transposed copy of the plane — written row-wise to a wave-private LDS tile (pitch W + 4 floats:
+// conflict-free both ways), read column-wise (lane = column), filtered, written back and read row-wise again.  Same window maxima
+// as the block kernel (max is associative; fmaxf treats a NaN as missing in any order), same candidates, same greedy selection.
+// The block kernel spends its time in 17 barriers and an LDS compaction per plane.
 template <int W>
 __global__ __launch_bounds__(256) void peaks5_wave_kernel(const float* __restrict__ hm, float* __restrict__ peak_val, int32_t* __restrict__ peak_idx,
                                                           int32_t* __restrict__ npeaks, float* __restrict__ mpe, float* __restrict__ margin,
                                                           long long planes) {
     constexpr int D = 5, H = 64;
     static_assert(W % 4 == 0 && W > 2 * D && W <= 64, "row of W floats per lane");
-    // Round 4: the 11 x 11 maximum filter as two in-register passes of the doubling scheme (windows of 2, 4, 8, then 8 + 4 overlapping = 11:
-    // 4 max operations per pixel and pass instead of 10), the COLUMN pass on a transposed copy of the plane — written row-wise to a
-    // wave-private LDS tile (pitch W + 4 floats: conflict-free both ways), read column-wise (lane = column), filtered, written back and
-    // read row-wise again — instead of six lane shuffles and eight max / select operations per pixel.  Round 3's kernel was bound by its
-    // ~1200 vector and ~290 LDS-permute instructions per plane (2.1 TB/s); this one issues ~600 + ~150.  Same window maxima (max is
-    // associative; fmaxf treats a NaN as missing in any order), same candidates, same greedy selection.
     constexpr int P = W + 4;
     extern __shared__ __attribute__((aligned(16))) float tile_all[];
     const int lane = threadIdx.x & 63;
     float* tile = tile_all + (threadIdx.x >> 6) * (H * P);
-    const long long plane = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long plane = wave_plane();
     if (plane >= planes) return;
     const float* src = hm + plane * (H * W) + lane * W;
     float v[W];
@@ -253,8 +306,8 @@ __global__ __launch_bounds__(256) void peaks5_wave_kernel(const float* __restric
     float pv[5]; int pi[5]; int n = 0;
     // Greedy selection.  A plane has few candidates (maxima of 11 x 11 windows: typically 10 - 25): they are compacted into a list of at most
     // 64 — one per lane, in LDS where the tile was — and the five rounds run on ONE value per lane (wave arg-max + one distance test) instead
-    // of re-scanning 48 registers per lane and round, which was two thirds of this kernel's vector instructions.  Planes with more than 64
-    // candidates (plateaus of equal values) take the register scan below.  Same order either way: value descending, flat index ascending.
+    // of re-scanning 48 registers per lane and round.  Planes with more than 64 candidates (plateaus of equal values) take the register scan
+    // below.  Same order either way: value descending, flat index ascending.
     int mine = 0;
 #pragma unroll
     for (int x = D; x < W - D; ++x) mine += cand[x] > -INFINITY ? 1 : 0;
@@ -277,11 +330,7 @@ __global__ __launch_bounds__(256) void peaks5_wave_kernel(const float* __restric
 #pragma unroll 1
         for (int k = 0; k < 5; ++k) {
             float bv = cv; int bi = cv > -INFINITY ? ci : 0x7FFFFFFF;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-            }
+            wave_argmax<false>(bv, bi);
             if (bv == -INFINITY) break;
             pv[n] = bv; pi[n] = bi; ++n;
             const int by = bi / W, bx = bi - by * W;
@@ -289,44 +338,36 @@ __global__ __launch_bounds__(256) void peaks5_wave_kernel(const float* __restric
         }
     } else {
 #pragma unroll 1
-    for (int k = 0; k < 5; ++k) {
-        float bv = -INFINITY; int bi = 0x7FFFFFFF;
-#pragma unroll
-        for (int x = 0; x < W; ++x)
-            if (cand[x] > bv) { bv = cand[x]; bi = lane * W + x; }          // ascending x: the first maximum of the row
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (bv == -INFINITY) break;
-        pv[n] = bv; pi[n] = bi; ++n;
-        const int by = bi / W, bx = bi - by * W;
-        if (abs(lane - by) < D) {
+        for (int k = 0; k < 5; ++k) {
+            float bv = -INFINITY; int bi = 0x7FFFFFFF;
 #pragma unroll
             for (int x = 0; x < W; ++x)
-                if (abs(x - bx) < D) cand[x] = -INFINITY;
+                if (cand[x] > bv) { bv = cand[x]; bi = lane * W + x; }          // ascending x: the first maximum of the row
+            wave_argmax<false>(bv, bi);
+            if (bv == -INFINITY) break;
+            pv[n] = bv; pi[n] = bi; ++n;
+            const int by = bi / W, bx = bi - by * W;
+            if (abs(lane - by) < D) {
+#pragma unroll
+                for (int x = 0; x < W; ++x)
+                    if (abs(x - bx) < D) cand[x] = -INFINITY;
+            }
         }
     }
-    }
-    if (lane == 0) {
-        npeaks[plane] = n;
-        for (int k = 0; k < 5; ++k) { peak_val[plane * 5 + k] = k < n ? pv[k] : 0.f; peak_idx[plane * 5 + k] = k < n ? pi[k] : -1; }
-        float e = 0.f;
-        if (n > 0) {                                            // entropy(softmax(peaks)), float32 like scipy on a float32 array
-            float ex[5], s = 0.f;
-            for (int k = 0; k < n; ++k) { ex[k] = expf(pv[k] - pv[0]); s += ex[k]; }
-            float q[5], qs = 0.f;
-            for (int k = 0; k < n; ++k) { q[k] = ex[k] / s; qs += q[k]; }
-            for (int k = 0; k < n; ++k) { const float p = q[k] / qs; e += p > 0.f ? -p * logf(p) : 0.f; }
-        }
-        mpe[plane] = e;
-        margin[plane] = n > 1 ? fabsf(pv[0] - pv[1]) : 0.f;
-    }
+    if (lane == 0) store_peaks5(peak_val, peak_idx, npeaks, mpe, margin, plane, pv, pi, n);
 }
 
-// scipy.stats.entropy(plane.flatten()): p = h / sum(h); sum of entr(p) with entr(p) = -p ln p (p > 0), 0 (p == 0),
-// -inf (p < 0); a zero sum gives nan like numpy's 0/0 and x/0.
+// --------------------------------------------------------------------------
+// Entropy: scipy.stats.entropy(plane.flatten()): p = h / sum(h), then the sum of entr(p); a zero sum gives nan like numpy's 0/0 and x/0
+// --------------------------------------------------------------------------
+// scipy.special.entr: -p ln p (p > 0), 0 (p == 0), -inf (p < 0), nan (nan)
+__device__ __forceinline__ float entr(float p) {
+    if (p > 0.f) return -p * logf(p);
+    if (p == 0.f) return 0.f;
+    if (p < 0.f) return -INFINITY;
+    return p;
+}
+
 __global__ __launch_bounds__(256) void plane_entropy_kernel(const float* __restrict__ hm, float* __restrict__ out, int HW) {
     const float* gsrc = hm + (long long)blockIdx.x * HW;
     extern __shared__ __attribute__((aligned(16))) float plane[];   // read from HBM once; each thread re-reads only what it wrote
@@ -343,40 +384,26 @@ __global__ __launch_bounds__(256) void plane_entropy_kernel(const float* __restr
     }
     const float* src = plane;
     const int step = (HW & 3) == 0 ? 4 : 1;            // pass 2 walks the elements this thread staged
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    block4_put(sh, wave_sum(s));
     __syncthreads();
-    const float total = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+    const float total = (float)block4_sum(sh);
     __syncthreads();
     double e = 0.0;
-    for (int i0 = threadIdx.x * step; i0 < HW; i0 += 256 * step) {
-        for (int i = i0; i < i0 + step; ++i) {
-            const float p = src[i] / total;
-            float t;
-            if (p > 0.f) t = -p * logf(p);
-            else if (p == 0.f) t = 0.f;
-            else if (p < 0.f) t = -INFINITY;
-            else t = p;                                         // nan
-            e += (double)t;
-        }
-    }
-    e = wave_sum(e);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = e;
+    for (int i0 = threadIdx.x * step; i0 < HW; i0 += 256 * step)
+        for (int i = i0; i < i0 + step; ++i) e += (double)entr(src[i] / total);
+    block4_put(sh, wave_sum(e));
     __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)block4_sum(sh);
 }
 
-// Same arithmetic with one WAVE per plane and the plane held in registers (NV float4 per lane, all loads in flight at once, no
-// LDS, no block barrier): used when the plane is exactly 64 * NV float4 (64x48 -> NV = 12, 96x72 -> NV = 27).
+// one wave per plane (scorer_common.h): same arithmetic
 template <int NV>
 __global__ __launch_bounds__(256) void plane_entropy_wave_kernel(const float* __restrict__ hm, float* __restrict__ out, int planes) {
     const int lane = threadIdx.x & 63;
-    const long long plane = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long long plane = wave_plane();
     if (plane >= planes) return;
-    const f32x4* src = reinterpret_cast<const f32x4*>(hm + plane * (64LL * NV * 4)) + lane;
     f32x4 v[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = src[k * 64];
+    load_plane<NV>(hm + plane * (64LL * NV * 4), lane, v);
     double s = 0.0;
 #pragma unroll
     for (int k = 0; k < NV; ++k) s += ((double)v[k][0] + (double)v[k][1]) + ((double)v[k][2] + (double)v[k][3]);
@@ -385,58 +412,40 @@ __global__ __launch_bounds__(256) void plane_entropy_wave_kernel(const float* __
 #pragma unroll
     for (int k = 0; k < NV; ++k)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float p = v[k][c] / total;
-            float t;
-            if (p > 0.f) t = -p * logf(p);
-            else if (p == 0.f) t = 0.f;
-            else if (p < 0.f) t = -INFINITY;
-            else t = p;                                         // nan
-            e += (double)t;
-        }
+        for (int c = 0; c < 4; ++c) e += (double)entr(v[k][c] / total);
     e = wave_sum(e);
     if (lane == 0) out[plane] = (float)e;
-}
-
-// compute_OKS (al_metric.py:42-69): one thread per item, float64 like the numpy original.
-__global__ void oks_kernel(const float* __restrict__ pred, const double* __restrict__ gt, const double* __restrict__ bbox_xywh,
-                           double* __restrict__ out, int N) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    const double sig[17] = {.026, .025, .025, .035, .035, .079, .079, .072, .072, .062, .062, .107, .107, .087, .087, .089, .089};
-    const double bx = bbox_xywh[4 * i], by = bbox_xywh[4 * i + 1], bw = bbox_xywh[4 * i + 2], bh = bbox_xywh[4 * i + 3];
-    const double area = bw * bh + 2.220446049250313e-16;                  // np.spacing(1)
-    const float* d = pred + (long long)i * 51;
-    const double* g = gt + (long long)i * 51;
-    bool any_vis = false;
-    for (int k = 0; k < 17; ++k) any_vis |= g[3 * k + 2] > 0.0;
-    double acc = 0.0; int cnt = 0;
-    for (int k = 0; k < 17; ++k) {
-        const double xd = (double)d[3 * k], yd = (double)d[3 * k + 1];
-        double dx, dy;
-        if (any_vis) {
-            if (!(g[3 * k + 2] > 0.0)) continue;
-            dx = xd - g[3 * k]; dy = yd - g[3 * k + 1];
-        } else {
-            dx = fmax(0.0, (bx - bw) - xd) + fmax(0.0, xd - (bx + 2 * bw));
-            dy = fmax(0.0, (by - bh) - yd) + fmax(0.0, yd - (by + 2 * bh));
-        }
-        const double var = (sig[k] * 2) * (sig[k] * 2);
-        acc += exp(-((dx * dx + dy * dy) / var / area * 0.5));
-        ++cnt;
-    }
-    out[i] = acc / (double)cnt;
 }
 
 }  // namespace vatl
 
 using namespace vatl;
 
-extern "C" int vatl_oks(const float* pred_kpts, const double* gt_kpts, const double* bbox_xywh, double* out, int N, void* stream) {
+extern "C" int vatl_thc_pairs(const float* a, const float* b, int64_t stride_a, int64_t stride_b, float* out,
+                              int P, int J, int HW, int norm, void* stream) {
+    if (norm != 1 && norm != 2) return fail(VATL_EINVAL, "thc_pairs: norm must be 1 (L1) or 2 (L2)");
+    if (P <= 0) return 0;
+    if (!a || !b || !out) return fail(VATL_EINVAL, "thc_pairs: null pointer");
+    if (((uintptr_t)a | (uintptr_t)b) & 15 || (stride_a & 3) || (stride_b & 3))
+        return fail(VATL_EINVAL, "thc_pairs: operands must be 16-byte aligned");
+    if (norm == 1) hipLaunchKernelGGL(thc_pairs_kernel<1>, dim3(P), dim3(256), 0, (hipStream_t)stream, a, b, (long long)stride_a, (long long)stride_b, out, J, J * HW);
+    else           hipLaunchKernelGGL(thc_pairs_kernel<2>, dim3(P), dim3(256), 0, (hipStream_t)stream, a, b, (long long)stride_a, (long long)stride_b, out, J, J * HW);
+    return check_launch("thc_pairs");
+}
+
+extern "C" int vatl_thc_combine(const float* pair, const uint8_t* is_prev, const uint8_t* is_next, float* thc, int N, void* stream) {
     if (N <= 0) return 0;
-    if (!pred_kpts || !gt_kpts || !bbox_xywh || !out) return fail(VATL_EINVAL, "oks: null pointer");
-    hipLaunchKernelGGL(oks_kernel, dim3((unsigned)((N + 127) / 128)), dim3(128), 0, (hipStream_t)stream, pred_kpts, gt_kpts, bbox_xywh, out, N);
-    return check_launch("oks");
+    if (!is_prev || !is_next || !thc || (N > 1 && !pair)) return fail(VATL_EINVAL, "thc_combine: null pointer");
+    hipLaunchKernelGGL(thc_combine_kernel, dim3(cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, pair, is_prev, is_next, thc, N);
+    return check_launch("thc_combine");
+}
+
+extern "C" int vatl_tpc_stream(const float* cur, const float* adj_prev, const float* adj_next, const float* bbox,
+                               const uint8_t* is_prev, const uint8_t* is_next, float* tpc, int N, int J, void* stream) {
+    if (N <= 0) return 0;
+    if (!cur || !bbox || !is_prev || !is_next || !tpc || (N > 1 && (!adj_prev || !adj_next))) return fail(VATL_EINVAL, "tpc_stream: null pointer");
+    hipLaunchKernelGGL(tpc_stream_kernel, dim3(cdiv(N, 128)), dim3(128), 0, (hipStream_t)stream, cur, adj_prev, adj_next, bbox, is_prev, is_next, tpc, N, J);
+    return check_launch("tpc_stream");
 }
 
 extern "C" int vatl_peaks5(const float* hm, float* peak_val, int32_t* peak_idx, int32_t* npeaks, float* mpe, float* margin,
@@ -462,9 +471,9 @@ extern "C" int vatl_plane_entropy(const float* hm, float* out, int N, int J, int
     const size_t smem = (size_t)H * W * sizeof(float);
     if (smem > 60 * 1024) return fail(VATL_EINVAL, "plane_entropy: heat-map %dx%d too large for the LDS tile", H, W);
     const long long planes = (long long)N * J;
-    const bool aligned = (((uintptr_t)hm) & 15) == 0;
-    if (aligned && H * W == 64 * 12 * 4) hipLaunchKernelGGL(plane_entropy_wave_kernel<12>, dim3(cdiv(planes, 4)), dim3(256), 0, (hipStream_t)stream, hm, out, (int)planes);
-    else if (aligned && H * W == 64 * 27 * 4) hipLaunchKernelGGL(plane_entropy_wave_kernel<27>, dim3(cdiv(planes, 4)), dim3(256), 0, (hipStream_t)stream, hm, out, (int)planes);
+    const int nv = wave_route_nv(hm, planes, H, W);
+    if (nv == 12) hipLaunchKernelGGL(plane_entropy_wave_kernel<12>, dim3(cdiv(planes, 4)), dim3(256), 0, (hipStream_t)stream, hm, out, (int)planes);
+    else if (nv == 27) hipLaunchKernelGGL(plane_entropy_wave_kernel<27>, dim3(cdiv(planes, 4)), dim3(256), 0, (hipStream_t)stream, hm, out, (int)planes);
     else hipLaunchKernelGGL(plane_entropy_kernel, dim3((unsigned)(N * J)), dim3(256), smem, (hipStream_t)stream, hm, out, H * W);
     return check_launch("plane_entropy");
 }
