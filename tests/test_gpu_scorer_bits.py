@@ -1,13 +1,18 @@
-"""The scorer kernels (csrc/decode.hip, localpeak.hip, heatmap_criteria.hip, pose_feature.hip) against tests/golden/scorer_bits.npz: the
-bits the library of the commit before they were re-cut by family wrote for the cases of tests/scorer_cases.py (tools/make_scorer_bits.py,
-tests/golden/README.md).  Their contract with the reference is exactness — integer results, HP, decoded coordinates — so any moved bit
-is a failure, whatever moved it."""
+"""Kernels whose bits are pinned to what the library of the commit before a refactor wrote (tools/make_scorer_bits.py, tests/golden/README.md):
+  tests/scorer_cases.py  tests/golden/scorer_bits.npz  the scorer kernels (csrc/decode.hip, localpeak.hip, heatmap_criteria.hip, pose_feature.hip).
+                         Their contract with the reference is exactness — integer results, HP, decoded coordinates.
+  tests/glue_cases.py    tests/golden/glue_bits.npz    the HBM-bound passes of the fine-tune step (csrc/layout.hip, pool.hip, fusion.hip, pack.hip,
+                         bn_train.hip): the fused stem tail relies on the pool kernels agreeing bit for bit, and the step on being reproducible.
+Any moved bit is a failure, whatever moved it."""
 import numpy as np
 import pytest
 
-from tests import scorer_cases
+from tests import glue_cases, scorer_cases
 
 pytestmark = pytest.mark.gpu
+
+MODULES = (scorer_cases, glue_cases)
+assert not set(scorer_cases.CASES) & set(glue_cases.CASES)
 
 
 @pytest.fixture(scope="module")
@@ -19,20 +24,21 @@ def vh():
 
 @pytest.fixture(scope="module")
 def golden_bits():
-    return np.load(scorer_cases.GOLDEN)
+    return {m: np.load(m.GOLDEN) for m in MODULES}
 
 
 def test_fixture_holds_exactly_the_cases(golden_bits):
-    have = {k.rsplit(".", 1)[0] for k in golden_bits.files if k != "parent_commit"}
-    assert have == set(scorer_cases.CASES), sorted(have ^ set(scorer_cases.CASES))
+    for m in MODULES:
+        have = {k.rsplit(".", 1)[0] for k in golden_bits[m].files if k != "parent_commit"}
+        assert have == set(m.CASES), (m.__name__, sorted(have ^ set(m.CASES)))
 
 
-@pytest.mark.parametrize("name", list(scorer_cases.CASES))
-def test_bits_are_the_recorded_ones(vh, golden_bits, name):
-    got = scorer_cases.run(vh, name)
+@pytest.mark.parametrize("cases,name", [pytest.param(m, name, id=name) for m in MODULES for name in m.CASES])
+def test_bits_are_the_recorded_ones(vh, golden_bits, cases, name):
+    got = cases.run(vh, name)
     assert got, name
     for key, have in got.items():
-        want = golden_bits[key]
+        want = golden_bits[cases][key]
         assert have.dtype == want.dtype and have.shape == want.shape, (key, have.dtype, have.shape, want.dtype, want.shape)
         bad = np.flatnonzero(have.reshape(-1) != want.reshape(-1))
         print(f"{key}: {bad.size} of {want.size} stored words differ", bad[:8])

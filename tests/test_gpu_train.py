@@ -556,6 +556,83 @@ def test_one_launch_weight_repack_plan_equals_per_tensor_packs(vh, name, monkeyp
     assert plan.stale
 
 
+def _expect_conv_pack(vh, w):
+    cout, cin, r, s = w.shape
+    spad, cinpad = (8, 4) if cin == 3 else (s, cin)
+    out = np.zeros((vh.conv_cout_pad(cout), r, spad, cinpad), np.float32)
+    out[:cout, :, :s, :cin] = w.transpose(0, 2, 3, 1)
+    return out
+
+
+def _expect_deconv_pack(vh, w):
+    cin, cout = w.shape[:2]
+    out = np.zeros((4, vh.conv_cout_pad(cout), 2, 2, cin), np.float32)
+    for ph in range(4):
+        for ty in range(2):
+            for tx in range(2):
+                out[ph, :cout, ty, tx, :] = w[:, :, 3 - (ph >> 1) - 2 * ty, 3 - (ph & 1) - 2 * tx].T
+    return out
+
+
+def _expect_dgrad_pack(vh, w, taps):
+    cout, cin = w.shape[:2]
+    out = np.zeros((vh.conv_cout_pad(cin), len(taps), cout), np.float32)
+    for t, (r, s) in enumerate(taps):
+        out[:cin, t, :] = w[:, :, r, s].T
+    return out
+
+
+_FLIPPED9 = [(2 - r, 2 - s) for r in range(3) for s in range(3)]
+PACK_CASES = {  # name: (weight shape, pack call, expected)
+    "conv3x3": ((5, 6, 3, 3), lambda vh, w: vh.pack_conv_weight(w), _expect_conv_pack),
+    "conv7x7_stem": ((5, 3, 7, 7), lambda vh, w: vh.pack_conv_weight(w), _expect_conv_pack),
+    "deconv": ((6, 5, 4, 4), lambda vh, w: vh.pack_deconv_weight(w), _expect_deconv_pack),
+    "dgrad_1tap": ((33, 34, 1, 1), lambda vh, w: vh.pack_dgrad_weight(w, [(0, 0)]), lambda vh, w: _expect_dgrad_pack(vh, w, [(0, 0)])),
+    "dgrad_4taps": ((33, 34, 3, 3), lambda vh, w: vh.pack_dgrad_weight(w, [(0, 0), (0, 2), (2, 0), (2, 2)]),
+                    lambda vh, w: _expect_dgrad_pack(vh, w, [(0, 0), (0, 2), (2, 0), (2, 2)])),
+    "dgrad_9flipped": ((33, 34, 3, 3), lambda vh, w: vh.pack_dgrad_weight(w, _FLIPPED9), lambda vh, w: _expect_dgrad_pack(vh, w, _FLIPPED9)),
+}
+
+
+@pytest.mark.parametrize("name", list(PACK_CASES))
+def test_weight_pack_layouts_exact_per_tensor_and_planned(vh, name):
+    """Every packed layout is a copy of the weights to fixed places, zeros elsewhere: the per-tensor entry point and the table-driven
+    launch behind a PackPlan holding the same job (csrc/pack.hip: one index formula for both) must give exactly the numpy expression."""
+    shape, pack, expect = PACK_CASES[name]
+    w_host = np.random.RandomState(len(name)).standard_normal(shape).astype(np.float32)
+    want = expect(vh, w_host)
+    w = to_dev(w_host)
+    assert vh.set_pack_plan(None) is None
+    single = pack(vh, w)
+    assert tuple(single.shape) == want.shape and np.array_equal(single.cpu().numpy(), want)
+    plan = vh.PackPlan()
+    vh.set_pack_plan(plan)
+    try:
+        plan.begin()
+        kept = pack(vh, w)                                   # recorded
+        plan.seal()
+        assert plan.ready and len(plan.jobs) == 1 and plan.total_blocks > 0
+        kept.fill_(float("nan"))
+        plan.begin()                                         # the one launch refreshes the kept buffer
+        again = pack(vh, w)
+        assert again.data_ptr() == kept.data_ptr() and not plan.stale
+        assert np.array_equal(again.cpu().numpy(), want)
+    finally:
+        vh.set_pack_plan(None)
+
+
+def test_dual_1x1_weight_pack_exact(vh):
+    r = np.random.RandomState(8)
+    c1, c2, cout = 8, 4, 5
+    w1, w2 = r.standard_normal((cout, c1, 1, 1)).astype(np.float32), r.standard_normal((cout, c2, 1, 1)).astype(np.float32)
+    s1, b1, s2, b2 = (r.standard_normal(cout).astype(np.float32) for _ in range(4))
+    out, bias = vh.pack_conv1x1_dual_weight(*(to_dev(a) for a in (w1, s1, b1, w2, s2, b2)))
+    want = np.zeros((vh.conv_cout_pad(cout), c1 + c2), np.float32)
+    want[:cout, :c1] = w1[:, :, 0, 0] * s1[:, None]
+    want[:cout, c1:] = w2[:, :, 0, 0] * s2[:, None]
+    assert np.array_equal(out.cpu().numpy(), want) and np.array_equal(bias.cpu().numpy(), b1 + b2)
+
+
 def test_fine_tune_step_is_bitwise_reproducible(vh):
     """No atomics anywhere in the step (weight gradients are reduced over pixel splits in a fixed order, BN statistics
     and the loss through ordered partials): two runs of forward + backward give identical bits for every gradient."""

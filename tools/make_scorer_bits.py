@@ -1,14 +1,18 @@
-"""Writes tests/golden/scorer_bits.npz: the bits the PARENT commit's library gives for the cases of tests/scorer_cases.py.
+"""Writes a bit fixture under tests/golden/: the bits the PARENT commit's library gives for the cases of a cases module.
 
-    VATL_HIP_LIB=/path/to/parent/libvatl_hip.so python tools/make_scorer_bits.py <parent commit hash> [out.npz]
+    VATL_HIP_LIB=/path/to/parent/libvatl_hip.so python tools/make_scorer_bits.py <parent commit hash> [out.npz] [--cases tests.glue_cases]
 
-Run on the MI355X against a library built from the commit BEFORE a change to the scorer kernels (csrc/decode.hip, localpeak.hip,
-heatmap_criteria.hip, pose_feature.hip, scorer_common.h), never against the tree's own library: the fixture exists so that a change
-of their arithmetic — a compiler upgrade, an edit — shows as a failure of tests/test_gpu_scorer_bits.py.  The parent library can be
-cross-compiled on a host without a GPU (git worktree add ../parent <hash>; python ../parent/vatl4pose-wacv2024_amd/build.py) and carried
-to the GPU box.  The hash is stored as given (`parent_commit`): the tool cannot tell which commit a library was built from, so it is
+A cases module has ``CASES`` (name -> case), ``GOLDEN`` (the fixture's path) and ``run(vatl_hip, name) -> {key: bits}``.  There are two:
+  tests.scorer_cases (the default)  tests/golden/scorer_bits.npz   csrc/decode.hip, localpeak.hip, heatmap_criteria.hip, pose_feature.hip, scorer_common.h
+  tests.glue_cases                  tests/golden/glue_bits.npz     csrc/layout.hip, pool.hip, fusion.hip, pack.hip (bn_fold), bn_train.hip, glue_common.h
+
+Run on the MI355X against a library built from the commit BEFORE a change to those kernels, never against the tree's own library: the
+fixture exists so that a change of their arithmetic — a compiler upgrade, an edit — shows as a failure of tests/test_gpu_scorer_bits.py.
+The parent library can be cross-compiled on a host without a GPU (git worktree add ../parent <hash>; python ../parent/vatl4pose-wacv2024_amd/build.py)
+and carried to the GPU box.  The hash is stored as given (`parent_commit`): the tool cannot tell which commit a library was built from, so it is
 the word of whoever ran it, as in make_optim_bits.py.  Outputs only: float32 / float64 as uint32 / uint64 bit patterns, masks as packed bits, integers raw.
 """
+import importlib
 import os
 import sys
 
@@ -17,24 +21,31 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "vatl4pose-wacv2024_amd")]
 
+argv = sys.argv[1:]
+module = "tests.scorer_cases"
+if "--cases" in argv:
+    k = argv.index("--cases")
+    module = argv[k + 1]
+    del argv[k:k + 2]
 if not os.environ.get("VATL_HIP_LIB"):
     sys.exit("make_scorer_bits: set VATL_HIP_LIB to the parent commit's libvatl_hip.so (see the docstring)")
-if len(sys.argv) < 2:
+if not argv:
     sys.exit(__doc__)
 
 import vatl_hip as vh  # noqa: E402
-from tests.scorer_cases import CASES, GOLDEN, run  # noqa: E402
+
+cases = importlib.import_module(module)
 
 
 def main():
-    out = {"parent_commit": np.array(sys.argv[1])}
-    for name in CASES:
-        got = run(vh, name)
+    out = {"parent_commit": np.array(argv[0])}
+    for name in cases.CASES:
+        got = cases.run(vh, name)
         out.update(got)
         print(name, {k.rsplit(".", 1)[1]: (v.dtype.name, v.shape) for k, v in got.items()})
-    path = sys.argv[2] if len(sys.argv) > 2 else GOLDEN
+    path = argv[1] if len(argv) > 1 else cases.GOLDEN
     np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes,", len(CASES), "cases, library", vh.LIB_PATH)
+    print("wrote", path, os.path.getsize(path), "bytes,", len(cases.CASES), "cases of", module, "library", vh.LIB_PATH)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 // One element of the F(2x2, 3x3) filter transform U = G g G^T, shared by the dedicated pack kernel (conv_winograd.hip) and the
-// table-driven multi-pack launch (layout.hip) so that both produce the same bits.  Computed in double, rounded once.
+// table-driven multi-pack launch (pack.hip) so that both produce the same bits.  Computed in double, rounded once.
 #pragma once
 
 namespace vatl {
