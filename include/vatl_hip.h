@@ -50,7 +50,7 @@ int vatl_flop_meter_end(double* direct_flops, double* winograd_flops, int64_t* d
  * BatchNorm-backward epilogue, ...) instead of trusting the dispatch rules. */
 #define VATL_ROUTE_NAMES "igemm,igemm_bnbwd,igemm_dma,persistent_1x1,streamk,rows_1x1,bottleneck_chain,stem_pool,halo_3x3," \
                          "winograd,winograd_2h,winograd_bnbwd,winograd_persist,winograd_c32,wgrad,winograd_wgrad,winograd_wgrad_2h," \
-                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring"
+                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43"
 int vatl_flop_meter_routes(int64_t* counts, int n);
 
 /* ------------------------------------------------------------------------ *
@@ -677,6 +677,17 @@ int64_t vatl_winograd_deconv_weight_floats(int Cout, int Cin);
 int vatl_pack_winograd_deconv_weight(const float* w, float* u, int Cout, int Cin, void* stream);
 int vatl_deconv4x4s2_winograd_fwd(const float* x, const float* u, const float* scale, const float* bias, float* y, int N, int H, int W,
                                   int Cin, int Cout, int relu, void* stream);
+/* The same layer as F(4x3, 2x2) (csrc/winograd_deconv43.hip, inference only): a 4-row x 3-column tile of phase outputs from a 5x4 input
+ * tile — 20 multiplies per 12 outputs instead of 16 per 9, and tiles that cover grids of H % 4 == 0, W % 3 == 0 (8x6, 16x12, 32x24)
+ * without padding.  Vertical transform on the points (0, 1, -1, 2, inf), horizontal transform that of F(3x3, 2x2); about twice the
+ * rounding error of F(3x3, 2x2), a crop's bits do not depend on its batch position.  u: vatl_winograd_deconv43_weight_floats(Cout, Cin)
+ * floats = four phase filters of 20 positions in the fragment order of vatl_pack_winograd_deconv_weight.  _supported: 1 for
+ * H % 4 == 0, W % 3 == 0, Cin % 16 == 0, Cout % 64 == 0 and tensors within 32-bit byte offsets, else 0 (_fwd fails on those). */
+int64_t vatl_winograd_deconv43_weight_floats(int Cout, int Cin);
+int vatl_pack_winograd_deconv43_weight(const float* w, float* u, int Cout, int Cin, void* stream);
+int vatl_deconv4x4s2_winograd43_supported(int N, int H, int W, int Cin, int Cout);
+int vatl_deconv4x4s2_winograd43_fwd(const float* x, const float* u, const float* scale, const float* bias, float* y, int N, int H, int W,
+                                    int Cin, int Cout, int relu, void* stream);
 int64_t vatl_winograd_deconv_stats_row_blocks(int64_t N, int H, int W);
 int vatl_deconv4x4s2_winograd_fwd_stats(const float* x, const float* u, float* y, double* stats, int64_t* row_blocks_used, int N, int H, int W,
                                         int Cin, int Cout, void* stream);

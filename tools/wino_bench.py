@@ -2,6 +2,7 @@
 """Winograd F(2x2,3x3) route against the implicit GEMM on the 3x3 / stride-1 layer shapes: error against float64 and time.
 
     python tools/wino_bench.py [--batch 1024] [--iters 5] [--layers l1.c2,...] [--check 8]
+    python tools/wino_bench.py --deconv43 --iters 10        # the transposed convs: F(3x3,2x2) against F(4x3,2x2)
 
 For every shape: max |error| of both routes against a float64 convolution (on `--check` crops), then `iters` launches of
 each route between HIP events (TFLOP/s are algorithmic = direct-convolution FLOPs for both).
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--group-kb", type=int, default=-1, help="vatl_tune_set(18, v): KB of filter slices per group of the Winograd tile order")
     ap.add_argument("--halves", type=int, default=0, help="vatl_tune_set(21, v): 32-channel filter halves per Winograd block (1, or 2 where the layer allows)")
     ap.add_argument("--persist", type=int, default=-1, help="vatl_tune_set(22, v): layers with at most v 16-channel stages take the persistent Winograd route (0 = never)")
+    ap.add_argument("--deconv43", action="store_true", help="deconv layers only: F(3x3,2x2) against F(4x3,2x2) (csrc/winograd_deconv43.hip), median of 3 alternating loops of --iters launches")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.persist >= 0:
@@ -57,8 +59,36 @@ def main():
         warm @ warm
     torch.cuda.synchronize()
     g = torch.Generator(device="cpu").manual_seed(5)
-    names = a.layers.split(",") if a.layers else list(SHAPES) + list(DECONVS)
+    names = a.layers.split(",") if a.layers else ([] if a.deconv43 else list(SHAPES)) + list(DECONVS)
     for name in names:
+        if name in DECONVS and a.deconv43:
+            h, w, cin, cout = DECONVS[name]
+            b = a.batch
+            x = torch.randn((b, h, w, cin), generator=g).to(dev)
+            wt = (torch.randn((cin, cout, 4, 4), generator=g) * (2.0 / (4 * cin)) ** 0.5).to(dev)
+            sc = (torch.rand(cout, generator=g) + 0.5).to(dev)
+            bi = torch.randn(cout, generator=g).to(dev)
+            up, u43 = vh.pack_winograd_deconv_weight(wt), vh.pack_winograd_deconv43_weight(wt)
+            if not vh.deconv4x4s2_winograd43_supported(b, h, w, cin, cout):
+                print(f"{name:11s} B={b:5d} not a shape of the F(4x3,2x2) route", flush=True)
+                continue
+            out = torch.empty((b, 2 * h, 2 * w, cout), device=dev)
+            y33 = vh.deconv4x4s2_winograd_fwd(x, up, sc, bi, cout, True)
+            y43 = vh.deconv4x4s2_winograd_fwd(x, up, sc, bi, cout, True, out=out, u43=u43)
+            k = min(a.check, b)
+            ref = torch.nn.functional.conv_transpose2d(x[:k].permute(0, 3, 1, 2).double(), wt.double(), None, 2, 1) * sc.double().view(1, -1, 1, 1) + bi.double().view(1, -1, 1, 1)
+            ref = ref.clamp_min(0).permute(0, 2, 3, 1)
+            e33, e43 = (y33[:k].double() - ref).abs().max().item(), (y43[:k].double() - ref).abs().max().item()
+            full = (y33 - y43).abs().max().item()
+            del y33
+            t33, t43 = [], []
+            for _ in range(3):
+                t33.append(timed(lambda: vh.deconv4x4s2_winograd_fwd(x, up, sc, bi, cout, True, out=out), a.iters))
+                t43.append(timed(lambda: vh.deconv4x4s2_winograd_fwd(x, up, sc, bi, cout, True, out=out, u43=u43), a.iters))
+            m33, m43 = sorted(t33)[1], sorted(t43)[1]
+            print(f"{name:11s} B={b:5d} F(3x3,2x2) {m33:8.1f} us err {e33:.2e} | F(4x3,2x2) {m43:8.1f} us err {e43:.2e} | max |difference| {full:.2e}  ref max {ref.abs().max().item():.2f}  "
+                  f"speed-up {m33 / m43:.3f}x  loops {' '.join(f'{v:.1f}' for v in t33)} / {' '.join(f'{v:.1f}' for v in t43)}", flush=True)
+            continue
         if name in DECONVS:
             h, w, cin, cout = DECONVS[name]
             b = a.batch

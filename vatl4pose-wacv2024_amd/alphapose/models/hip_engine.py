@@ -58,6 +58,10 @@ WINO_C32 = True
 # 128-channel branches, the DUC convs) as Winograd F(4x4,3x3) (csrc/winograd_f4.hip: 0.5625x the multiplies of F(2x2); measured 1.17 - 1.47x at 1024 crops, tools/f4_bench.py).
 # Geometry-only choice like WINOGRAD: a crop's bits do not depend on its batch.  False = the F(2x2) route (same values to fp32 rounding, not the same bits).
 WINO_F4 = True
+# Transposed convs on grids of whole 4x3 tiles (H % 4 == 0, W % 3 == 0: the 8x6 / 16x12 / 32x24 of the 256x192 heads), Cout a multiple of 64, as Winograd
+# F(4x3,2x2) (csrc/winograd_deconv43.hip: 20 multiplies per 12 outputs and no padded tiles, against 16 per 9 of F(3x3,2x2)).  Geometry-only choice like WINOGRAD.
+# False = the F(3x3,2x2) route (same values to fp32 rounding, not the same bits).
+DECONV_43 = True
 
 
 class _Conv:
@@ -107,12 +111,14 @@ class _Conv:
 
 
 class _Deconv:
-    __slots__ = ("w", "u", "scale", "bias", "cout")
+    __slots__ = ("w", "u", "u43", "wsrc", "d43", "scale", "bias", "cout")
 
     def __init__(self, dc: nn.ConvTranspose2d, bn: nn.BatchNorm2d):
         assert dc.kernel_size == (4, 4) and dc.stride == (2, 2) and dc.padding == (1, 1) and dc.bias is None
         self.cout = dc.weight.shape[1]
-        self.u = None
+        self.u = self.u43 = None
+        self.d43 = WINOGRAD and DECONV_43 and dc.weight.shape[0] % 16 == 0 and self.cout % 64 == 0
+        self.wsrc = dc.weight.detach() if self.d43 else None      # the F(4x3,2x2) filter is packed on the first call that takes its route (see _Conv)
         if WINOGRAD and dc.weight.shape[0] % 16 == 0 and self.cout % 4 == 0:     # four 2x2 phase convolutions as Winograd F(3x3, 2x2)
             self.u = vh.pack_winograd_deconv_weight(dc.weight.detach())
         self.w = vh.pack_deconv_weight(dc.weight.detach())                      # the implicit GEMM serves the small-batch module calls
@@ -120,7 +126,9 @@ class _Deconv:
 
     def __call__(self, x, relu=True):
         if self.u is not None and not vh.latency_mode():
-            return vh.deconv4x4s2_winograd_fwd(x, self.u, self.scale, self.bias, self.cout, relu)
+            if self.d43 and self.u43 is None and vh.deconv4x4s2_winograd43_supported(x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.cout):
+                self.u43 = vh.pack_winograd_deconv43_weight(self.wsrc)
+            return vh.deconv4x4s2_winograd_fwd(x, self.u, self.scale, self.bias, self.cout, relu, u43=self.u43)
         return vh.deconv4x4s2_fwd(x, self.w, self.scale, self.bias, self.cout, relu)
 
 

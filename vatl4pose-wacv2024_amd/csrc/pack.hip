@@ -111,6 +111,12 @@ __global__ void bn_fold_kernel(const float* gamma, const float* beta, const floa
     bias[c] = b;
 }
 
+// F(4x3,2x2) phase filters of ConvTranspose2d(4,2,1) (winograd_pack.h).  Inference only: the plans pack it once per weight version, so it has
+// no kind in the table-driven launch below.
+__global__ __launch_bounds__(256) void wino43_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin) {
+    wino43_pack_block(w, out, Cout, Cin, blockIdx.x, threadIdx.x);
+}
+
 // Every weight re-pack of a fine-tune step in ONE launch (the trainers need ~60 .. 180 packed copies per step — forward
 // layouts of the 3x3 / 7x7 / transposed convs, data-gradient layouts of every conv — and each used to be its own 5 us
 // launch).  jobs: device array sorted by first_block; a block of 256 threads makes 1024 consecutive elements of one job (kinds 0 / 2),
@@ -180,6 +186,18 @@ extern "C" int vatl_pack_deconv4x4s2_weight(const float* w, float* out, int Cin,
     if (!w || !out || CoutPad < Cout) return fail(VATL_EINVAL, "pack_deconv4x4s2_weight: bad arguments");
     hipLaunchKernelGGL(pack_deconv_weight_kernel, dim3(ew_grid(16LL * CoutPad * Cin)), dim3(256), 0, (hipStream_t)stream, w, out, Cin, Cout, CoutPad);
     return check_launch("pack_deconv4x4s2_weight");
+}
+
+// ConvTranspose2d(4, 2, 1) filter (Cin, Cout, 4, 4) -> four phase filters G4 g_phase G3^T of 20 positions each
+extern "C" int64_t vatl_winograd_deconv43_weight_floats(int Cout, int Cin) { return 4LL * 20 * Cout * Cin; }
+
+extern "C" int vatl_pack_winograd_deconv43_weight(const float* w, float* u, int Cout, int Cin, void* stream) {
+    if (!w || !u || Cout <= 0 || Cin <= 0) return fail(VATL_EINVAL, "pack_winograd_deconv43_weight: null pointer or empty filter");
+    if (Cin % 16 != 0 || Cout % 64 != 0) return fail(VATL_EINVAL, "pack_winograd_deconv43_weight: Cin %d must be a multiple of 16 and Cout %d of 64", Cin, Cout);
+    const long long blocks = 4LL * (Cout / 32) * (Cin / 8);
+    if (blocks > 0x7FFFFFFF) return fail(VATL_EINVAL, "pack_winograd_deconv43_weight: filter too large");
+    hipLaunchKernelGGL(wino43_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, u, Cout, Cin);
+    return check_launch("wino43_pack");
 }
 
 extern "C" int vatl_pack_dgrad_weight(const float* w_oihw, float* out, int Cout, int Cin, int R, int S, int CinPad, int CoutK,

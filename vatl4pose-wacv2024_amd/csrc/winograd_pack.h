@@ -79,6 +79,43 @@ __device__ __forceinline__ void wino_pack_block(const float* __restrict__ w, flo
     }
 }
 
+// F(4x3,2x2) filter transform of ConvTranspose2d(4,2,1) (csrc/winograd_deconv43.hip): U = G4 g G3^T, 5 x 4 = 20 positions per phase filter.
+// G3 = [1 0; .5 .5; .5 -.5; 0 -1] is the G of mode 2 above (horizontal, points 0, 1, -1, inf); G4 = [1/2 0; -1/2 -1/2; -1/6 1/6; 1/6 1/3; 0 1]
+// (vertical, points 0, 1, -1, 2, inf) pairs with B4^T = [2 -1 -2 1 0; 0 -2 -1 1 0; 0 2 -3 1 0; 0 -1 0 1 0; 0 2 -1 -2 1] and
+// A4^T = [1 1 1 1 0; 0 1 -1 2 0; 0 1 1 4 0; 0 1 -1 8 1] in the kernel.  Same fragment order as mode 2 with 20 positions (xi * 4 + nu) where that
+// has 16 and NH = 2 (Cout % 64 == 0): [phase][n / 64][step = c / 8][position][n / 32 % 2][lane = (c % 8 / 4) * 32 + n % 32][c % 4]; a block of 256
+// threads makes the 20 x 256 elements of (32 output channels, one 8-channel step).  u = sum_a sum_b G4[xi][a] g[a][b] G3[nu][b] in double, rounded once.
+__device__ __forceinline__ void wino43_pack_block(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, long long bl, int tid) {
+    const int steps = Cin >> 3;
+    const long long per = (long long)(Cout >> 5) * steps;             // blocks per phase filter
+    const int phase = (int)(bl / per);
+    bl -= phase * per;
+    out += phase * per * 5120;
+    const int n32 = (int)(bl / steps), step = (int)(bl - (long long)n32 * steps);
+    const int nl = tid & 31, cc = tid >> 5;
+    const int n = n32 * 32 + nl, c = step * 8 + cc;
+    const int py = phase >> 1, px = phase & 1;
+    const double G4[5][2] = {{0.5, 0.0}, {-0.5, -0.5}, {-1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3}, {0.0, 1.0}};
+    const double G3[4][2] = {{1.0, 0.0}, {0.5, 0.5}, {0.5, -0.5}, {0.0, -1.0}};
+    double g[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) g[a][b] = (double)w[(((long long)c * Cout + n) * 4 + (3 - py - 2 * a)) * 4 + (3 - px - 2 * b)];
+    float* o = out + ((((long long)((n32 >> 1) * steps + step) * 20) * 2 + (n32 & 1)) * 64 + (cc >> 2) * 32 + nl) * 4 + (cc & 3);
+#pragma unroll
+    for (int xi = 0; xi < 5; ++xi)
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+            double v = 0.0;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) v += G4[xi][a] * g[a][b] * G3[nu][b];
+            o[(long long)(xi * 4 + nu) * 512] = (float)v;
+        }
+}
+
 // One 16-byte item of the F(4x4,3x3) filter transform U = G g G^T (csrc/winograd_f4.hip), shared by its pack kernel and the table-driven multi-pack launch.
 // Fragment order [stage = c / 16][position xi * 6 + nu][column block = n / 16][lane = (c % 16 / 4) * 16 + n % 16][k-step = c % 4]; item = (stage, position, block, lane).
 // dgrad = 0: g = w[n][c] of the (Cout, Cin, 3, 3) filter (w_i = Cin); 1: the data gradient's filter g = rot180(w[o = c][i = n]) of the forward (O, I, 3, 3) filter

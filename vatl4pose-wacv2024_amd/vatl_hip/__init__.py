@@ -120,6 +120,10 @@ SIGNATURES = {
     "vatl_winograd_deconv_weight_floats": (_i64, [_i, _i]),
     "vatl_pack_winograd_deconv_weight": (_i, [_p, _p, _i, _i, _p]),
     "vatl_deconv4x4s2_winograd_fwd": (_i, [_p] * 5 + [_i] * 6 + [_p]),
+    "vatl_winograd_deconv43_weight_floats": (_i64, [_i, _i]),
+    "vatl_pack_winograd_deconv43_weight": (_i, [_p, _p, _i, _i, _p]),
+    "vatl_deconv4x4s2_winograd43_supported": (_i, [_i, _i, _i, _i, _i]),
+    "vatl_deconv4x4s2_winograd43_fwd": (_i, [_p] * 5 + [_i] * 6 + [_p]),
     "vatl_winograd_deconv_stats_row_blocks": (_i64, [_i64, _i, _i]),
     "vatl_deconv4x4s2_winograd_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_conv2d_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
@@ -262,7 +266,7 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
 
 ROUTE_NAMES = ("igemm", "igemm_bnbwd", "igemm_dma", "persistent_1x1", "streamk", "rows_1x1", "bottleneck_chain", "stem_pool", "halo_3x3", "winograd",
                "winograd_2h", "winograd_bnbwd", "winograd_persist", "winograd_c32", "wgrad", "winograd_wgrad", "winograd_wgrad_2h", "winograd_wgrad_table", "winograd_f4", "winograd_f4_bnbwd",
-               "gemm1x1_ring")
+               "gemm1x1_ring", "winograd_deconv43")
 
 
 class flop_meter:
@@ -604,6 +608,16 @@ def pack_winograd_deconv_weight(w: torch.Tensor) -> torch.Tensor:
         _winograd_fields(_PACK_WINOGRAD_DECONV, cout, cin, 4, cout)))
 
 
+def pack_winograd_deconv43_weight(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the four phase filters in the F(4x3,2x2) transform domain, 20 positions each, MFMA fragment
+    order (csrc/winograd_deconv43.hip).  Inference only: packed on the spot, never part of a PackPlan's one-launch re-pack table."""
+    cin, cout = w.shape[:2]
+    if tuple(w.shape[2:]) != (4, 4):
+        raise VatlError("pack_winograd_deconv43_weight: 4x4 filters only")
+    return _pack(("winograd_deconv43", w.data_ptr(), tuple(w.shape)), w, lambda: (
+        int(lib().vatl_winograd_deconv43_weight_floats(cout, cin)), "vatl_pack_winograd_deconv43_weight", (cout, cin), None), planned=False)
+
+
 def pack_winograd_deconv_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
     """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the filters of its DATA gradient (a 4x4 / stride 2 conv over dz = four pixel
     phases x 2x2 convolutions) in the F(3x3,2x2) transform domain."""
@@ -794,10 +808,19 @@ def deconv4x4s2_fwd(x, w_packed, scale, bias, cout: int, relu: bool):
     return y
 
 
-def deconv4x4s2_winograd_fwd(x, u_packed, scale, bias, cout: int, relu: bool, out=None):
-    """ConvTranspose2d(4,2,1) of an NHWC tensor through Winograd F(3x3, 2x2) on its four sub-pixel phases."""
+def deconv4x4s2_winograd43_supported(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    return bool(lib().vatl_deconv4x4s2_winograd43_supported(n, h, w, cin, cout))
+
+
+def deconv4x4s2_winograd_fwd(x, u_packed, scale, bias, cout: int, relu: bool, out=None, u43=None):
+    """ConvTranspose2d(4,2,1) of an NHWC tensor through Winograd F(3x3, 2x2) on its four sub-pixel phases — or, when ``u43``
+    (pack_winograd_deconv43_weight) is given and the shape is one the F(4x3, 2x2) kernel serves, through that kernel (other bits)."""
     n, h, w, cin = x.shape
     y = out if out is not None else torch.empty((n, 2 * h, 2 * w, cout), device=x.device, dtype=torch.float32)
+    if u43 is not None and deconv4x4s2_winograd43_supported(n, h, w, cin, cout):
+        _check(lib().vatl_deconv4x4s2_winograd43_fwd(_ptr(x), _ptr(u43), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
+               "vatl_deconv4x4s2_winograd43_fwd")
+        return y
     _check(lib().vatl_deconv4x4s2_winograd_fwd(_ptr(x), _ptr(u_packed), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
            "vatl_deconv4x4s2_winograd_fwd")
     return y
