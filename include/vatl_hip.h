@@ -50,7 +50,7 @@ int vatl_flop_meter_end(double* direct_flops, double* winograd_flops, int64_t* d
  * BatchNorm-backward epilogue, ...) instead of trusting the dispatch rules. */
 #define VATL_ROUTE_NAMES "igemm,igemm_bnbwd,igemm_dma,persistent_1x1,streamk,rows_1x1,bottleneck_chain,stem_pool,halo_3x3," \
                          "winograd,winograd_2h,winograd_bnbwd,winograd_persist,winograd_c32,wgrad,winograd_wgrad,winograd_wgrad_2h," \
-                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43"
+                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43,winograd_s2_43"
 int vatl_flop_meter_routes(int64_t* counts, int n);
 
 /* ------------------------------------------------------------------------ *
@@ -688,6 +688,20 @@ int vatl_pack_winograd_deconv43_weight(const float* w, float* u, int Cout, int C
 int vatl_deconv4x4s2_winograd43_supported(int N, int H, int W, int Cin, int Cout);
 int vatl_deconv4x4s2_winograd43_fwd(const float* x, const float* u, const float* scale, const float* bias, float* y, int N, int H, int W,
                                     int Cin, int Cout, int relu, void* stream);
+/* nn.Conv2d(3, stride 2, pad 1) + BN(eval) + ReLU (Bottleneck.conv2 of a stage's first block) as Winograd F(4x3, 2x2) summed over the four input
+ * phases (csrc/winograd_s2_43.hip, inference only): phase (by, bx) of the input, x[2i + by - 1][2j + bx - 1], meets the taps w[2a + by][2b + bx] of the
+ * filter padded to 4x4; all four phases add into one transform-domain accumulator set, 72 multiplies per 12 outputs against 108 of the direct sum.
+ * x (N,H,W,Cin) NHWC -> y (N,H/2,W/2,Cout) dense NHWC, y = relu?(scale * conv + bias) (scale / bias may be null), no residual.
+ * u: vatl_winograd_s2_43_weight_floats(Cout, Cin) = 72 * Cout * Cin floats from vatl_pack_winograd_s2_43_weight (w = (Cout,Cin,3,3); the two by = 1
+ * phases store 16 positions, their fifth row position is identically zero).  _supported: 1 for H % 8 == 0, W % 6 == 0 (output grid of whole 4x3
+ * tiles), Cin % 16 == 0, Cout % 64 == 0 and tensors within 32-bit byte offsets, else 0 (_fwd fails on those).  About 2.5x the rounding error of the
+ * direct sum at Cin = 512; a crop's bits do not depend on its batch position.  The flop meter books the launch's executed FLOPs,
+ * 2 * (tiles rounded up to 32) * 72 * Cin * Cout, in its DIRECT class: the call is made in place of vatl_conv2d_fwd. */
+int64_t vatl_winograd_s2_43_weight_floats(int Cout, int Cin);
+int vatl_pack_winograd_s2_43_weight(const float* w, float* u, int Cout, int Cin, void* stream);
+int vatl_conv3x3s2_winograd43_supported(int N, int H, int W, int Cin, int Cout);
+int vatl_conv3x3s2_winograd43_fwd(const float* x, const float* u, const float* scale, const float* bias, float* y, int N, int H, int W,
+                                  int Cin, int Cout, int relu, void* stream);
 int64_t vatl_winograd_deconv_stats_row_blocks(int64_t N, int H, int W);
 int vatl_deconv4x4s2_winograd_fwd_stats(const float* x, const float* u, float* y, double* stats, int64_t* row_blocks_used, int N, int H, int W,
                                         int Cin, int Cout, void* stream);

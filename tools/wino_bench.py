@@ -3,6 +3,7 @@
 
     python tools/wino_bench.py [--batch 1024] [--iters 5] [--layers l1.c2,...] [--check 8]
     python tools/wino_bench.py --deconv43 --iters 10        # the transposed convs: F(3x3,2x2) against F(4x3,2x2)
+    python tools/wino_bench.py --s2 --iters 10              # the stride-2 3x3 convs: implicit GEMM against F(4x3,2x2) over the four input phases
 
 For every shape: max |error| of both routes against a float64 convolution (on `--check` crops), then `iters` launches of
 each route between HIP events (TFLOP/s are algorithmic = direct-convolution FLOPs for both).
@@ -23,6 +24,11 @@ SHAPES = {  # name: (H, W, Cin, Cout, residual)
     "hr.b32": (64, 48, 32, 32, True), "hr.b64": (32, 24, 64, 64, True), "hr.b128": (16, 12, 128, 128, True), "hr.b256": (8, 6, 256, 256, True),
     "r152.l2.c2": (48, 36, 128, 128, False), "r152.l3.c2": (24, 18, 256, 256, False), "r152.l4.c2": (12, 9, 512, 512, False),
 }
+# 3x3 / stride 2 / pad 1 layers (H, W = input grid, Cin, Cout): layer2/3/4.0.conv2 of the 256x192 ResNets (SimplePose, FastPose), and the HRNet-W32 layers the shape
+# rule of csrc/winograd_s2_43.hip admits (stem conv2, the transitions, the fuse layers' down-sampling convs with >= 64 output channels)
+S2 = {"l2.0.c2": (64, 48, 128, 128), "l3.0.c2": (32, 24, 256, 256), "l4.0.c2": (16, 12, 512, 512)}
+S2_HR = {"hr.stem2": (128, 96, 64, 64), "hr.t1": (64, 48, 256, 64), "hr.t2": (32, 24, 64, 128), "hr.t3": (16, 12, 128, 256), "hr.f32-64": (64, 48, 32, 64),
+         "hr.f32-128": (32, 24, 32, 128), "hr.f32-256": (16, 12, 32, 256), "hr.f64-64": (32, 24, 64, 64), "hr.f64-256": (16, 12, 64, 256)}
 DECONVS = {"deconv1": (8, 6, 2048, 256), "deconv2": (16, 12, 256, 256), "deconv3": (32, 24, 256, 256)}
 
 
@@ -46,6 +52,8 @@ def main():
     ap.add_argument("--halves", type=int, default=0, help="vatl_tune_set(21, v): 32-channel filter halves per Winograd block (1, or 2 where the layer allows)")
     ap.add_argument("--persist", type=int, default=-1, help="vatl_tune_set(22, v): layers with at most v 16-channel stages take the persistent Winograd route (0 = never)")
     ap.add_argument("--deconv43", action="store_true", help="deconv layers only: F(3x3,2x2) against F(4x3,2x2) (csrc/winograd_deconv43.hip), median of 3 alternating loops of --iters launches")
+    ap.add_argument("--s2", action="store_true", help="stride-2 3x3 layers only: implicit GEMM against F(4x3,2x2) over the four input phases (csrc/winograd_s2_43.hip), "
+                    "median of 3 alternating loops of --iters launches; --layers picks from the flagship's three and the hr.* shapes (default: the flagship's)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.persist >= 0:
@@ -60,7 +68,40 @@ def main():
     torch.cuda.synchronize()
     g = torch.Generator(device="cpu").manual_seed(5)
     names = a.layers.split(",") if a.layers else ([] if a.deconv43 else list(SHAPES)) + list(DECONVS)
+    if a.s2:
+        names = (list(S2) + list(S2_HR) if a.layers == "all" else a.layers.split(",")) if a.layers else list(S2)
     for name in names:
+        if a.s2:
+            h, w, cin, cout = {**S2, **S2_HR}[name]
+            b = a.batch
+            if not vh.conv3x3s2_winograd43_supported(b, h, w, cin, cout):
+                print(f"{name:11s} B={b:5d} not a shape of the stride-2 F(4x3,2x2) route", flush=True)
+                continue
+            x = torch.randn((b, h, w, cin), generator=g).to(dev)
+            wt = (torch.randn((cout, cin, 3, 3), generator=g) * (2.0 / (9 * cin)) ** 0.5).to(dev)
+            sc = (torch.rand(cout, generator=g) + 0.5).to(dev)
+            bi = torch.randn(cout, generator=g).to(dev)
+            wp, us2 = vh.pack_conv_weight(wt), vh.pack_winograd_s2_43_weight(wt)
+            out = torch.empty((b, h // 2, w // 2, cout), device=dev)
+            yd = vh.conv2d_fwd(x, wp, sc, bi, cout, 3, 3, 2, 1, True)
+            yw = vh.conv2d_fwd(x, wp, sc, bi, cout, 3, 3, 2, 1, True, out=out, u_s2=us2)
+            k = min(a.check, b)
+            ref = torch.nn.functional.conv2d(x[:k].permute(0, 3, 1, 2).double(), wt.double(), None, 2, 1) * sc.double().view(1, -1, 1, 1) + bi.double().view(1, -1, 1, 1)
+            ref = ref.clamp_min(0).permute(0, 2, 3, 1)
+            ed, ew = (yd[:k].double() - ref).abs().max().item(), (yw[:k].double() - ref).abs().max().item()
+            full = (yd - yw).abs().max().item()
+            del yd
+            td, tw = [], []
+            for _ in range(3):
+                td.append(timed(lambda: vh.conv2d_fwd(x, wp, sc, bi, cout, 3, 3, 2, 1, True, out=out), a.iters))
+                tw.append(timed(lambda: vh.conv2d_fwd(x, wp, sc, bi, cout, 3, 3, 2, 1, True, out=out, u_s2=us2), a.iters))
+            md, mw = sorted(td)[1], sorted(tw)[1]
+            m = b * (h // 2) * (w // 2)
+            fd = 2.0 * m * 9 * cin * cout / 157.3e12 * 1e6                                      # executed-FLOP floors at the fp32 MFMA peak, us
+            fw = 2.0 * ((m // 12 + 31) // 32 * 32) * 72 * cin * cout / 157.3e12 * 1e6
+            print(f"{name:11s} B={b:5d} igemm {md:8.1f} us (floor {fd:7.1f}, {fd / md:.3f}) err {ed:.2e} | s2 F(4x3,2x2) {mw:8.1f} us (floor {fw:7.1f}, {fw / mw:.3f}) err {ew:.2e} | "
+                  f"max |difference| {full:.2e}  ref max {ref.abs().max().item():.2f}  speed-up {md / mw:.3f}x of 1.5  loops {' '.join(f'{v:.1f}' for v in td)} / {' '.join(f'{v:.1f}' for v in tw)}", flush=True)
+            continue
         if name in DECONVS and a.deconv43:
             h, w, cin, cout = DECONVS[name]
             b = a.batch

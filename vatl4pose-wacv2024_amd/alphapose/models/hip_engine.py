@@ -62,10 +62,15 @@ WINO_F4 = True
 # F(4x3,2x2) (csrc/winograd_deconv43.hip: 20 multiplies per 12 outputs and no padded tiles, against 16 per 9 of F(3x3,2x2)).  Geometry-only choice like WINOGRAD.
 # False = the F(3x3,2x2) route (same values to fp32 rounding, not the same bits).
 DECONV_43 = True
+# 3x3 / stride 2 / pad 1 layers (Bottleneck.conv2 of a stage's first block) whose output grid is whole 4x3 tiles (H % 8 == 0, W % 6 == 0: 64x48 / 32x24 / 16x12 in
+# the 256x192 networks), Cin a multiple of 16, Cout of 64, as Winograd F(4x3,2x2) summed over the four input phases (csrc/winograd_s2_43.hip: 72 multiplies per 12
+# outputs against 108 of the direct sum).  Geometry-only choice like WINOGRAD; not taken with a residual, for NCHW output or in the small-batch module call.
+# False = the implicit GEMM (same values to fp32 rounding, not the same bits).
+S2_43 = True
 
 
 class _Conv:
-    __slots__ = ("w", "u", "u32", "u4", "wsrc", "wino", "c32", "f4", "scale", "bias", "cout", "r", "s", "stride", "pad")
+    __slots__ = ("w", "u", "u32", "u4", "us2", "wsrc", "wino", "c32", "f4", "s2", "scale", "bias", "cout", "r", "s", "stride", "pad")
 
     def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d | None):
         assert conv.groups == 1 and conv.dilation == (1, 1)
@@ -81,7 +86,9 @@ class _Conv:
         self.wino = WINOGRAD and (self.r, self.s, self.stride, self.pad) == (3, 3, 1, 1) and conv.in_channels % 16 == 0 and self.cout % 4 == 0
         self.c32 = self.wino and WINO_C32 and conv.in_channels == 32 and self.cout == 32
         self.f4 = self.wino and WINO_F4 and conv.in_channels >= 64 and conv.in_channels % 16 == 0 and self.cout % 64 == 0
-        self.wsrc = conv.weight.detach() if self.wino else None
+        self.us2 = None
+        self.s2 = WINOGRAD and S2_43 and (self.r, self.s, self.stride, self.pad) == (3, 3, 2, 1) and conv.in_channels % 16 == 0 and self.cout % 64 == 0
+        self.wsrc = conv.weight.detach() if self.wino or self.s2 else None
         cb = conv.bias.detach() if conv.bias is not None else None
         if bn is not None:
             self.scale, self.bias = vh.bn_fold(_d(bn.weight), _d(bn.bias), bn.running_mean, bn.running_var, bn.eps, cb)
@@ -106,8 +113,13 @@ class _Conv:
         if (ROWS_GEMM and self.r == 1 and self.stride == 1 and not out_nchw and not vh.latency_mode() and x.shape[-1] in ROWS_GEMM_K
                 and vh.conv1x1_rows_supported(x.shape[-1], 0, self.cout, x.shape[0] * x.shape[1] * x.shape[2])):
             return vh.conv1x1_rows_fwd(x, self.w, self.scale, self.bias, self.cout, relu, residual=residual, out=out)     # K = 128 / 256, wide N: row-streaming GEMM
+        us2 = None
+        if self.s2 and residual is None and not out_nchw and not vh.latency_mode():       # stride-2 3x3: F(4x3,2x2) over the four input phases, inside conv2d_fwd
+            if self.us2 is None and vh.conv3x3s2_winograd43_supported(x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.cout):
+                self.us2 = vh.pack_winograd_s2_43_weight(self.wsrc)
+            us2 = self.us2
         return vh.conv2d_fwd(x, self.w, self.scale, self.bias, self.cout, self.r, self.s, self.stride, self.pad, relu,
-                             residual=residual, out_nchw=out_nchw, out=out)
+                             residual=residual, out_nchw=out_nchw, out=out, u_s2=us2)
 
 
 class _Deconv:

@@ -117,6 +117,11 @@ __global__ __launch_bounds__(256) void wino43_pack_kernel(const float* __restric
     wino43_pack_block(w, out, Cout, Cin, blockIdx.x, threadIdx.x);
 }
 
+// F(4x3,2x2) phase filters of the 3x3 / stride 2 conv (winograd_pack.h), inference only like the one above.
+__global__ __launch_bounds__(256) void wino_s2_43_pack_kernel(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin) {
+    wino_s2_43_pack_block(w, out, Cout, Cin, blockIdx.x, threadIdx.x);
+}
+
 // Every weight re-pack of a fine-tune step in ONE launch (the trainers need ~60 .. 180 packed copies per step — forward
 // layouts of the 3x3 / 7x7 / transposed convs, data-gradient layouts of every conv — and each used to be its own 5 us
 // launch).  jobs: device array sorted by first_block; a block of 256 threads makes 1024 consecutive elements of one job (kinds 0 / 2),
@@ -198,6 +203,18 @@ extern "C" int vatl_pack_winograd_deconv43_weight(const float* w, float* u, int 
     if (blocks > 0x7FFFFFFF) return fail(VATL_EINVAL, "pack_winograd_deconv43_weight: filter too large");
     hipLaunchKernelGGL(wino43_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, u, Cout, Cin);
     return check_launch("wino43_pack");
+}
+
+// 3x3 / stride 2 / pad 1 filter (Cout, Cin, 3, 3) -> its four input-phase filters G4 g_phase G3^T: 20 positions for the two by = 0 phases, 16 for the two by = 1
+extern "C" int64_t vatl_winograd_s2_43_weight_floats(int Cout, int Cin) { return 72LL * Cout * Cin; }
+
+extern "C" int vatl_pack_winograd_s2_43_weight(const float* w, float* u, int Cout, int Cin, void* stream) {
+    if (!w || !u || Cout <= 0 || Cin <= 0) return fail(VATL_EINVAL, "pack_winograd_s2_43_weight: null pointer or empty filter");
+    if (Cin % 16 != 0 || Cout % 64 != 0) return fail(VATL_EINVAL, "pack_winograd_s2_43_weight: Cin %d must be a multiple of 16 and Cout %d of 64", Cin, Cout);
+    const long long blocks = 4LL * (Cout / 32) * (Cin / 8);
+    if (blocks > 0x7FFFFFFF) return fail(VATL_EINVAL, "pack_winograd_s2_43_weight: filter too large");
+    hipLaunchKernelGGL(wino_s2_43_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, u, Cout, Cin);
+    return check_launch("wino_s2_43_pack");
 }
 
 extern "C" int vatl_pack_dgrad_weight(const float* w_oihw, float* out, int Cout, int Cin, int R, int S, int CinPad, int CoutK,

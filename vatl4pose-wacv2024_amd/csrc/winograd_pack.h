@@ -116,6 +116,48 @@ __device__ __forceinline__ void wino43_pack_block(const float* __restrict__ w, f
         }
 }
 
+// F(4x3,2x2) filter transform of the 3x3 / stride 2 / pad 1 conv summed over its four input phases (csrc/winograd_s2_43.hip): w = (Cout, Cin, 3, 3) padded to 4x4
+// with a zero last row and column, phase (by, bx): g[a][b] = w[n][c][2a + by][2b + bx], U = G4 g G3^T with the G4, G3 above.  The by = 1 phases have g[1][.] = 0
+// and G4's last row is [0 1], so their row position xi = 4 is identically zero and is NOT stored: 20 + 20 + 16 + 16 = 72 floats per channel pair.  The phases are
+// concatenated along the step index so that a block's filter stream is contiguous:
+//   [n / 64][by = 0: bx, step = c / 8, 20 positions xi * 4 + nu | by = 1: bx, step, 16 positions][n / 32 % 2][lane = (c % 8 / 4) * 32 + n % 32][c % 4]
+// i.e. per 64 output channels (Cin / 8) * 36864 floats, the by = 1 part starting at (Cin / 8) * 20480.  bl = phase * (Cout / 32) * (Cin / 8) + (n / 32) * (Cin / 8) + c / 8;
+// a block of 256 threads makes the 20 (16) x 256 elements of (32 output channels, one 8-channel step).  Float64 arithmetic, rounded once.
+__device__ __forceinline__ void wino_s2_43_pack_block(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, long long bl, int tid) {
+    const int steps = Cin >> 3;
+    const long long per = (long long)(Cout >> 5) * steps;             // blocks per phase
+    const int phase = (int)(bl / per);
+    bl -= phase * per;
+    const int n32 = (int)(bl / steps), step = (int)(bl - (long long)n32 * steps);
+    const int nl = tid & 31, cc = tid >> 5;
+    const int n = n32 * 32 + nl, c = step * 8 + cc;
+    const int by = phase >> 1, bx = phase & 1;
+    const double G4[5][2] = {{0.5, 0.0}, {-0.5, -0.5}, {-1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3}, {0.0, 1.0}};
+    const double G3[4][2] = {{1.0, 0.0}, {0.5, 0.5}, {0.5, -0.5}, {0.0, -1.0}};
+    double g[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+            g[a][b] = (2 * a + by < 3 && 2 * b + bx < 3) ? (double)w[(((long long)n * Cin + c) * 3 + (2 * a + by)) * 3 + (2 * b + bx)] : 0.0;
+    const long long gstep = (long long)bx * steps + step;
+    float* o = out + (long long)(n32 >> 1) * steps * 36864 + (by ? (long long)steps * 20480 + gstep * 8192 : gstep * 10240) +
+               ((n32 & 1) * 64 + (cc >> 2) * 32 + nl) * 4 + (cc & 3);
+#pragma unroll
+    for (int xi = 0; xi < 5; ++xi) {
+        if (by && xi == 4) continue;
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+            double v = 0.0;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) v += G4[xi][a] * g[a][b] * G3[nu][b];
+            o[(long long)(xi * 4 + nu) * 512] = (float)v;
+        }
+    }
+}
+
 // One 16-byte item of the F(4x4,3x3) filter transform U = G g G^T (csrc/winograd_f4.hip), shared by its pack kernel and the table-driven multi-pack launch.
 // Fragment order [stage = c / 16][position xi * 6 + nu][column block = n / 16][lane = (c % 16 / 4) * 16 + n % 16][k-step = c % 4]; item = (stage, position, block, lane).
 // dgrad = 0: g = w[n][c] of the (Cout, Cin, 3, 3) filter (w_i = Cin); 1: the data gradient's filter g = rot180(w[o = c][i = n]) of the forward (O, I, 3, 3) filter

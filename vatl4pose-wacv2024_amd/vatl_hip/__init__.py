@@ -124,6 +124,10 @@ SIGNATURES = {
     "vatl_pack_winograd_deconv43_weight": (_i, [_p, _p, _i, _i, _p]),
     "vatl_deconv4x4s2_winograd43_supported": (_i, [_i, _i, _i, _i, _i]),
     "vatl_deconv4x4s2_winograd43_fwd": (_i, [_p] * 5 + [_i] * 6 + [_p]),
+    "vatl_winograd_s2_43_weight_floats": (_i64, [_i, _i]),
+    "vatl_pack_winograd_s2_43_weight": (_i, [_p, _p, _i, _i, _p]),
+    "vatl_conv3x3s2_winograd43_supported": (_i, [_i, _i, _i, _i, _i]),
+    "vatl_conv3x3s2_winograd43_fwd": (_i, [_p] * 5 + [_i] * 6 + [_p]),
     "vatl_winograd_deconv_stats_row_blocks": (_i64, [_i64, _i, _i]),
     "vatl_deconv4x4s2_winograd_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_conv2d_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
@@ -266,7 +270,7 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
 
 ROUTE_NAMES = ("igemm", "igemm_bnbwd", "igemm_dma", "persistent_1x1", "streamk", "rows_1x1", "bottleneck_chain", "stem_pool", "halo_3x3", "winograd",
                "winograd_2h", "winograd_bnbwd", "winograd_persist", "winograd_c32", "wgrad", "winograd_wgrad", "winograd_wgrad_2h", "winograd_wgrad_table", "winograd_f4", "winograd_f4_bnbwd",
-               "gemm1x1_ring", "winograd_deconv43")
+               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43")
 
 
 class flop_meter:
@@ -618,6 +622,17 @@ def pack_winograd_deconv43_weight(w: torch.Tensor) -> torch.Tensor:
         int(lib().vatl_winograd_deconv43_weight_floats(cout, cin)), "vatl_pack_winograd_deconv43_weight", (cout, cin), None), planned=False)
 
 
+def pack_winograd_s2_43_weight(w: torch.Tensor) -> torch.Tensor:
+    """3x3 / stride 2 / pad 1 conv weight (Cout,Cin,3,3) -> its four input-phase filters in the F(4x3,2x2) transform domain (20 positions for the two
+    by = 0 phases, 16 for the two by = 1), concatenated along the step index in MFMA fragment order (csrc/winograd_s2_43.hip).  Inference only: packed on
+    the spot, never part of a PackPlan's one-launch re-pack table."""
+    cout, cin = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3):
+        raise VatlError("pack_winograd_s2_43_weight: 3x3 filters only")
+    return _pack(("winograd_s2_43", w.data_ptr(), tuple(w.shape)), w, lambda: (
+        int(lib().vatl_winograd_s2_43_weight_floats(cout, cin)), "vatl_pack_winograd_s2_43_weight", (cout, cin), None), planned=False)
+
+
 def pack_winograd_deconv_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
     """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the filters of its DATA gradient (a 4x4 / stride 2 conv over dz = four pixel
     phases x 2x2 convolutions) in the F(3x3,2x2) transform domain."""
@@ -683,13 +698,25 @@ def bn_fold(gamma, beta, mean, var, eps: float, conv_bias=None, channels: int | 
 # backbone ops (NHWC)
 # ----------------------------------------------------------------------------
 
+def conv3x3s2_winograd43_supported(n: int, h: int, w: int, cin: int, cout: int) -> bool:
+    return bool(lib().vatl_conv3x3s2_winograd43_supported(n, h, w, cin, cout))
+
+
 def conv2d_fwd(x, w_packed, scale, bias, cout: int, r: int, s: int, stride: int, pad: int, relu: bool,
-               residual=None, out_nchw: bool = False, out=None):
+               residual=None, out_nchw: bool = False, out=None, u_s2=None):
+    """Conv2d + folded BN (+ residual) (+ ReLU) of an NHWC tensor on the implicit GEMM — or, when ``u_s2`` (pack_winograd_s2_43_weight) is given and the
+    call is a 3x3 / stride 2 / pad 1 layer without residual, NHWC output, of a shape the kernel serves (conv3x3s2_winograd43_supported), as Winograd
+    F(4x3,2x2) summed over the four input phases (csrc/winograd_s2_43.hip; other bits).  Every other call ignores ``u_s2``."""
     n, h, w, cin = x.shape
     ho = (h + 2 * pad - r) // stride + 1
     wo = (w + 2 * pad - s) // stride + 1
     shape = (n, cout, ho, wo) if out_nchw else (n, ho, wo, cout)
     y = out if out is not None else torch.empty(shape, device=x.device, dtype=torch.float32)
+    if (u_s2 is not None and (r, s, stride, pad) == (3, 3, 2, 1) and residual is None and not out_nchw
+            and conv3x3s2_winograd43_supported(n, h, w, cin, cout)):
+        _check(lib().vatl_conv3x3s2_winograd43_fwd(_ptr(x), _ptr(u_s2), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
+               "vatl_conv3x3s2_winograd43_fwd")
+        return y
     _check(lib().vatl_conv2d_fwd(_ptr(x), _ptr(w_packed), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout,
                                  w_packed.shape[0], r, s, stride, pad, int(relu), int(out_nchw), _stream()), "vatl_conv2d_fwd")
     return y
