@@ -50,7 +50,7 @@ int vatl_flop_meter_end(double* direct_flops, double* winograd_flops, int64_t* d
  * BatchNorm-backward epilogue, ...) instead of trusting the dispatch rules. */
 #define VATL_ROUTE_NAMES "igemm,igemm_bnbwd,igemm_dma,persistent_1x1,streamk,rows_1x1,bottleneck_chain,stem_pool,halo_3x3," \
                          "winograd,winograd_2h,winograd_bnbwd,winograd_persist,winograd_c32,wgrad,winograd_wgrad,winograd_wgrad_2h," \
-                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43,winograd_s2_43"
+                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43,winograd_s2_43,stem_pool_w1d"
 int vatl_flop_meter_routes(int64_t* counts, int n);
 
 /* ------------------------------------------------------------------------ *
@@ -82,6 +82,19 @@ int vatl_pack_stem_pool_weight(const float* w_oihw, float* packed, void* stream)
 int vatl_stem_pool_supported(int H, int W);
 int vatl_stem7x7s2_pool_fwd(const float* x_nchw, const float* w_packed, const float* scale, const float* bias, float* y_nhwc,
                             int N, int H, int W, void* stream);
+/* The same stem with a 1-D Winograd transform along the image rows (csrc/stem_pool_w1d.hip, inference only): the odd pixels of a row meet the taps
+ * w[0::2] as F(2,4), the even pixels the taps w[1::2] as F(2,3), both on tiles of two neighbouring stem outputs: 9 products per (channel, filter row)
+ * and tile instead of 16; the reduction over the 21 (filter row, channel) entries runs on v_mfma_f32_16x16x4_f32 padded to K = 24.  Same contract as
+ * vatl_stem7x7s2_pool_fwd, same precision class, other bits.  Filter: vatl_pack_stem_pool_w1d_weight, (64,3,7,7) OIHW -> vatl_stem_pool_w1d_weight_floats()
+ * floats, [channel / 16][position 0-8][k-step][lane = 16 (kk % 4) + channel % 16], kk = 3 ky + c, entries 21 .. 23 zero; positions 0 - 4 =
+ * G4 w[..][0::2] with G4 = [1/2 0 0 0; 1/2 1/2 1/2 1/2; 1/6 -1/6 1/6 -1/6; 1/6 1/3 2/3 4/3; 0 0 0 1], positions 5 - 8 = G3 w[..][1::2] with
+ * G3 = [1 0 0; 1/2 1/2 1/2; 1/2 -1/2 1/2; 0 0 1], float64 rounded once.  Served sizes: vatl_stem_pool_w1d_supported(H, W) != 0 (W in {64, 128, 192},
+ * H % 4 == 0; 256x192: yes).  x and y must be 16-byte aligned. */
+int64_t vatl_stem_pool_w1d_weight_floats(void);
+int vatl_pack_stem_pool_w1d_weight(const float* w_oihw, float* packed, void* stream);
+int vatl_stem_pool_w1d_supported(int H, int W);
+int vatl_stem7x7s2_pool_w1d_fwd(const float* x_nchw, const float* w_packed, const float* scale, const float* bias, float* y_nhwc,
+                                int N, int H, int W, void* stream);
 /* HRNet's first stem layer the same way: NCHW crops -> conv 3x3 / stride 2 / pad 1 (3 -> 64) -> folded BatchNorm -> ReLU -> NHWC
  * (N, H/2, W/2, 64)  (hrnet.py:109-110, 426-428: conv1, bn1, relu).  Filter (64,3,3,3) packed by vatl_pack_stem3_weight into
  * vatl_stem3_weight_floats() floats; same served sizes (vatl_stem_pool_supported). */

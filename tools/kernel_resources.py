@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Register / LDS budget of every kernel of a csrc file, from hipcc's own remarks (no GPU needed):
 
-    python tools/kernel_resources.py conv_igemm [gemm1x1_ring conv_streamk conv_wgrad winograd_deconv43 winograd_s2_43 ...]
+    python tools/kernel_resources.py conv_igemm [gemm1x1_ring conv_streamk conv_wgrad winograd_deconv43 winograd_s2_43 stem_pool_w1d ...]
 (names of csrc/*.hip files; the persistent 1x1 kernels are part of conv_igemm) prints arch VGPRs, accumulator VGPRs, spills, scratch bytes per lane, waves per SIMD and static LDS bytes per block
 (the Winograd kernels' LDS is dynamic: see their launchers).  A kernel whose waves leave part of the
 SIMD's 512 registers free lets a small element-wise wave of another stream share the CU (profiles/r05_notes.md)."""

@@ -4,6 +4,7 @@
     python tools/wino_bench.py [--batch 1024] [--iters 5] [--layers l1.c2,...] [--check 8]
     python tools/wino_bench.py --deconv43 --iters 10        # the transposed convs: F(3x3,2x2) against F(4x3,2x2)
     python tools/wino_bench.py --s2 --iters 10              # the stride-2 3x3 convs: implicit GEMM against F(4x3,2x2) over the four input phases
+    python tools/wino_bench.py --stem --iters 10            # the fused ResNet stem: direct sum against the 1-D Winograd F(2,4) + F(2,3) along the rows
 
 For every shape: max |error| of both routes against a float64 convolution (on `--check` crops), then `iters` launches of
 each route between HIP events (TFLOP/s are algorithmic = direct-convolution FLOPs for both).
@@ -54,6 +55,8 @@ def main():
     ap.add_argument("--deconv43", action="store_true", help="deconv layers only: F(3x3,2x2) against F(4x3,2x2) (csrc/winograd_deconv43.hip), median of 3 alternating loops of --iters launches")
     ap.add_argument("--s2", action="store_true", help="stride-2 3x3 layers only: implicit GEMM against F(4x3,2x2) over the four input phases (csrc/winograd_s2_43.hip), "
                     "median of 3 alternating loops of --iters launches; --layers picks from the flagship's three and the hr.* shapes (default: the flagship's)")
+    ap.add_argument("--stem", action="store_true", help="the fused ResNet stem on 256x192 crops only: csrc/stem_pool.hip against csrc/stem_pool_w1d.hip, median of 3 alternating "
+                    "loops of --iters launches, each over its own executed-FLOP floor")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.persist >= 0:
@@ -67,6 +70,33 @@ def main():
         warm @ warm
     torch.cuda.synchronize()
     g = torch.Generator(device="cpu").manual_seed(5)
+    if a.stem:
+        b, h, w = a.batch, 256, 192
+        x = (torch.rand((b, 3, h, w), generator=g) - 0.45).to(dev)
+        wt = (torch.randn((64, 3, 7, 7), generator=g) * (2.0 / 147) ** 0.5).to(dev)
+        sc = (torch.rand(64, generator=g) + 0.5).to(dev)
+        bi = (torch.randn(64, generator=g) * 0.5).to(dev)
+        pw, u1d = vh.pack_stem_pool_weight(wt), vh.pack_stem_pool_w1d_weight(wt)
+        out = torch.empty((b, h // 4, w // 4, 64), device=dev)
+        yd = vh.stem_pool_fwd(x, pw, sc, bi)
+        yw = vh.stem_pool_fwd(x, pw, sc, bi, out=out, u1d=u1d)
+        k = min(a.check, b)
+        ref = torch.nn.functional.conv2d(x[:k].double(), wt.double(), None, 2, 3) * sc.double().view(1, -1, 1, 1) + bi.double().view(1, -1, 1, 1)
+        ref = torch.nn.functional.max_pool2d(ref.clamp_min(0), 3, 2, 1).permute(0, 2, 3, 1)
+        ed, ew = (yd[:k].double() - ref).abs().max().item(), (yw[:k].double() - ref).abs().max().item()
+        full = (yd - yw).abs().max().item()
+        del yd
+        td, tw = [], []
+        for _ in range(3):
+            td.append(timed(lambda: vh.stem_pool_fwd(x, pw, sc, bi, out=out), a.iters))
+            tw.append(timed(lambda: vh.stem_pool_fwd(x, pw, sc, bi, out=out, u1d=u1d), a.iters))
+        md, mw = sorted(td)[1], sorted(tw)[1]
+        px = b * (h // 2) * (w // 2)                                                             # stem outputs (bands recompute a few rows more below 512 crops)
+        fd = 2.0 * px * 168 * 64 / 157.3e12 * 1e6                                              # executed-FLOP floors at the fp32 MFMA peak, us
+        fw = 2.0 * (px // 2) * 9 * 24 * 64 / 157.3e12 * 1e6
+        print(f"stem 7x7/2 + pool B={b:5d} direct {md:8.1f} us (floor {fd:7.1f}, {fd / md:.3f}) err {ed:.2e} | 1-D F(2,4)+F(2,3) {mw:8.1f} us (floor {fw:7.1f}, {fw / mw:.3f}) err {ew:.2e} | "
+              f"max |difference| {full:.2e}  ref max {ref.abs().max().item():.2f}  speed-up {md / mw:.3f}x of {168 / 108:.3f}  loops {' '.join(f'{v:.1f}' for v in td)} / {' '.join(f'{v:.1f}' for v in tw)}", flush=True)
+        return
     names = a.layers.split(",") if a.layers else ([] if a.deconv43 else list(SHAPES)) + list(DECONVS)
     if a.s2:
         names = (list(S2) + list(S2_HR) if a.layers == "all" else a.layers.split(",")) if a.layers else list(S2)

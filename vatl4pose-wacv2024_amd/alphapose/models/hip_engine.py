@@ -217,6 +217,10 @@ def _run_blocks(blocks, x, out=None):
 # 4-channel implicit GEMM, no 3.2 GB stem activation per 1024 crops, no layout pass) where the input size allows (256x192: yes; 384x288: no).  Not in the
 # small-batch module calls (vh.latency_mode(): a handful of crops leaves most of its per-image blocks without work).  False = three launches (K summed in another order).
 FUSE_STEM = True
+# ... and, where the width is 64, 128 or 192 (256x192: yes), with a 1-D Winograd transform along the rows: F(2,4) on the odd pixels + F(2,3) on the even pixels of
+# every input row (csrc/stem_pool_w1d.hip: 108 executed multiplies per output and channel against 168).  Geometry-only choice like WINOGRAD; the filter is packed on
+# the first call that takes the route.  False = csrc/stem_pool.hip (same values to fp32 rounding, not the same bits).
+STEM_W1D = True
 
 
 def _stem_pool_weight(net):
@@ -231,12 +235,18 @@ class _TrunkPlan:
     def __init__(self, net):
         self.stem = _Conv(net.conv1, net.bn1)
         self.stem_pw = _stem_pool_weight(net)
+        self.stem_src, self.stem_u1d = net.conv1.weight.detach(), None
         self.blocks = [_BottleneckPlan(b) for stage in net.stages() for b in stage]
         self.n_stage1 = len(net.stages()[0])
 
     def _stem(self, x_nchw):
         if self.stem_pw is not None and not vh.latency_mode() and vh.stem_pool_supported(x_nchw.shape[2], x_nchw.shape[3]):
-            return vh.stem_pool_fwd(x_nchw, self.stem_pw, self.stem.scale, self.stem.bias)
+            u1d = None
+            if STEM_W1D and vh.stem_pool_w1d_supported(x_nchw.shape[2], x_nchw.shape[3]):
+                if self.stem_u1d is None:
+                    self.stem_u1d = vh.pack_stem_pool_w1d_weight(self.stem_src)
+                u1d = self.stem_u1d
+            return vh.stem_pool_fwd(x_nchw, self.stem_pw, self.stem.scale, self.stem.bias, u1d=u1d)
         x = vh.nchw_to_nhwc(x_nchw, 4)                              # 3 -> 4 channels (zero), 16-byte pixels
         x = self.stem(x, relu=True)
         return vh.maxpool3x3s2_fwd(x)
@@ -304,6 +314,7 @@ class _SETrunkPlan(_TrunkPlan):
     def __init__(self, net):
         self.stem = _Conv(net.conv1, net.bn1)
         self.stem_pw = _stem_pool_weight(net)
+        self.stem_src, self.stem_u1d = net.conv1.weight.detach(), None
         self.blocks = [(_SEBottleneckPlan(b) if getattr(b, "reduc", False) else _BottleneckPlan(b))
                        for stage in net.stages() for b in stage]
         self.n_stage1 = len(net.stages()[0])

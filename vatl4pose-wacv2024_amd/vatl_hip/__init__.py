@@ -54,6 +54,10 @@ SIGNATURES = {
     "vatl_stem_pool_weight_floats": (_i64, []),
     "vatl_pack_stem_pool_weight": (_i, [_p, _p, _p]),
     "vatl_stem_pool_supported": (_i, [_i, _i]),
+    "vatl_stem_pool_w1d_weight_floats": (_i64, []),
+    "vatl_pack_stem_pool_w1d_weight": (_i, [_p, _p, _p]),
+    "vatl_stem_pool_w1d_supported": (_i, [_i, _i]),
+    "vatl_stem7x7s2_pool_w1d_fwd": (_i, [_p] * 5 + [_i] * 3 + [_p]),
     "vatl_stem7x7s2_pool_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "vatl_stem3_weight_floats": (_i64, []),
     "vatl_pack_stem3_weight": (_i, [_p, _p, _p]),
@@ -270,7 +274,7 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
 
 ROUTE_NAMES = ("igemm", "igemm_bnbwd", "igemm_dma", "persistent_1x1", "streamk", "rows_1x1", "bottleneck_chain", "stem_pool", "halo_3x3", "winograd",
                "winograd_2h", "winograd_bnbwd", "winograd_persist", "winograd_c32", "wgrad", "winograd_wgrad", "winograd_wgrad_2h", "winograd_wgrad_table", "winograd_f4", "winograd_f4_bnbwd",
-               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43")
+               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43", "stem_pool_w1d")
 
 
 class flop_meter:
@@ -675,6 +679,17 @@ def pack_stem_pool_weight(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def pack_stem_pool_w1d_weight(w: torch.Tensor) -> torch.Tensor:
+    """(64,3,7,7) OIHW stem filter -> its 1-D Winograd transform in the fragment order of vatl_stem7x7s2_pool_w1d_fwd (csrc/stem_pool_w1d.hip): positions 0 - 4 =
+    G4 w[..., 0::2], 5 - 8 = G3 w[..., 1::2], float64 rounded once.  Inference only: packed on the spot, never part of a PackPlan's one-launch re-pack table."""
+    if tuple(w.shape) != (64, 3, 7, 7):
+        raise VatlError(f"pack_stem_pool_w1d_weight: expected a (64,3,7,7) filter, got {tuple(w.shape)}")
+    w = w.detach().float().contiguous()
+    out = torch.empty(int(lib().vatl_stem_pool_w1d_weight_floats()), device=w.device, dtype=torch.float32)
+    _check(lib().vatl_pack_stem_pool_w1d_weight(_ptr(w), _ptr(out), _stream()), "vatl_pack_stem_pool_w1d_weight")
+    return out
+
+
 def pack_stem3_weight(w: torch.Tensor) -> torch.Tensor:
     """(64,3,3,3) OIHW filter of HRNet's conv1 -> the fragment order of vatl_stem3x3s2_fwd."""
     if tuple(w.shape) != (64, 3, 3, 3):
@@ -781,12 +796,31 @@ def stem_pool_supported(h: int, w: int) -> bool:
     return bool(lib().vatl_stem_pool_supported(int(h), int(w)))
 
 
-def stem_pool_fwd(x_nchw: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, out=None) -> torch.Tensor:
-    """NCHW crops (N,3,H,W) -> conv7x7/2 + folded BN + ReLU + maxpool3x3/2 -> NHWC (N,H/4,W/4,64) in one launch (Resnet.py:155-158, 171-172)."""
+def stem_pool_w1d_supported(h: int, w: int) -> bool:
+    return bool(lib().vatl_stem_pool_w1d_supported(int(h), int(w)))
+
+
+def stem_pool_w1d_fwd(x_nchw: torch.Tensor, u1d: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, out=None) -> torch.Tensor:
+    """stem_pool_fwd on the 1-D Winograd kernel alone (csrc/stem_pool_w1d.hip); a size it does not serve is an error."""
+    n, c, h, w = x_nchw.shape
+    if c != 3:
+        raise VatlError(f"stem_pool_w1d_fwd: expected 3 input channels, got {c}")
+    y = out if out is not None else torch.empty((n, h // 4, w // 4, 64), device=x_nchw.device, dtype=torch.float32)
+    _check(lib().vatl_stem7x7s2_pool_w1d_fwd(_ptr(x_nchw), _ptr(u1d), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, _stream()), "vatl_stem7x7s2_pool_w1d_fwd")
+    return y
+
+
+def stem_pool_fwd(x_nchw: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, out=None, u1d=None) -> torch.Tensor:
+    """NCHW crops (N,3,H,W) -> conv7x7/2 + folded BN + ReLU + maxpool3x3/2 -> NHWC (N,H/4,W/4,64) in one launch (Resnet.py:155-158, 171-172).  With ``u1d``
+    (pack_stem_pool_w1d_weight) and a size that kernel serves (stem_pool_w1d_supported) the launch is the 1-D Winograd stem (csrc/stem_pool_w1d.hip; other
+    bits); every other call ignores ``u1d``."""
     n, c, h, w = x_nchw.shape
     if c != 3:
         raise VatlError(f"stem_pool_fwd: expected 3 input channels, got {c}")
     y = out if out is not None else torch.empty((n, h // 4, w // 4, 64), device=x_nchw.device, dtype=torch.float32)
+    if u1d is not None and stem_pool_w1d_supported(h, w):
+        _check(lib().vatl_stem7x7s2_pool_w1d_fwd(_ptr(x_nchw), _ptr(u1d), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, _stream()), "vatl_stem7x7s2_pool_w1d_fwd")
+        return y
     _check(lib().vatl_stem7x7s2_pool_fwd(_ptr(x_nchw), _ptr(w_packed), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, _stream()), "vatl_stem7x7s2_pool_fwd")
     return y
 
