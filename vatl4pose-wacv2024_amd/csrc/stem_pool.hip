@@ -268,8 +268,10 @@ static int launch_stem_pool(const StemPoolParams& p, hipStream_t st) {
     constexpr int smem = StemPoolLds<TPR, KS>::FLOATS * (int)sizeof(float);
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, configured, "stem_pool")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(p.N * p.bands)), dim3(256), smem, st, p);
-    // executed MFMA FLOPs: every step multiplies 2 stem rows x (W / 2) pixels x 64 channels x K = 3 KS (KS + 1) (+ one recomputed step per pooling band below the first)
-    const double steps = (double)p.N * ((p.H >> 2) + (KS == 7 ? p.bands - 1 : 0));
+    // executed MFMA FLOPs: every step multiplies 2 stem rows x (W / 2) pixels x 64 channels x K = 3 KS (KS + 1) (+ one recomputed step per pooling band below the first;
+    // a band that starts past the last pooled row — PH = 33 in 8 bands of 5 — leaves at once and recomputes nothing)
+    const int PH = p.H >> 2, nonempty = (PH + p.steps_per_band - 1) / p.steps_per_band;
+    const double steps = (double)p.N * (PH + (KS == 7 ? nonempty - 1 : 0));
     meter_add(0, 2.0 * steps * 2.0 * (p.W / 2) * 64.0 * (3.0 * KS * (KS + 1)));
     meter_route(kRouteStemPool);
     return check_launch("stem_pool");

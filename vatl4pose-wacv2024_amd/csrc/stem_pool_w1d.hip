@@ -299,7 +299,9 @@ static int launch_stem_pool_w1d(const StemW1dParams& p, hipStream_t st) {
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, configured, "stem_pool_w1d")) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(p.N * p.bands)), dim3(256), smem, st, p);
     // executed MFMA FLOPs: every step multiplies 2 stem rows x (W / 4) tiles x 9 positions x 64 channels x K = 24 (21 + 3 of padding), + one recomputed step per band below the first
-    const double steps = (double)p.N * ((p.H >> 2) + p.bands - 1);
+    // (a band that starts past the last pooled row — PH = 33 in 8 bands of 5 — leaves at once and recomputes nothing)
+    const int PH = p.H >> 2, nonempty = (PH + p.steps_per_band - 1) / p.steps_per_band;
+    const double steps = (double)p.N * (PH + nonempty - 1);
     meter_add(0, 2.0 * steps * 2.0 * (p.W / 4) * 9.0 * 24.0 * 64.0);
     meter_route(kRouteStemPoolW1d);
     return check_launch("stem_pool_w1d");

@@ -782,12 +782,12 @@ def bottleneck_chain_fwd(a, w3, scale3, bias3, skip, w1=None, scale1=None, bias1
     return t, y1
 
 
-def stem3_fwd(x_nchw: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+def stem3_fwd(x_nchw: torch.Tensor, w_packed: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, out=None) -> torch.Tensor:
     """NCHW crops (N,3,H,W) -> conv3x3/2 + folded BN + ReLU -> NHWC (N,H/2,W/2,64) in one launch (hrnet.py:109-110, 426-428)."""
     n, c, h, w = x_nchw.shape
     if c != 3:
         raise VatlError(f"stem3_fwd: expected 3 input channels, got {c}")
-    y = torch.empty((n, h // 2, w // 2, 64), device=x_nchw.device, dtype=torch.float32)
+    y = out if out is not None else torch.empty((n, h // 2, w // 2, 64), device=x_nchw.device, dtype=torch.float32)
     _check(lib().vatl_stem3x3s2_fwd(_ptr(x_nchw), _ptr(w_packed), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, _stream()), "vatl_stem3x3s2_fwd")
     return y
 
