@@ -50,7 +50,8 @@ int vatl_flop_meter_end(double* direct_flops, double* winograd_flops, int64_t* d
  * BatchNorm-backward epilogue, ...) instead of trusting the dispatch rules. */
 #define VATL_ROUTE_NAMES "igemm,igemm_bnbwd,igemm_dma,persistent_1x1,streamk,rows_1x1,bottleneck_chain,stem_pool,halo_3x3," \
                          "winograd,winograd_2h,winograd_bnbwd,winograd_persist,winograd_c32,wgrad,winograd_wgrad,winograd_wgrad_2h," \
-                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43,winograd_s2_43,stem_pool_w1d"
+                         "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43,winograd_s2_43,stem_pool_w1d," \
+                         "chain_proj,chain_step"
 int vatl_flop_meter_routes(int64_t* counts, int n);
 
 /* ------------------------------------------------------------------------ *
@@ -185,6 +186,21 @@ int vatl_bottleneck_chain_supported(int Cmid, int Cout, int Cnext, int64_t M);
 int vatl_bottleneck_chain_fwd(const float* a, const float* w3, const float* scale3, const float* bias3, const float* skip, float* t,
                               const float* w1, const float* scale1, const float* bias1, float* y1, int64_t M, int Cmid, int Cout,
                               int Cnext, void* stream);
+
+/* The two other 256-channel boundaries of ResNet stage 1 / HRNet layer1 as one launch each (csrc/bottleneck_chain.hip, chain_form_kernel): t is written once and
+ * the next block's conv1 takes it from LDS.
+ *   vatl_chain_proj_fwd: t = act(scale * ([a | x2] W^T) + bias), the dual-source conv3 + projection shortcut of a stage's first block exactly as
+ *     vatl_conv1x1_rows_fwd computes it with x2 (a, x2 (M, 64); w [256][128] from vatl_pack_conv1x1_dual_weight; t has its bits), and
+ *     y1 = relu(scale1 * (t W1^T) + bias1), the next block's conv1 (w1 [64][256]): fp32 rounding of the separate launch's value, not its bits.
+ *   vatl_chain_step_fwd: t = relu(scale3 * (a W3^T) + bias3 + skip) as vatl_bottleneck_chain_fwd computes it (same bits) and
+ *     y1 = relu(scale1 * (t W1^T) + bias1) with w1 [128][256], the first conv1 of stage 2: the bits of vatl_conv1x1_rows_fwd (K = 256).
+ * scale / bias / skip may be NULL.  Served (the _supported calls, host only): Cmid 64, Cout 256, Cnext 64 (proj) / 128 (step), (M + 32) * 256 < 2^30. */
+int vatl_chain_proj_supported(int Cmid, int Cout, int Cnext, int64_t M);
+int vatl_chain_proj_fwd(const float* a, const float* x2, const float* w, const float* scale, const float* bias, float* t, const float* w1,
+                        const float* scale1, const float* bias1, float* y1, int64_t M, int Cmid, int Cout, int Cnext, int relu, void* stream);
+int vatl_chain_step_supported(int Cmid, int Cout, int Cnext, int64_t M);
+int vatl_chain_step_fwd(const float* a, const float* w3, const float* scale3, const float* bias3, const float* skip, float* t, const float* w1,
+                        const float* scale1, const float* bias1, float* y1, int64_t M, int Cmid, int Cout, int Cnext, void* stream);
 
 /* Route selectors (benchmarks / A-B tests only).  PROCESS-GLOBAL (relaxed atomics inside the library; set them before
  * several host threads launch) and FROZEN: the shipped library accepts exactly the knobs of this table, and every accepted value

@@ -166,25 +166,46 @@ class _BottleneckPlan:
                                                self.proj.scale, self.proj.bias)
             self.dual = (w, b, self.proj.stride)
 
-    def __call__(self, x, out=None, y1=None):
+    def __call__(self, x, out=None, y1=None, nxt=None):
         y = y1 if y1 is not None else self.c1(x, relu=True)         # y1: conv1 + bn1 + relu already computed by the block before (chained launch)
         y = self.c2(y, relu=True)
-        return self.tail(y, x, out=out)
+        return self.tail(y, x, out=out, nxt=nxt)
 
-    def tail(self, y, x, out=None):
+    def tail(self, y, x, out=None, nxt=None):
+        """The block's output; with `nxt` (the next block's conv1 as (w, scale, bias), see _run_blocks) the pair (output, next block's y1 or None)."""
         if self.dual is not None:                                   # relu(bn3(conv3(y)) + bn_p(conv_p(x))) in one GEMM over K = C1 + C2
             if (ROWS_GEMM and self.dual[2] == 1 and y.shape[-1] == 64 and x.shape[-1] == 64 and not vh.latency_mode()
                     and vh.conv1x1_rows_supported(64, 64, self.c3.cout, y.shape[0] * y.shape[1] * y.shape[2])):
-                return vh.conv1x1_rows_fwd(y, self.dual[0], None, self.dual[1], self.c3.cout, True, x2=x, out=out)
-            return vh.conv1x1_dual_fwd(y, x, self.dual[0], self.dual[1], self.c3.cout, self.dual[2], True, out=out)
-        skip = x if self.proj is None else self.proj(x, relu=False)
-        return self.c3(y, relu=True, residual=skip, out=out)        # relu(bn3(conv3) + skip)
+                if nxt is not None and FUSE_CHAIN_PROJ and vh.chain_proj_supported(64, self.c3.cout, nxt[0].shape[0], y.shape[0] * y.shape[1] * y.shape[2]):
+                    return vh.conv1x1_rows_fwd(y, self.dual[0], None, self.dual[1], self.c3.cout, True, x2=x, out=out, next_conv1=nxt)
+                t = vh.conv1x1_rows_fwd(y, self.dual[0], None, self.dual[1], self.c3.cout, True, x2=x, out=out)
+            else:
+                t = vh.conv1x1_dual_fwd(y, x, self.dual[0], self.dual[1], self.c3.cout, self.dual[2], True, out=out)
+        else:
+            skip = x if self.proj is None else self.proj(x, relu=False)
+            t = self.c3(y, relu=True, residual=skip, out=out)       # relu(bn3(conv3) + skip)
+        return t if nxt is None else (t, None)
 
 
 # conv3 + bn3 + skip + relu of an identity-shortcut bottleneck chained with the NEXT block's conv1 + bn1 + relu in one launch (csrc/bottleneck_chain.hip, the
 # 64 -> 256 -> 64 shapes of ResNet stage 1 / HRNet layer1): the 256-channel tensor is written once and not re-read.  Not in the small-batch module calls.
 # False = the separate launches (conv3's output bit-identical; the chained conv1 sums K in four pieces).
 FUSE_CHAIN = True
+# The same for the two other 256-channel boundaries of such a stage (csrc/bottleneck_chain.hip, chain_form_kernel), each with its own switch:
+# FUSE_CHAIN_PROJ: conv3 + projection shortcut of the stage's first block (the dual-source row GEMM) with the second block's 256 -> 64 conv1
+#                  (the block output bit-identical; the chained conv1 sums K in another order: fp32 rounding);
+# FUSE_CHAIN_STEP: conv3 + skip of the stage's last block with the 256 -> 128 conv1 of the next stage's first block (both outputs bit-identical).
+# Not in the small-batch module calls.  False = the separate launches.
+FUSE_CHAIN_PROJ = True
+FUSE_CHAIN_STEP = True
+
+
+def _conv1_of(nxt, cout):
+    """(w, scale, bias) of the block's conv1 where a chained launch of the block before can compute it: a plain bottleneck whose conv1 is 1x1 / stride 1 with `cout` filters."""
+    if (type(nxt) is _BottleneckPlan and (nxt.c1.r, nxt.c1.stride, nxt.c1.pad) == (1, 1, 0) and nxt.c1.scale is not None and nxt.c1.cout == cout
+            and not vh.latency_mode()):
+        return nxt.c1.w, nxt.c1.scale, nxt.c1.bias
+    return None
 
 
 def _run_blocks(blocks, x, out=None):
@@ -196,18 +217,20 @@ def _run_blocks(blocks, x, out=None):
         if type(b) is not _BottleneckPlan:
             x, y1 = b(x), None
             continue
+        nxt = None if last else blocks[k + 1]
         m = x.shape[0] * x.shape[1] * x.shape[2]
         chain = (FUSE_CHAIN and b.proj is None and not vh.latency_mode() and b.c3.scale is not None
                  and vh.bottleneck_chain_supported(b.c3.w.shape[-1], b.c3.cout, 0, m))
         if not chain:
-            x, y1 = b(x, out=o, y1=y1), None
+            c1 = _conv1_of(nxt, 64) if b.dual is not None and FUSE_CHAIN_PROJ else None
+            x, y1 = b(x, out=o, y1=y1, nxt=c1) if c1 is not None else (b(x, out=o, y1=y1), None)
             continue
-        nxt = None if last else blocks[k + 1]
-        link = (type(nxt) is _BottleneckPlan and (nxt.c1.r, nxt.c1.stride, nxt.c1.pad) == (1, 1, 0) and nxt.c1.scale is not None
-                and vh.bottleneck_chain_supported(b.c3.w.shape[-1], b.c3.cout, nxt.c1.cout, m))
         y = b.c2(y1 if y1 is not None else b.c1(x, relu=True), relu=True)
-        if link:
-            x, y1 = vh.bottleneck_chain_fwd(y, b.c3.w, b.c3.scale, b.c3.bias, x, nxt.c1.w, nxt.c1.scale, nxt.c1.bias, out=o)
+        link, step = _conv1_of(nxt, 64), _conv1_of(nxt, 128) if FUSE_CHAIN_STEP else None
+        if link is not None and vh.bottleneck_chain_supported(b.c3.w.shape[-1], b.c3.cout, 64, m):
+            x, y1 = vh.bottleneck_chain_fwd(y, b.c3.w, b.c3.scale, b.c3.bias, x, *link, out=o)
+        elif step is not None and vh.chain_step_supported(b.c3.w.shape[-1], b.c3.cout, 128, m):
+            x, y1 = vh.bottleneck_chain_fwd(y, b.c3.w, b.c3.scale, b.c3.bias, x, out=o, next_stage_conv1=step)
         else:
             x, y1 = vh.bottleneck_chain_fwd(y, b.c3.w, b.c3.scale, b.c3.bias, x, out=o)[0], None
     return x
@@ -237,7 +260,6 @@ class _TrunkPlan:
         self.stem_pw = _stem_pool_weight(net)
         self.stem_src, self.stem_u1d = net.conv1.weight.detach(), None
         self.blocks = [_BottleneckPlan(b) for stage in net.stages() for b in stage]
-        self.n_stage1 = len(net.stages()[0])
 
     def _stem(self, x_nchw):
         if self.stem_pw is not None and not vh.latency_mode() and vh.stem_pool_supported(x_nchw.shape[2], x_nchw.shape[3]):
@@ -251,14 +273,8 @@ class _TrunkPlan:
         x = self.stem(x, relu=True)
         return vh.maxpool3x3s2_fwd(x)
 
-    def _stage1(self, x_nchw, out=None):
-        return _run_blocks(self.blocks[:self.n_stage1], self._stem(x_nchw), out=out)
-
     def __call__(self, x_nchw):
-        x = self._stage1(x_nchw)
-        for b in self.blocks[self.n_stage1:]:
-            x = b(x)
-        return x
+        return _run_blocks(self.blocks, self._stem(x_nchw))         # one walk over all stages: a chained launch may reach across a stage boundary
 
 
 class _SimplePosePlan:
@@ -317,7 +333,6 @@ class _SETrunkPlan(_TrunkPlan):
         self.stem_src, self.stem_u1d = net.conv1.weight.detach(), None
         self.blocks = [(_SEBottleneckPlan(b) if getattr(b, "reduc", False) else _BottleneckPlan(b))
                        for stage in net.stages() for b in stage]
-        self.n_stage1 = len(net.stages()[0])
 
 
 class _FastPosePlan:

@@ -186,6 +186,206 @@ __global__ __launch_bounds__(256, 2) void bottleneck_chain_kernel(ChainParams p)
     }
 }
 
+
+// ---- The two other 256-channel boundaries of stage 1 as one launch each (same idea as above: T stored once, the next block's conv1 takes it from LDS) ----
+//   form P (projection block):  T = relu(bias + [conv2 output | block input] x Wdual^T)   K = 64 + 64 (the packed dual filter and folded bias of conv1x1_rows_kernel<true>),
+//                               Y = relu(scale1 * (T x W1^T) + bias1)                     W1: 256 -> 64   (next block's conv1)
+//   form S (step into stage 2): T = relu(scale3 * (A x W3^T) + bias3 + skip)              K = 64 (the first GEMM above),
+//                               Y = relu(scale1 * (T x W1^T) + bias1)                     W1: 256 -> 128  (stage 2's first conv1)
+// The plain extension of the kernel above needs 192 filter registers and does not fit two blocks per CU.  What is different here:
+//   * the second GEMM is split over N, not K: wave w owns Y columns 32 w .. 32 w + 31 (S, v_mfma_f32_32x32x2_f32) or 16 w .. 16 w + 15 (P, v_mfma_f32_16x16x4_f32) and
+//     reads the whole T tile from LDS.  No partial sums, no exchange, two barriers per tile.  S walks K in the order of conv1x1_rows256_kernel: Y has its bits.
+//     P walks K as 16 q + 4 j + tt (j = lane / 16): fp32 rounding of the tiled GEMM's value, not its bits.
+//   * the T tile is kept as four 64-column blocks [wave][32 rows][64] with the 16-byte chunks XOR-swizzled by (row & 7), the A stage's layout: the wave that computes a
+//     64-column block of T is the one that brings its skip values in by LDS-DMA (S: eight 1 KB requests per wave and tile, issued before the first GEMM), so the skip
+//     needs a counted s_waitcnt and no barrier, and no registers across the MFMAs.
+// T has the bits of the launches replaced (same k order, same epilogue expression).  Arithmetic is per tile: a crop's bits do not depend on its batch position.
+struct FormParams {
+    const float* a;          // (M, 64) conv2 output
+    const float* x2;         // P: (M, 64) block input
+    const float* w3;         // P: packed dual [256][128]; S: packed [256][64]
+    const float* scale3;
+    const float* bias3;
+    const float* res;        // S: (M, 256) or null
+    float* t;                // (M, 256)
+    const float* w1;         // packed [N2][256]
+    const float* scale1;
+    const float* bias1;
+    float* y;                // (M, N2)
+    int m_tiles, relu3;
+    unsigned a_bytes, t_bytes, y_bytes;
+};
+
+// scalar + lane part of an address; opaque to the compiler, so the sums are formed where they are used and not kept in registers across the tile loop
+__device__ __forceinline__ unsigned uadd(unsigned s_part, unsigned v_part) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned r;
+    asm("v_add_u32 %0, %1, %2" : "=v"(r) : "s"(s_part), "v"(v_part));
+    return r;
+#else
+    return s_part + v_part;
+#endif
+}
+
+constexpr int CF_TS = 4 * 32 * 64;                // the T tile: [4 column blocks][32 rows][64], chunks swizzled
+
+template <bool PROJ>
+__global__ __launch_bounds__(256, 2) void chain_form_kernel(FormParams p) {
+    constexpr int K1 = PROJ ? 128 : 64, G1 = K1 / 8, AS = 32 * K1, N2 = PROJ ? 64 : 128;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* As = smem;                             // [2][32][K1]
+    float* Ts = smem + 2 * AS;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 31, h = lane >> 5;
+    const int nblk = gridDim.x;
+
+    const __amdgpu_buffer_rsrc_t ar = buf_rsrc(p.a, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(PROJ ? p.x2 : p.a, PROJ ? p.a_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t w3r = buf_rsrc(p.w3, 256u * K1 * 4u);
+    const __amdgpu_buffer_rsrc_t w1r = buf_rsrc(p.w1, (unsigned)N2 * 256u * 4u);
+    const __amdgpu_buffer_rsrc_t tr = buf_rsrc(p.t, p.t_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(p.res ? p.res : p.t, p.res ? p.t_bytes : 0u);
+    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
+
+    // first GEMM: this wave's 64 channels of T, all of K1, in MFMA B-fragment order (lane = (channel fr of a 32-column block, k half h))
+    f32x4 w3f[2][G1];
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int g = 0; g < G1; ++g) w3f[nb][g] = buf_load4(w3r, (unsigned)(((wave * 64 + nb * 32 + fr) * K1 + 8 * g + 4 * h) * 4));
+    float sc3[2], bi3[2];
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+        const int n = wave * 64 + nb * 32 + fr;
+        sc3[nb] = p.scale3 ? p.scale3[n] : 1.f;
+        bi3[nb] = p.bias3 ? p.bias3[n] : 0.f;
+    }
+    // second GEMM: this wave's Y columns, all 256 values of K.  S: lane (column fr, k half h) holds W1[n][8 g + 4 h ..]; P: lane (column lane & 15, k quarter j) W1[n][16 q + 4 j ..]
+    const int l16 = lane & 15, j = lane >> 4;
+    const int n1 = PROJ ? wave * 16 + l16 : wave * 32 + fr;
+    f32x4 w1f[PROJ ? 16 : 32];
+#pragma unroll
+    for (int g = 0; g < (PROJ ? 16 : 32); ++g) w1f[g] = buf_load4(w1r, (unsigned)((n1 * 256 + (PROJ ? 16 * g + 4 * j : 8 * g + 4 * h)) * 4));
+    const float sc1 = p.scale1 ? p.scale1[n1] : 1.f, bi1 = p.bias1 ? p.bias1[n1] : 0.f;
+    const float lo3 = p.relu3 ? 0.f : -INFINITY;
+
+    // Lane parts of the LDS and global addresses, kept few on purpose (the filters take 192 of the 256 registers); the wave- and tile-dependent parts are scalar and
+    // joined by uadd() inside the loop.  LDS addresses are float indices into smem.
+    const int c4 = lane, r0 = wave;               // T write-out: 64 float4 columns x 4 rows per pass, 8 passes
+    int ax[4], tq[4], tw[2], tx[PROJ ? 2 : 4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        ax[k] = fr * K1 + (((2 * k + h) ^ (fr & 7)) << 2);                                  // A fragment g: ax[g & 3] + 32 (g >> 2)   (chunk (2 g + h) ^ (fr & 7))
+        tq[k] = 2 * AS + 4 * h * 64 + ((((fr >> 2) ^ (4 * h) ^ k) << 2) | (fr & 3));        // T element e of column block nb: tq[e & 3] + 64 ((e & 3) + 8 (e >> 2)) + 32 nb
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) tw[k] = 2 * AS + (c4 >> 4) * 2048 + (((c4 & 15) ^ (r0 | 4 * k)) << 2);       // T piece of row r0 + 4 u: tw[u & 1] + 64 r0 + 256 u
+#pragma unroll
+    for (int k = 0; k < (PROJ ? 2 : 4); ++k)      // T fragment.  S, g: tx[g & 3] + 32 ((g >> 2) & 1) + 2048 (g >> 3);  P, (q, rb): tx[q & 1] + 32 ((q >> 1) & 1) + 2048 (q >> 2) + 1024 rb
+        tx[k] = 2 * AS + (PROJ ? l16 * 64 + (((4 * k + j) ^ (l16 & 7)) << 2) : fr * 64 + (((2 * k + h) ^ (fr & 7)) << 2));
+    unsigned va[PROJ ? 4 : 2], vs[2];             // A and skip requests: byte offset of the lane's piece within the request's rows
+#pragma unroll
+    for (int u = 0; u < (PROJ ? 4 : 2); ++u)
+        va[u] = PROJ ? (unsigned)(h * 64 + (((lane & 31) ^ (2 * u + h)) & 15) * 4) * 4u : (unsigned)(j * 64 + (l16 ^ (4 * u + j)) * 4) * 4u;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) vs[k] = (unsigned)(j * 256 + (l16 ^ (4 * k + j)) * 4) * 4u;
+    const unsigned vy = PROJ ? (unsigned)(4 * j * N2 + l16) * 4u : (unsigned)(4 * h * N2 + fr) * 4u;          // accumulator layout: rows 4 j + r (P) / (e & 3) + 8 (e >> 2) + 4 h (S)
+
+    // A stage by LDS-DMA, one tile ahead: 16-byte pieces, LDS piece (row, position) receives the row's chunk position ^ (row & 7).  Rows past M (and the tile after the
+    // last one) need no test: their byte offsets lie past the descriptors' sizes (the hardware writes zeros for those loads and drops those stores).
+    auto a_dma = [&](int buf, int mt) {
+#pragma unroll
+        for (int u = 0; u < K1 / 32; ++u) {
+            const int piece = wave * (K1 / 32) + u;                 // 1 KB of the stage: 4 rows (S) / 2 rows (P)
+            lds_void* dst = (lds_void*)(As + buf * AS + piece * 256);
+            const unsigned off = uadd((unsigned)mt * (32u * 64u * 4u) + (unsigned)piece * (PROJ ? 2u : 4u) * 256u, va[u]);
+            if constexpr (PROJ) {                 // chunks 0 .. 15 from the conv2 output, 16 .. 31 from the block input: two requests with complementary lanes
+                if ((lane & 16) == 0) __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, dst, 16, off, 0, 0, 0);
+                else                  __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, dst, 16, off, 0, 0, 0);
+            } else {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(ar, dst, 16, off, 0, 0, 0);
+            }
+        }
+    };
+    // S: the skip values of this wave's 64 columns of the tile, straight into its block of the T tile: request u brings rows 4 u .. 4 u + 3
+    auto skip_dma = [&](int mt) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rr, (lds_void*)(Ts + wave * 2048 + u * 256), 16,
+                                                     uadd((unsigned)mt * (32u * 1024u) + (unsigned)u * 4096u + (unsigned)wave * 256u, vs[u & 1]), 0, 0, 0);
+    };
+
+    int mt = blockIdx.x, buf = 0;
+    a_dma(0, mt);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    for (; mt < p.m_tiles; mt += nblk, buf ^= 1) {
+        lds_barrier();                            // this tile's A rows have landed (waited for at the end of the pass before); every wave is done with the T tile of the pass before
+        if constexpr (!PROJ) skip_dma(mt);        // (no skip tensor: a descriptor of size 0, the requests write zeros)
+        a_dma(buf ^ 1, mt + nblk);                // always issued (past the last tile: zeros into the idle stage), so the counted waits below hold on every pass
+        __builtin_amdgcn_sched_barrier(0);
+        // the wave's two 32-column blocks one after the other (16 accumulator registers live, not 32); bn3 (+ skip) + ReLU into the wave's block of the T tile
+        const int abase = buf * AS, tqbase = wave * 2048;
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            f32x16 acc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+            for (int g = 0; g < G1; ++g) {
+                const f32x4 af = *reinterpret_cast<const f32x4*>(smem + abase + ax[g & 3] + 32 * (g >> 2));
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tt], w3f[nb][g][tt], acc, 0, 0, 0);
+            }
+            if (!PROJ && nb == 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");      // the skip requests are older than the two A requests: they have landed
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                float* q = smem + tqbase + tq[e & 3] + 64 * ((e & 3) + 8 * (e >> 2)) + 32 * nb;
+                const float v = acc[e] * sc3[nb] + bi3[nb];
+                *q = fmaxf(v + (PROJ ? 0.f : *q), lo3);
+            }
+        }
+        lds_barrier();
+        // T, the block output: 16-byte pieces of whole rows
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            buf_store4(tr, uadd((unsigned)mt * (32u * 1024u) + (unsigned)(r0 + 4 * u) * 1024u, (unsigned)c4 * 16u),
+                       *reinterpret_cast<const f32x4*>(smem + r0 * 64 + tw[u & 1] + 256 * u));
+        // second GEMM: A fragments from the T tile, Y stored straight from the accumulator layout
+        const unsigned ytile = (unsigned)mt * (32u * N2 * 4u) + (unsigned)wave * (PROJ ? 64u : 128u);
+        if constexpr (PROJ) {
+            f32x4 acc2[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                f32x4 tf[2];
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) tf[rb] = *reinterpret_cast<const f32x4*>(smem + tx[q & 1] + 32 * ((q >> 1) & 1) + 2048 * (q >> 2) + 1024 * rb);
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt)
+#pragma unroll
+                    for (int rb = 0; rb < 2; ++rb) acc2[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(tf[rb][tt], w1f[q][tt], acc2[rb], 0, 0, 0);
+            }
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) buf_store1(yr, uadd(ytile + (unsigned)(rb * 16 + r) * (N2 * 4u), vy), fmaxf(acc2[rb][r] * sc1 + bi1, 0.f));
+            asm volatile("s_waitcnt vmcnt(16)" ::: "memory");       // the next tile's A rows were requested before this pass's 8 + 8 stores: wait for them only
+        } else {
+            f32x16 acc2;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc2[e] = 0.f;
+#pragma unroll
+            for (int g = 0; g < 32; ++g) {
+                const f32x4 tf = *reinterpret_cast<const f32x4*>(smem + tx[g & 3] + 32 * ((g >> 2) & 1) + 2048 * (g >> 3));
+#pragma unroll
+                for (int tt = 0; tt < 4; ++tt) acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(tf[tt], w1f[g][tt], acc2, 0, 0, 0);
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) buf_store1(yr, uadd(ytile + (unsigned)((e & 3) + 8 * (e >> 2)) * (N2 * 4u), vy), fmaxf(acc2[e] * sc1 + bi1 + 0.f, 0.f));
+            asm volatile("s_waitcnt vmcnt(24)" ::: "memory");       // ... 8 + 16 stores
+        }
+    }
+}
+
 }  // namespace vatl
 
 using namespace vatl;
@@ -223,4 +423,46 @@ extern "C" int vatl_bottleneck_chain_fwd(const float* a, const float* w3, const 
         meter_route(kRouteChain);
     }
     return check_launch("bottleneck_chain");
+}
+
+static bool form_shape_ok(int Cmid, int Cout, int Cnext, int want_next, int64_t M) {
+    return Cmid == 64 && Cout == 256 && Cnext == want_next && M > 0 && (M + 32) * 256 < (1LL << 30);                // as chain_shape_ok
+}
+
+extern "C" int vatl_chain_proj_supported(int Cmid, int Cout, int Cnext, int64_t M) { return form_shape_ok(Cmid, Cout, Cnext, 64, M) ? 1 : 0; }
+extern "C" int vatl_chain_step_supported(int Cmid, int Cout, int Cnext, int64_t M) { return form_shape_ok(Cmid, Cout, Cnext, 128, M) ? 1 : 0; }
+
+static int chain_form_launch(bool proj, FormParams p, int64_t M, void* stream) {
+    const int N2 = proj ? 64 : 128, K1 = proj ? 128 : 64;
+    const char* what = proj ? "chain_proj" : "chain_step";
+    p.m_tiles = (int)((M + 31) / 32);
+    p.a_bytes = (unsigned)(M * 64 * 4); p.t_bytes = (unsigned)(M * 256 * 4); p.y_bytes = (unsigned)(M * N2 * 4);
+    const int smem = (2 * 32 * K1 + CF_TS) * (int)sizeof(float);
+    static std::atomic<unsigned> c[2] = {{0}, {0}};
+    void (*kern)(FormParams) = chain_form_kernel<false>;
+    if (proj) kern = chain_form_kernel<true>;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), smem, c[proj], what)) return rc;
+    const int grid = p.m_tiles < 512 ? p.m_tiles : 512;                       // two blocks per CU
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, (hipStream_t)stream, p);
+    meter_add(0, 2.0 * ((double)p.m_tiles * 32.0) * 256.0 * (double)(K1 + N2));
+    meter_route(proj ? kRouteChainProj : kRouteChainStep);
+    return check_launch(what);
+}
+
+extern "C" int vatl_chain_proj_fwd(const float* a, const float* x2, const float* w, const float* scale, const float* bias, float* t, const float* w1, const float* scale1,
+                                   const float* bias1, float* y1, int64_t M, int Cmid, int Cout, int Cnext, int relu, void* stream) {
+    if (!a || !x2 || !w || !t || !w1 || !y1) return fail(VATL_EINVAL, "chain_proj_fwd: bad arguments");
+    if (!form_shape_ok(Cmid, Cout, Cnext, 64, M)) return fail(VATL_EINVAL, "chain_proj_fwd: serves 64 + 64 -> 256 -> 64 channels and (M + 32) * 256 < 2^30 pixels x channels");
+    FormParams p{};
+    p.a = a; p.x2 = x2; p.w3 = w; p.scale3 = scale; p.bias3 = bias; p.t = t; p.w1 = w1; p.scale1 = scale1; p.bias1 = bias1; p.y = y1; p.relu3 = relu;
+    return chain_form_launch(true, p, M, stream);
+}
+
+extern "C" int vatl_chain_step_fwd(const float* a, const float* w3, const float* scale3, const float* bias3, const float* skip, float* t, const float* w1,
+                                   const float* scale1, const float* bias1, float* y1, int64_t M, int Cmid, int Cout, int Cnext, void* stream) {
+    if (!a || !w3 || !t || !w1 || !y1) return fail(VATL_EINVAL, "chain_step_fwd: bad arguments");
+    if (!form_shape_ok(Cmid, Cout, Cnext, 128, M)) return fail(VATL_EINVAL, "chain_step_fwd: serves 64 -> 256 -> 128 channels and (M + 32) * 256 < 2^30 pixels x channels");
+    FormParams p{};
+    p.a = a; p.w3 = w3; p.scale3 = scale3; p.bias3 = bias3; p.res = skip; p.t = t; p.w1 = w1; p.scale1 = scale1; p.bias1 = bias1; p.y = y1; p.relu3 = 1;
+    return chain_form_launch(false, p, M, stream);
 }

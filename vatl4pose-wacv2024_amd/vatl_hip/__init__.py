@@ -51,6 +51,10 @@ SIGNATURES = {
     "vatl_conv1x1_rows_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "vatl_bottleneck_chain_supported": (_i, [_i, _i, _i, _i64]),
     "vatl_bottleneck_chain_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "vatl_chain_proj_supported": (_i, [_i, _i, _i, _i64]),
+    "vatl_chain_proj_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
+    "vatl_chain_step_supported": (_i, [_i, _i, _i, _i64]),
+    "vatl_chain_step_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "vatl_stem_pool_weight_floats": (_i64, []),
     "vatl_pack_stem_pool_weight": (_i, [_p, _p, _p]),
     "vatl_stem_pool_supported": (_i, [_i, _i]),
@@ -274,7 +278,7 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
 
 ROUTE_NAMES = ("igemm", "igemm_bnbwd", "igemm_dma", "persistent_1x1", "streamk", "rows_1x1", "bottleneck_chain", "stem_pool", "halo_3x3", "winograd",
                "winograd_2h", "winograd_bnbwd", "winograd_persist", "winograd_c32", "wgrad", "winograd_wgrad", "winograd_wgrad_2h", "winograd_wgrad_table", "winograd_f4", "winograd_f4_bnbwd",
-               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43", "stem_pool_w1d")
+               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43", "stem_pool_w1d", "chain_proj", "chain_step")
 
 
 class flop_meter:
@@ -751,13 +755,26 @@ def conv1x1_rows_supported(k1: int, k2: int, n: int, m: int) -> bool:
     return bool(lib().vatl_conv1x1_rows_supported(k1, k2, n, m))
 
 
-def conv1x1_rows_fwd(a, w, scale, bias, cout: int, relu: bool, residual=None, x2=None, out=None):
-    """relu?(scale * (A W^T) + bias + residual) for K = 128 input channels (a (N,H,W,128), or a (N,H,W,64) + x2 (N,H,W,64)); w [cout][128] packed."""
+def conv1x1_rows_fwd(a, w, scale, bias, cout: int, relu: bool, residual=None, x2=None, out=None, next_conv1=None, y1_out=None):
+    """relu?(scale * (A W^T) + bias + residual) for K = 128 input channels (a (N,H,W,128), or a (N,H,W,64) + x2 (N,H,W,64)); w [cout][128] packed.
+    next_conv1 = (w1, scale1, bias1) of the next block's 256 -> 64 conv1 (two-source form only): the same launch also computes
+    y1 = relu(scale1 * (y W1^T) + bias1) from the tile in LDS (vatl_chain_proj_fwd) and the call returns (y, y1)."""
     n, h, w_, k1 = a.shape
     k2 = 0 if x2 is None else x2.shape[-1]
     assert w.numel() >= cout * (k1 + k2) and (x2 is None or tuple(x2.shape[:3]) == (n, h, w_)) and (residual is None or tuple(residual.shape) == (n, h, w_, cout))
     y = out if out is not None else torch.empty((n, h, w_, cout), device=a.device, dtype=torch.float32)
     assert a.is_contiguous() and y.is_contiguous() and (x2 is None or x2.is_contiguous()) and (residual is None or residual.is_contiguous())
+    if next_conv1 is not None:
+        w1, scale1, bias1 = next_conv1
+        cnext = w1.shape[0]
+        if x2 is None or k2 != k1 or residual is not None:
+            raise VatlError("conv1x1_rows_fwd: next_conv1 goes with the two-source form (a, x2 of 64 channels each) and no residual")
+        assert w1.numel() == cnext * cout
+        y1 = y1_out if y1_out is not None else torch.empty((n, h, w_, cnext), device=a.device, dtype=torch.float32)
+        assert y1.is_contiguous()
+        _check(lib().vatl_chain_proj_fwd(_ptr(a), _ptr(x2), _ptr(w), _ptr(scale), _ptr(bias), _ptr(y), _ptr(w1), _ptr(scale1), _ptr(bias1), _ptr(y1),
+                                         n * h * w_, k1, cout, cnext, int(relu), _stream()), "vatl_chain_proj_fwd")
+        return y, y1
     _check(lib().vatl_conv1x1_rows_fwd(_ptr(a), _ptr(x2), _ptr(w), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n * h * w_, k1, k2, cout, int(relu),
                                        _stream()), "vatl_conv1x1_rows_fwd")
     return y
@@ -767,18 +784,37 @@ def bottleneck_chain_supported(cmid: int, cout: int, cnext: int, m: int) -> bool
     return bool(lib().vatl_bottleneck_chain_supported(cmid, cout, cnext, m))
 
 
-def bottleneck_chain_fwd(a, w3, scale3, bias3, skip, w1=None, scale1=None, bias1=None, out=None, y1_out=None):
+def chain_proj_supported(cmid: int, cout: int, cnext: int, m: int) -> bool:
+    """conv3 + projection of a stage's first block with the next block's conv1 (conv1x1_rows_fwd(..., next_conv1=)): 64 + 64 -> 256 -> 64."""
+    return bool(lib().vatl_chain_proj_supported(cmid, cout, cnext, m))
+
+
+def chain_step_supported(cmid: int, cout: int, cnext: int, m: int) -> bool:
+    """conv3 + skip of a stage's last block with the next stage's first conv1 (bottleneck_chain_fwd(..., next_stage_conv1=)): 64 -> 256 -> 128."""
+    return bool(lib().vatl_chain_step_supported(cmid, cout, cnext, m))
+
+
+def bottleneck_chain_fwd(a, w3, scale3, bias3, skip, w1=None, scale1=None, bias1=None, out=None, y1_out=None, next_stage_conv1=None):
     """t = relu(bn3(conv3(a)) + skip) and, when w1 is given, y1 = relu(bn1(conv1_next(t))) in one launch: a (N,H,W,Cmid), skip (N,H,W,Cout) NHWC,
-    w3 / w1 = packed 1x1 filters (pack_conv_weight).  Returns (t, y1) (y1 None without w1)."""
+    w3 / w1 = packed 1x1 filters (pack_conv_weight).  Returns (t, y1) (y1 None without w1).
+    next_stage_conv1 = (w1, scale1, bias1) of a 256 -> 128 conv1 (the first block of the next stage; not together with w1): the same, through
+    vatl_chain_step_fwd (y1 has the bits of conv1x1_rows_fwd)."""
     n, h, w_, cmid = a.shape
     cout = w3.shape[0]
+    step = next_stage_conv1 is not None
+    if step:
+        if w1 is not None:
+            raise VatlError("bottleneck_chain_fwd: w1 and next_stage_conv1 are exclusive")
+        w1, scale1, bias1 = next_stage_conv1
     cnext = 0 if w1 is None else w1.shape[0]
     assert w3.numel() == cout * cmid and (w1 is None or w1.numel() == cnext * cout) and (skip is None or tuple(skip.shape) == (n, h, w_, cout))
     t = out if out is not None else torch.empty((n, h, w_, cout), device=a.device, dtype=torch.float32)
     assert t.is_contiguous() and a.is_contiguous() and (skip is None or skip.is_contiguous())
     y1 = None if w1 is None else (y1_out if y1_out is not None else torch.empty((n, h, w_, cnext), device=a.device, dtype=torch.float32))
-    _check(lib().vatl_bottleneck_chain_fwd(_ptr(a), _ptr(w3), _ptr(scale3), _ptr(bias3), _ptr(skip), _ptr(t), _ptr(w1), _ptr(scale1), _ptr(bias1), _ptr(y1),
-                                           n * h * w_, cmid, cout, cnext, _stream()), "vatl_bottleneck_chain_fwd")
+    assert y1 is None or y1.is_contiguous()
+    fn, name = (lib().vatl_chain_step_fwd, "vatl_chain_step_fwd") if step else (lib().vatl_bottleneck_chain_fwd, "vatl_bottleneck_chain_fwd")
+    _check(fn(_ptr(a), _ptr(w3), _ptr(scale3), _ptr(bias3), _ptr(skip), _ptr(t), _ptr(w1), _ptr(scale1), _ptr(bias1), _ptr(y1),
+              n * h * w_, cmid, cout, cnext, _stream()), name)
     return t, y1
 
 
