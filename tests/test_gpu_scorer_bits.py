@@ -3,16 +3,18 @@
                          Their contract with the reference is exactness — integer results, HP, decoded coordinates.
   tests/glue_cases.py    tests/golden/glue_bits.npz    the HBM-bound passes of the fine-tune step (csrc/layout.hip, pool.hip, fusion.hip, pack.hip,
                          bn_train.hip): the fused stem tail relies on the pool kernels agreeing bit for bit, and the step on being reproducible.
+  tests/wino43_cases.py  tests/golden/wino43_bits.npz  the F(4x3,2x2) Winograd kernels and their filter packs (csrc/winograd_deconv43.hip, winograd_s2_43.hip,
+                         winograd43.h, winograd_stage.h, tile_order.h) and one layer per route of csrc/conv_winograd.hip's launcher.
 Any moved bit is a failure, whatever moved it."""
 import numpy as np
 import pytest
 
-from tests import glue_cases, scorer_cases
+from tests import glue_cases, scorer_cases, wino43_cases
 
 pytestmark = pytest.mark.gpu
 
-MODULES = (scorer_cases, glue_cases)
-assert not set(scorer_cases.CASES) & set(glue_cases.CASES)
+MODULES = (scorer_cases, glue_cases, wino43_cases)
+assert len({name for m in MODULES for name in m.CASES}) == sum(len(m.CASES) for m in MODULES)
 
 
 @pytest.fixture(scope="module")

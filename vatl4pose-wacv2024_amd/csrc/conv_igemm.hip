@@ -39,6 +39,7 @@
 // The same kernel runs ConvTranspose2d(4,2,1) as four 2x2 sub-pixel phases
 // (blockIdx.y = py*2+px): pad = (1-py, 1-px), output scattered to (2y+py, 2x+px).
 #include "conv_igemm.h"
+#include "tile_order.h"
 #include "tune.h"
 
 #include <algorithm>
@@ -75,12 +76,10 @@ __global__ __launch_bounds__(NT, 2) void conv_igemm_kernel(ConvParams p) {
     const int wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
-    // XCD-aware tile order: block b runs on XCD b%8; give each XCD a contiguous
-    // run of tiles with the n-tile fastest so the blocks sharing an A panel hit
-    // the same L2 (bijective for any grid size).
+    // XCD-aware tile order (tile_order.h): each XCD a contiguous run of tiles with the n-tile fastest, so the
+    // blocks sharing an A panel hit the same L2
     const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, loc = bid >> 3, q = nblk >> 3, r8 = nblk & 7;
-    const int t = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+    const int t = xcd_contiguous_index(bid, nblk);
     int m_tile, n_tile;
     if (p.order == 0) { m_tile = t / p.n_tiles; n_tile = t - m_tile * p.n_tiles; }
     else              { n_tile = t / p.m_tiles; m_tile = t - n_tile * p.m_tiles; }
@@ -407,9 +406,7 @@ __device__ __forceinline__ void conv_igemm_dma_body(const ConvParams& p, float* 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, loc = bid >> 3, q = nblk >> 3, r8 = nblk & 7;
-    const int t = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+    const int t = xcd_contiguous_index(blockIdx.x, gridDim.x);
     const int m_tile = t / p.n_tiles;
     const int n_tile = t - m_tile * p.n_tiles;
     const int m0 = m_tile * BM, n0 = n_tile * BN;

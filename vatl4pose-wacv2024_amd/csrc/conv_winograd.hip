@@ -40,7 +40,9 @@
 // The per-output arithmetic depends only on the tile's own pixels: results are independent of the batch position (SURVEY.md §7 hard part 3).
 #include "common.h"
 #include "buffer.h"
+#include "tile_order.h"
 #include "tune.h"
+#include "winograd_stage.h"
 #include "winograd_pack.h"
 
 #include <algorithm>
@@ -96,42 +98,23 @@ struct WinoParams {
 
 constexpr unsigned WOOB_BASE = 0xF0000000u;               // out of range for every descriptor, and still so with a fragment offset added
 constexpr unsigned WOOB = 0xFFFFFFFFu;
-constexpr unsigned WOOB_G = 0xFFFF0000u;                  // staging offset of a zero piece: still out of range with stage * 64 bytes added (stages < 1024, tensors <= 0xFFFF0000 bytes: checked on the host), so the per-stage offset needs no select
-
-constexpr int W_TB = 32;                        // tiles per block
-constexpr int W_CK = 16;                        // channels per LDS stage
-constexpr int W_NQ = W_TB + 1;                  // entries of a column array: one per tile + the halo of the last tile
 constexpr int W_ZERO = 16;                      // floats of the zero pixel in front of the stages
 constexpr int W_LDP = 32;                       // row stride of the output-transform tiles in LDS
-// LDS stage: [4 input rows i][MO column arrays r][33 entries q][16 channels]; entry (r, q) = column r of tile q (= column MO + r of tile q - 1)
-template <int MO> struct WinoStage {
-    static constexpr int ROWE = MO * W_NQ + 1;             // entries per input row: MO column arrays of W_NQ + ONE ZERO ENTRY (its four pieces are requested out of range by
-                                                           // every stage): the column of a tile that lies outside the image reads it — at the same index in every row, so the
-                                                           // fragment reads need no per-lane select (2 per column and step before; vector instructions are not hidden behind the MFMAs)
-    static constexpr int ITEMS = 4 * ROWE * 4;             // 16-byte pieces
-    static constexpr int NDMA = (ITEMS + 63) / 64;         // wave-wide LDS-DMA instructions (1 KB each; the last one is partly used)
-    static constexpr int FLOATS = NDMA * 256;
-    static constexpr int NLD = (NDMA + 3) / 4;             // per wave
-};
-
 // (body in a __device__ function: with the DMA builtin inside the __global__ template hipcc 7.2 drops the kernel's host stub)
 template <int MO, bool BNB, bool GATHER, int NB>
 __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, const int bid, const int nblk) {
     constexpr int NT = 256, BN = 32 * NB, NW = 4;       // NB: 32-channel halves of the filter tile per block (2: the staged pixels and their transform serve 64 output channels)
     using ST = WinoStage<MO>;
-    constexpr int W_NLD = ST::NLD, STAGE = ST::FLOATS, ROWF = ST::ROWE * W_CK;   // DMA instructions per wave, floats per stage / per input row
+    constexpr int W_NLD = ST::NLD, STAGE = ST::FLOATS, ROWF = ST::ROWF;   // DMA instructions per wave, floats per stage / per input row
     float* Rs = smem + W_ZERO;                             // [2][4 rows][MO arrays][33 entries][16 channels], chunk-swizzled
 
     int tid_ = threadIdx.x;
     if constexpr (GATHER) asm volatile("" : "+v"(tid_));   // (part of the gather instantiations' loop form, see winograd_kernel)
     const int tid = tid_, lane = tid & 63, xi = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // XCD-aware tile order: block b runs on XCD b % 8; each XCD gets a contiguous run of the sequence
-    //     for (group of rn filter slices) for (m-tile) for (slice in the group)        slice = (phase, 32 output channels)
-    // so the blocks that are resident together read the same input tiles (fetched from HBM once per group instead of once per slice)
-    // while the group's filter slices (rn * Cin * 2 KB <= 2 MB) stay in that XCD's L2 for the whole sweep over the m-tiles.
-    const int xcd = bid & 7, loc = bid >> 3, q8 = nblk >> 3, r8 = nblk & 7;
-    const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    // XCD-contiguous, grouped tile order (tile_order.h): slice = (phase, 32 NB output channels), rn * Cin * 2 KB <= 2 MB per group.
+    // (The decode below is tile_order.h's grouped_tile, kept as text here: through the function every instantiation compiles to other code.)
+    const int t = xcd_contiguous_index(bid, nblk);
     const int units = p.n_tiles * (p.deconv ? 4 : 1);      // (gather mode: deconv = 0, the four input phases are part of the reduction)
     const int grp = fdiv(t, p.d_grp), rem = t - grp * (p.m_tiles * p.rn);
     const bool last_grp = units - grp * p.rn < p.rn;       // the last group may be smaller
@@ -168,16 +151,9 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
         for (int nu = 0; nu < 4; ++nu) ua[nu] = buf_load4(ur, (abl & 4) ? WOOB : u0 + nu * (p.nhp * 1024u));
     }
 
-    // ---- staging by LDS-DMA (buffer_load ... lds: no staging registers, no ds_write pass).  The destination of a wave instruction is
-    // lane-linear (base + lane * 16 bytes), so the chunk swizzle is applied on the SOURCE side: LDS position p = (entry p >> 2, chunk
-    // position p & 3) receives the entry's global chunk (p & 3) ^ ((q >> 2) & 3).
-    // Column arrays: pixel column j of tile t (x = MO tx + j - pad) lives in array r = j % MO at entry q = t + j / MO — the tile index
-    // is FLAT, so consecutive tiles are consecutive 64-byte entries even across tile-row ends and the 16 lanes of a ds_read_b128 group
-    // ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31}) hit 16 different 16-byte bank slots (with one slot per distinct pixel column —
-    // stride MO between tiles and a gap at row ends — every fragment read was a 3-way bank conflict: SQ_LDS_BANK_CONFLICT 65 % of the
-    // LDS cycles).  At a row end entry (r, q) is asked for by two tiles: column r of tile q (first of its row: x = r - pad) and
-    // column MO + r of tile q - 1 (last of its row: x = MO TW + r - pad) — never both inside the image; the entry holds whichever is,
-    // and a tile whose column is outside the image reads the zero pixel instead.
+    // ---- staging by LDS-DMA into the column arrays of winograd_stage.h (layout, chunk swizzle, row ends and zero pieces: explained there).
+    // (The offset computation below is winograd_stage.h's wino_piece_offset, kept as text here and in winograd_persist_body: through the function the
+    // gather and the persistent instantiations compile to other code — the gather ones with 61 instead of 19 spilled scalar registers.)
     unsigned goff[W_NLD];                                  // byte offset of the lane's piece in the first stage (WOOB_G: zeros)
     auto set_goff = [&](int ph) {                          // ph: input phase of the gather mode (0 otherwise)
         const int gy = ph >> 1, gx = ph & 1;
@@ -246,11 +222,7 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
         for (int v = 0; v < (GATHER ? 2 : 1); ++v) {
             const int px_ = GATHER ? v : pad_x;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int xx = MO * tx + j - px_;
-                const int q = tl + j / MO;
-                ra[v][j] = (unsigned)xx < (unsigned)p.W ? ((j % MO) * W_NQ + q) * W_CK + ((h ^ ((q >> 2) & 3)) << 2) : MO * W_NQ * W_CK + (h << 2);
-            }
+            for (int j = 0; j < 4; ++j) ra[v][j] = wino_frag_col<MO>(j, tl, h, tx, px_, p.W);
         }
     }
     // row transform of this wave: t = d[ia] + sgn * d[ib]   (B^T rows: d0 - d2, d1 + d2, d2 - d1, d1 - d3)
@@ -603,15 +575,14 @@ template <int NB, bool PF>
 __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float* smem) {
     constexpr int MO = 2, NT = 256, BN = 32 * NB, NW = 4;
     using ST = WinoStage<MO>;
-    constexpr int W_NLD = ST::NLD, STAGE = ST::FLOATS, ROWF = ST::ROWE * W_CK;
+    constexpr int W_NLD = ST::NLD, STAGE = ST::FLOATS, ROWF = ST::ROWF;
     float* Rs = smem + W_ZERO;
     const int tid = threadIdx.x, lane = tid & 63, xi = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // block -> (part, group of the period, filter tile); consecutive ids of the sequence on one XCD (block b runs on XCD b % 8), the
     // filter tile fastest: the blocks that read the same staged pixels are neighbours in time and share an L2
     const int bid = blockIdx.x, nblk = gridDim.x;
-    const int xcd = bid & 7, loc = bid >> 3, q8 = nblk >> 3, r8 = nblk & 7;
-    const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    const int t = xcd_contiguous_index(bid, nblk);
     const int units = p.pg * p.n_tiles;
     const int part = fdiv(t, p.d_grp), unit = t - part * units;
     const int slot = fdiv(unit, p.d_ntiles), n_tile = unit - slot * p.n_tiles;
@@ -620,7 +591,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
     const int m0 = slot * W_TB, n0 = n_tile * BN;
     const int Lt = p.pg * W_TB;                            // tiles of one period (whole images): the geometry below is that of period 0
 
-    // ---- staging offsets (see winograd_body: one slot per distinct pixel column of a tile row, chunk swizzle on the source side) ----
+    // ---- staging offsets (winograd_stage.h; this file's copy of wino_piece_offset, see winograd_body) ----
     // The geometry of the block — staging offsets, fragment addresses, store offsets: 16 words per thread — is parked in LDS behind the stage
     // buffers and read back at the top of every period (staging / fragment part) and before the write-out (store part): as plain loop invariants
     // these 13 values stay live across the MFMA loop AND the write-out, and the two-half kernel spilled 22 - 53 registers into the stage loop.
@@ -661,11 +632,7 @@ __device__ __forceinline__ void winograd_persist_body(const WinoParams& p, float
         const int m = m0 + tl;                             // < Lt: a period holds whole groups
         const int gr = fdiv(m, p.d_TW), tx = m - gr * p.TW;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int xx = MO * tx + j - 1;
-            const int q = tl + j / MO;
-            ra[j] = (unsigned)xx < (unsigned)p.W ? ((j % MO) * W_NQ + q) * W_CK + ((h ^ ((q >> 2) & 3)) << 2) : MO * W_NQ * W_CK + (h << 2);
-        }
+        for (int j = 0; j < 4; ++j) ra[j] = wino_frag_col<MO>(j, tl, h, tx, 1, p.W);
         Gs[NT + tid] = u32x4{g0[4], ((unsigned)ra[0] & 0xFFFFu) | ((unsigned)ra[1] << 16), ((unsigned)ra[2] & 0xFFFFu) | ((unsigned)ra[3] << 16), 0u};
     }
     const int ia = xi == 0 ? 0 : (xi == 2 ? 2 : 1);
@@ -1139,11 +1106,9 @@ static int winograd_impl(int MO, const float* x, const float* u, const float* sc
     // a slice is Cin * 2 KB (x 4 input phases in the gather mode); at least two per group (deconv1, Cin = 2048: 4 MB slices, 4326 -> 4135 us
     // with two), unless the knob says 0
     const int gkb = g_wino_group_kb.load(std::memory_order_relaxed);
-    p.rn = std::max(1, std::min(p.n_tiles * phases, std::max(gkb > 0 ? 2 : 1, gkb / (2 * Cin * NBh * (gather ? 4 : 1)))));
     const int units = p.n_tiles * phases;
-    p.d_TH = make_fastdiv(p.TH); p.d_TW = make_fastdiv(p.TW); p.d_tpi = make_fastdiv(p.tpi);
-    p.d_grp = make_fastdiv((unsigned)(p.m_tiles * p.rn)); p.d_rn = make_fastdiv(p.rn); p.d_ntiles = make_fastdiv(p.n_tiles);
-    p.d_rn_last = make_fastdiv(units % p.rn ? units % p.rn : p.rn);
+    set_grouped_order(p, units, std::max(1, std::min(units, std::max(gkb > 0 ? 2 : 1, gkb / (2 * Cin * NBh * (gather ? 4 : 1))))));
+    p.d_TH = make_fastdiv(p.TH); p.d_TW = make_fastdiv(p.TW); p.d_tpi = make_fastdiv(p.tpi); p.d_ntiles = make_fastdiv(p.n_tiles);
     if ((long long)p.m_tiles * units >= (1LL << 31)) return fail(VATL_EINVAL, "winograd: too many blocks");
     if (fuse) {
         if (deconv) return fail(VATL_EINVAL, "winograd: the BatchNorm-backward epilogue exists for the data-gradient launches only");

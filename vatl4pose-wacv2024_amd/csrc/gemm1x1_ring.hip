@@ -1,5 +1,6 @@
 // The LDS-DMA ring GEMM for the long-K 1x1 layers: kernel, launcher, the gate dispatch() asks (ring_wanted) and knob 27.
 #include "conv_igemm.h"
+#include "tile_order.h"
 #include "tune.h"
 
 namespace vatl {
@@ -46,9 +47,7 @@ __device__ __forceinline__ void gemm1x1_ring_body(const ConvParams& p, float* sm
     const int wm = wave >> 1, wn = wave & 1;      // 2 x 2 waves of 64 x 64
 
     // tile order of conv_igemm_kernel (order 0): each XCD a contiguous run, n-tile fastest
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, loc = bid >> 3, q = nblk >> 3, r8 = nblk & 7;
-    const int t = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+    const int t = xcd_contiguous_index(blockIdx.x, gridDim.x);
     const int m_tile = t / p.n_tiles, n_tile = t - m_tile * p.n_tiles;
     const int m0 = m_tile * 128, n0 = n_tile * 128;
 

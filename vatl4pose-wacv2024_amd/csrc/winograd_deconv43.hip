@@ -8,26 +8,22 @@
 //
 //     Y = A4^T [ (G4 g G3^T) .* (B4^T d B3) ] A3        U = G4 g G3^T: 20 values per filter, packed once (winograd_pack.h: wino43_pack_block)
 //
-//     B4^T = [2 -1 -2 1 0; 0 -2 -1 1 0; 0 2 -3 1 0; 0 -1 0 1 0; 0 2 -1 -2 1]      A4^T = [1 1 1 1 0; 0 1 -1 2 0; 0 1 1 4 0; 0 1 -1 8 1]
-//     B3^T, A3^T: those of conv_winograd.hip (rows d0 - d2, d1 + d2, d2 - d1, d1 - d3;  [1 1 1 0; 0 1 -1 0; 0 1 1 1])
-//
 // About twice the rounding error of F(3x3,2x2) (the factors 2, 3, 8 of the vertical transform); tests hold both to the same float64 bound.
 //
-// The block follows winograd_body's two-half form: 32 tiles (flat index over image, tile row, tile column) x 64 output channels x one
-// phase, four waves, two blocks per CU.  What differs:
-//   * wave nu owns COLUMN position nu and all five row positions (there: wave xi owns row position xi): 5 positions x 2 halves x 16 = 160
-//     accumulator registers.  Per 8-channel step a wave reads its two columns of the five staged rows (10 ds_read_b128), forms the column
-//     combination per row, then the five row combinations, and issues 40 MFMAs 32x32x2 (20 per 32-channel half, the two filter-fragment sets
-//     of 20 registers alternating between the halves one group ahead).
-//   * a stage holds 5 input rows: [5][3 column arrays of 33 entries + one zero entry][16 channels] = 2000 sixteen-byte pieces, 32 LDS-DMA
-//     instructions, 32 KB; two stages.  Column arrays, flat tile index, chunk swizzle on the source side and the zero entry are winograd_body's.
+// The matrices, the block (32 tiles x 64 output channels, wave nu = column position nu x all five row positions), the row transform and the MFMA
+// group are winograd43.h's, shared with winograd_s2_43.hip; the stage and its offsets winograd_stage.h's; the tile order tile_order.h's.  This file's:
+//   * one phase per block — the tile unit is (phase, 64 channels) — with that phase's padding and filter;
+//   * per 8-channel step a wave reads its two columns of the five staged rows (10 ds_read_b128) and issues 40 MFMAs 32x32x2 (20 per 32-channel
+//     half, the two filter-fragment sets of 20 registers alternating between the halves one group ahead);
 //   * output transform: the xi sum (5 -> 4 rows) in registers, the nu sum (4 -> 3 columns) through LDS — [4 nu][4 rows][32 tiles][32 channels]
 //     is exactly the two stage buffers — one 32-channel half at a time; a thread owns (tile, channel quad) and walks the four rows, so a
-//     wave reads 1 KB contiguous per (nu, row) and stores 128-byte NHWC channel runs with scale / bias / ReLU.
+//     wave reads 1 KB contiguous per (nu, row) and stores 128-byte NHWC channel runs with scale / bias / ReLU into the phase's pixels of the
+//     2H x 2W output.  (winograd_s2_43.hip has the same transform as text: as one function called from both, this kernel spills a register.)
 // The per-output arithmetic depends only on the tile's own pixels: results do not depend on the batch position.
 #include "common.h"
 #include "buffer.h"
-#include "winograd_pack.h"
+#include "tile_order.h"
+#include "winograd43.h"
 
 #include <algorithm>
 #include <atomic>
@@ -51,37 +47,17 @@ struct Deconv43Params {
     FastDivU d_TH, d_TW, d_tpi, d_grp, d_rn, d_rn_last, d_ntiles;
 };
 
-constexpr unsigned D43_OOB = 0xFFFF0000u;      // staging offset of a zero piece: out of range for every tensor the host accepts, still so with stage * 64 bytes added
-constexpr int D43_TB = 32;                     // tiles per block
-constexpr int D43_CK = 16;                     // channels per LDS stage
-constexpr int D43_NQ = D43_TB + 1;             // entries of a column array: one per tile + the halo of the last tile
-constexpr int D43_ROWE = 3 * D43_NQ + 1;       // entries per input row: three column arrays + the zero entry
-constexpr int D43_ROWF = D43_ROWE * D43_CK;    // floats per input row
-constexpr int D43_ITEMS = 5 * D43_ROWE * 4;    // 16-byte pieces of a stage
-constexpr int D43_NDMA = (D43_ITEMS + 63) / 64;
-constexpr int D43_STAGE = D43_NDMA * 256;      // floats per stage
-constexpr int D43_NLD = D43_NDMA / 4;          // DMA instructions per wave and stage
-constexpr int D43_LDS_BYTES = 2 * D43_STAGE * 4;
-static_assert(D43_NDMA % 4 == 0 && 16 * D43_TB * 32 * 4 == D43_LDS_BYTES, "stage buffers = output-transform tiles");
-
 // (body in a __device__ function, as winograd_body: with the DMA builtin inside the __global__ function hipcc drops the kernel's host stub)
 __device__ __forceinline__ void winograd_deconv43_body(const Deconv43Params& p, float* smem) {
     constexpr int NW = 4;
     float* Rs = smem;                                      // [2][5 rows][3 arrays x 33 entries + zero entry][16 channels], chunk-swizzled
     const int tid = threadIdx.x, lane = tid & 63, nu = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    // XCD-aware tile order of winograd_body: block b runs on XCD b % 8; each XCD gets a contiguous run of
-    //     for (group of rn filter slices) for (m-tile) for (slice in the group)        slice = (phase, 64 output channels)
-    const int bid = blockIdx.x, nblk = gridDim.x;
-    const int xcd = bid & 7, loc = bid >> 3, q8 = nblk >> 3, r8 = nblk & 7;
-    const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-    const int units = p.n_tiles * 4;
-    const int grp = fdiv(t, p.d_grp), rem = t - grp * (p.m_tiles * p.rn);
-    const bool last_grp = units - grp * p.rn < p.rn;
-    const int rn_g = last_grp ? units - grp * p.rn : p.rn;
-    const int m_tile = fdiv(rem, last_grp ? p.d_rn_last : p.d_rn), unit = grp * p.rn + (rem - m_tile * rn_g);
+    // tile order (tile_order.h): slice = (phase, 64 output channels)
+    int m_tile, unit;
+    grouped_tile(p, xcd_contiguous_index(blockIdx.x, gridDim.x), p.n_tiles * 4, m_tile, unit);
     const int phase = fdiv(unit, p.d_ntiles), n_tile = unit - phase * p.n_tiles;
-    const int m0 = m_tile * D43_TB, n0 = n_tile * 64;
+    const int m0 = m_tile * W_TB, n0 = n_tile * 64;
     const int py = phase >> 1, px = phase & 1;
     const int pad_y = 1 - py, pad_x = 1 - px;
 
@@ -100,37 +76,16 @@ __device__ __forceinline__ void winograd_deconv43_body(const Deconv43Params& p, 
     f32x4 ua[5], ub[5];
     u_load(ua, 0, 0);
 
-    // ---- staging by LDS-DMA: winograd_body's loader with five input rows (rows 4 ty - pad_y + i) -------------------------------------
-    unsigned goff[D43_NLD];
+    // ---- staging by LDS-DMA (winograd_stage.h): five input rows 4 ty - pad_y + i of the dense image -----------------------------------------
+    unsigned goff[W43_NLD];
 #pragma unroll
-    for (int u = 0; u < D43_NLD; ++u) {
-        const int pz = (nu + NW * u) * 64 + lane;
-        goff[u] = D43_OOB;
-        if (pz >= D43_ITEMS) continue;
-        const int cpos = pz & 3, e = pz >> 2;
-        const int i = e / D43_ROWE, re = e - i * D43_ROWE;
-        const int r = re / D43_NQ, q = re - r * D43_NQ;
-        if (r >= 3) continue;                              // the row's zero entry
-        const int chunk = cpos ^ ((q >> 2) & 3);
-        int m = m0 + q;                                    // column r of tile m ...
-        int gr = fdiv(m, p.d_TW), tx = m - gr * p.TW;
-        int xx = 3 * tx + r - pad_x;
-        if (m >= p.Mtiles || (tx == 0 && xx < 0)) {        // ... or, when that is outside, column 3 + r of the tile before (a row end / the halo)
-            m -= 1;
-            if (m < 0) continue;
-            gr = fdiv(m, p.d_TW); tx = m - gr * p.TW;
-            xx = 3 * tx + 3 + r - pad_x;
-        }
-        const int b = fdiv(gr, p.d_TH), ty = gr - b * p.TH;
-        const int yy = 4 * ty - pad_y + i;
-        if (m < p.Mtiles && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W)
-            goff[u] = (unsigned)(((b * p.H + yy) * p.W + xx) * p.Cin + chunk * 4) << 2;
-    }
+    for (int u = 0; u < W43_NLD; ++u)
+        goff[u] = wino_piece_offset<W43Stage, 3, 4, false>(p, (nu + NW * u) * 64 + lane, m0, p.Mtiles, pad_y, pad_x, p.H, p.W);
     auto stage_dma = [&](int buf, int st) {
 #pragma unroll
-        for (int u = 0; u < D43_NLD; ++u)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void*)(Rs + buf * D43_STAGE + (nu + NW * u) * 256), 16,
-                                                     goff[u] + (unsigned)st * (D43_CK * 4), 0, 0, 0);
+        for (int u = 0; u < W43_NLD; ++u)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void*)(Rs + buf * W43Stage::FLOATS + (nu + NW * u) * 256), 16,
+                                                     goff[u] + (unsigned)st * (W_CK * 4), 0, 0, 0);
     };
     stage_dma(0, 0);
     if (p.stages > 1) stage_dma(1, 1);
@@ -139,20 +94,14 @@ __device__ __forceinline__ void winograd_deconv43_body(const Deconv43Params& p, 
     // (B3^T rows: d0 - d2, d1 + d2, d2 - d1, d1 - d3).  ca / cb: float index (relative to a stage's input row, first 8-channel step) of the
     // two columns of the lane's tile; the second step is the same index ^ 8; a column outside the image = the row's zero entry.
     const int h = lane >> 5;
-    const int ja = nu == 0 ? 0 : (nu == 2 ? 2 : 1);
-    const int jb = nu == 0 ? 2 : (nu == 1 ? 2 : (nu == 2 ? 1 : 3));
     const float sgn = nu == 1 ? 1.f : -1.f;
     int ca, cb;
     {
         const int tl = lane & 31;
         const int m = min(m0 + tl, p.Mtiles - 1);
         const int gr = fdiv(m, p.d_TW), tx = m - gr * p.TW;
-        auto col = [&](int j) {
-            const int xx = 3 * tx + j - pad_x;
-            const int q = tl + j / 3;
-            return (unsigned)xx < (unsigned)p.W ? ((j % 3) * D43_NQ + q) * D43_CK + ((h ^ ((q >> 2) & 3)) << 2) : 3 * D43_NQ * D43_CK + (h << 2);
-        };
-        ca = col(ja); cb = col(jb);
+        ca = wino_frag_col<3>(w43_col_a(nu), tl, h, tx, pad_x, p.W);
+        cb = wino_frag_col<3>(w43_col_b(nu), tl, h, tx, pad_x, p.W);
     }
 
     f32x16 accs[2][5];
@@ -166,54 +115,30 @@ __device__ __forceinline__ void winograd_deconv43_body(const Deconv43Params& p, 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's DMA pieces have landed
     __syncthreads();
 
-    // V = B4^T d B3 of the lane's tile: this wave's five positions, four channels
-    auto make_v = [&](f32x4 (&v)[5], const float* Rb, int x8) {
-        f32x4 tc[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const f32x4 da = *reinterpret_cast<const f32x4*>(Rb + i * D43_ROWF + (ca ^ x8));
-            const f32x4 db = *reinterpret_cast<const f32x4*>(Rb + i * D43_ROWF + (cb ^ x8));
-            tc[i] = da + sgn * db;
-        }
-        const f32x4 s = tc[3] - tc[1];
-        v[0] = 2.f * (tc[0] - tc[2]) + s;                  // 2 t0 -   t1 - 2 t2 +   t3
-        v[1] = s - (tc[1] + tc[2]);                        //      - 2 t1 -   t2 +   t3
-        v[2] = 2.f * tc[1] + (tc[3] - 3.f * tc[2]);        //        2 t1 - 3 t2 +   t3
-        v[3] = s;                                          //      -   t1        +   t3
-        v[4] = (tc[4] - tc[2]) - 2.f * s;                  //        2 t1 -   t2 - 2 t3 + t4
-    };
-    auto mfma_group = [&](f32x16 (&ac)[5], const f32x4 (&v)[5], const f32x4 (&uu)[5]) {
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-            for (int xi = 0; xi < 5; ++xi)
-                ac[xi] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[xi][tt], uu[xi][tt], ac[xi], 0, 0, 0);
-    };
-
     // The two fragment sets alternate between the halves with a look-ahead of one group of 20 MFMAs: (step 0, half 0) = ua [requested in the
     // stage before], (step 0, half 1) = ub, (step 1, half 0) = ua, ...  The scheduler barriers keep the requests where they are written.
     for (int st = 0; st < p.stages; ++st) {
         const int buf = st & 1;
-        const float* Rb = Rs + buf * D43_STAGE;
+        const float* Rb = Rs + buf * W43Stage::FLOATS;
         f32x4 v[5];
         u_load(ub, 2 * st, 1);
         __builtin_amdgcn_sched_barrier(0);
-        make_v(v, Rb, 0);
-        mfma_group(accs[0], v, ua);
+        w43_make_v<5>(v, Rb, ca, cb, sgn, 0);
+        w43_mfma_group<5>(accs[0], v, ua);
         __builtin_amdgcn_sched_barrier(0);
         u_load(ua, 2 * st + 1, 0);
         __builtin_amdgcn_sched_barrier(0);
-        mfma_group(accs[1], v, ub);
+        w43_mfma_group<5>(accs[1], v, ub);
         __builtin_amdgcn_sched_barrier(0);
         u_load(ub, 2 * st + 1, 1);
         if (st + 1 < p.stages && st > 0) stage_dma(buf ^ 1, st + 1);       // (behind the fragments of this stage's second step: loads retire in order)
         __builtin_amdgcn_sched_barrier(0);
-        make_v(v, Rb, 8);
-        mfma_group(accs[0], v, ua);
+        w43_make_v<5>(v, Rb, ca, cb, sgn, 8);
+        w43_mfma_group<5>(accs[0], v, ua);
         __builtin_amdgcn_sched_barrier(0);
         u_load(ua, 2 * st + 2, 0);
         __builtin_amdgcn_sched_barrier(0);
-        mfma_group(accs[1], v, ub);
+        w43_mfma_group<5>(accs[1], v, ub);
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of the next stage have landed
         __syncthreads();
@@ -249,10 +174,10 @@ __device__ __forceinline__ void winograd_deconv43_body(const Deconv43Params& p, 
             for (int e = 0; e < 16; ++e) {
                 const int row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
                 const float sum = ac[1][e] + ac[2][e], dif = ac[1][e] - ac[2][e], m3 = ac[3][e];
-                Ps[((nu * 4 + 0) * D43_TB + row) * 32 + cl] = ac[0][e] + sum + m3;
-                Ps[((nu * 4 + 1) * D43_TB + row) * 32 + cl] = dif + 2.f * m3;
-                Ps[((nu * 4 + 2) * D43_TB + row) * 32 + cl] = sum + 4.f * m3;
-                Ps[((nu * 4 + 3) * D43_TB + row) * 32 + cl] = dif + 8.f * m3 + ac[4][e];
+                Ps[((nu * 4 + 0) * W_TB + row) * 32 + cl] = ac[0][e] + sum + m3;
+                Ps[((nu * 4 + 1) * W_TB + row) * 32 + cl] = dif + 2.f * m3;
+                Ps[((nu * 4 + 2) * W_TB + row) * 32 + cl] = sum + 4.f * m3;
+                Ps[((nu * 4 + 3) * W_TB + row) * 32 + cl] = dif + 8.f * m3 + ac[4][e];
             }
         }
         lds_barrier();
@@ -261,7 +186,7 @@ __device__ __forceinline__ void winograd_deconv43_body(const Deconv43Params& p, 
         for (int a = 0; a < 4; ++a) {
             f32x4 pq[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) pq[k] = *reinterpret_cast<const f32x4*>(&Ps[((k * 4 + a) * D43_TB + tl) * 32 + c4 * 4]);
+            for (int k = 0; k < 4; ++k) pq[k] = *reinterpret_cast<const f32x4*>(&Ps[((k * 4 + a) * W_TB + tl) * 32 + c4 * 4]);
             f32x4 yv[3];
             yv[0] = pq[0] + pq[1] + pq[2];
             yv[1] = pq[1] - pq[2];
@@ -287,13 +212,6 @@ __global__ __launch_bounds__(256, 2) void winograd_deconv43_kernel(Deconv43Param
 
 static std::atomic<unsigned> g_d43_lds_done;
 
-// tensors within the 32-bit byte offsets of the buffer descriptors (the bounds of conv_winograd.hip's host check)
-static bool d43_in_range(long long N, int H, int W, int Cin, int Cout) {
-    const long long mt = N * (H / 4) * (W / 3), xe = N * H * W * Cin, ye = 4 * N * H * W * Cout, ue = 20LL * Cout * Cin;
-    return xe <= (long long)(D43_OOB / 4) && ye < (1LL << 30) && ue < (1LL << 28) && mt < (1LL << 30) && Cin / D43_CK < 1024 &&
-           (mt + D43_TB - 1) / D43_TB * (Cout / 64) * 4 < (1LL << 31);
-}
-
 }  // namespace vatl
 
 using namespace vatl;
@@ -301,7 +219,8 @@ using namespace vatl;
 extern "C" int vatl_deconv4x4s2_winograd43_supported(int N, int H, int W, int Cin, int Cout) {
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return 0;
     if (H % 4 != 0 || W % 3 != 0 || Cin % 16 != 0 || Cout % 64 != 0) return 0;
-    return d43_in_range(N, H, W, Cin, Cout) ? 1 : 0;
+    const w43_count n = N;
+    return w43_in_range(n * (H / 4) * (W / 3), n * H * W * Cin, 4 * n * H * W * Cout, (w43_count)20 * Cout * Cin, Cin, Cout / 64 * 4) ? 1 : 0;
 }
 
 extern "C" int vatl_deconv4x4s2_winograd43_fwd(const float* x, const float* u, const float* scale, const float* bias, float* y, int N, int H, int W,
@@ -315,22 +234,20 @@ extern "C" int vatl_deconv4x4s2_winograd43_fwd(const float* x, const float* u, c
     p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
     p.TH = H / 4; p.TW = W / 3; p.tpi = p.TH * p.TW;
     p.Mtiles = N * p.tpi;
-    p.m_tiles = cdiv(p.Mtiles, D43_TB);
+    p.m_tiles = cdiv(p.Mtiles, W_TB);
     p.n_tiles = Cout / 64;
-    p.stages = Cin / D43_CK;
+    p.stages = Cin / W_CK;
     p.u_phase_floats = 20LL * Cout * Cin;
     p.x_bytes = (unsigned)((long long)N * H * W * Cin * 4);
     p.y_bytes = (unsigned)(4LL * N * H * W * Cout * 4);
     p.u_bytes = (unsigned)(p.u_phase_floats * 4);
     // a slice (phase, 64 channels) is Cin * 5 KB; the slices of a group (<= 2 MB, at least two) stay in an XCD's L2 over the sweep of the m-tiles
     const int units = p.n_tiles * 4;
-    p.rn = std::max(1, std::min(units, std::max(2, 2048 / (5 * Cin))));
-    p.d_TH = make_fastdiv(p.TH); p.d_TW = make_fastdiv(p.TW); p.d_tpi = make_fastdiv(p.tpi);
-    p.d_grp = make_fastdiv((unsigned)(p.m_tiles * p.rn)); p.d_rn = make_fastdiv(p.rn); p.d_ntiles = make_fastdiv(p.n_tiles);
-    p.d_rn_last = make_fastdiv(units % p.rn ? units % p.rn : p.rn);
-    if (int rc = ensure_dynamic_lds((const void*)winograd_deconv43_kernel, D43_LDS_BYTES, g_d43_lds_done, "winograd_deconv43")) return rc;
-    hipLaunchKernelGGL(winograd_deconv43_kernel, dim3((unsigned)(p.m_tiles * units)), dim3(256), D43_LDS_BYTES, (hipStream_t)stream, p);
-    meter_add(1, 2.0 * ((double)p.m_tiles * D43_TB) * 20.0 * (double)Cin * (double)Cout * 4.0);
+    set_grouped_order(p, units, std::max(1, std::min(units, std::max(2, 2048 / (5 * Cin)))));
+    p.d_TH = make_fastdiv(p.TH); p.d_TW = make_fastdiv(p.TW); p.d_tpi = make_fastdiv(p.tpi); p.d_ntiles = make_fastdiv(p.n_tiles);
+    if (int rc = ensure_dynamic_lds((const void*)winograd_deconv43_kernel, W43_LDS_BYTES, g_d43_lds_done, "winograd_deconv43")) return rc;
+    hipLaunchKernelGGL(winograd_deconv43_kernel, dim3((unsigned)(p.m_tiles * units)), dim3(256), W43_LDS_BYTES, (hipStream_t)stream, p);
+    meter_add(1, 2.0 * ((double)p.m_tiles * W_TB) * 20.0 * (double)Cin * (double)Cout * 4.0);
     meter_route(kRouteWinoDeconv43);
     return check_launch("winograd_deconv43");
 }

@@ -79,12 +79,31 @@ __device__ __forceinline__ void wino_pack_block(const float* __restrict__ w, flo
     }
 }
 
-// F(4x3,2x2) filter transform of ConvTranspose2d(4,2,1) (csrc/winograd_deconv43.hip): U = G4 g G3^T, 5 x 4 = 20 positions per phase filter.
-// G3 = [1 0; .5 .5; .5 -.5; 0 -1] is the G of mode 2 above (horizontal, points 0, 1, -1, inf); G4 = [1/2 0; -1/2 -1/2; -1/6 1/6; 1/6 1/3; 0 1]
-// (vertical, points 0, 1, -1, 2, inf) pairs with B4^T = [2 -1 -2 1 0; 0 -2 -1 1 0; 0 2 -3 1 0; 0 -1 0 1 0; 0 2 -1 -2 1] and
-// A4^T = [1 1 1 1 0; 0 1 -1 2 0; 0 1 1 4 0; 0 1 -1 8 1] in the kernel.  Same fragment order as mode 2 with 20 positions (xi * 4 + nu) where that
-// has 16 and NH = 2 (Cout % 64 == 0): [phase][n / 64][step = c / 8][position][n / 32 % 2][lane = (c % 8 / 4) * 32 + n % 32][c % 4]; a block of 256
-// threads makes the 20 x 256 elements of (32 output channels, one 8-channel step).  u = sum_a sum_b G4[xi][a] g[a][b] G3[nu][b] in double, rounded once.
+// The F(4x3,2x2) filter transform of one (output channel, input channel) pair, shared by the two pack blocks below: U = G4 g G3^T, 5 x 4 positions
+// xi * 4 + nu, 512 floats apart in the fragment order; the first nxi row positions are stored.  G3 = [1 0; .5 .5; .5 -.5; 0 -1] is the G of mode 2
+// above (horizontal, points 0, 1, -1, inf); G4 = [1/2 0; -1/2 -1/2; -1/6 1/6; 1/6 1/3; 0 1] (vertical, points 0, 1, -1, 2, inf) pairs with B4^T and
+// A4^T of csrc/winograd43.h.  u = sum_a sum_b G4[xi][a] g[a][b] G3[nu][b] in double, rounded once.
+__device__ __forceinline__ void wino43_store_u(const double (&g)[2][2], float* o, int nxi) {
+    const double G4[5][2] = {{0.5, 0.0}, {-0.5, -0.5}, {-1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3}, {0.0, 1.0}};
+    const double G3[4][2] = {{1.0, 0.0}, {0.5, 0.5}, {0.5, -0.5}, {0.0, -1.0}};
+#pragma unroll
+    for (int xi = 0; xi < 5; ++xi) {
+        if (xi >= nxi) continue;
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+            double v = 0.0;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) v += G4[xi][a] * g[a][b] * G3[nu][b];
+            o[(long long)(xi * 4 + nu) * 512] = (float)v;
+        }
+    }
+}
+
+// F(4x3,2x2) filter transform of ConvTranspose2d(4,2,1) (csrc/winograd_deconv43.hip): 20 positions per phase filter.  Same fragment order as mode 2
+// with 20 positions (xi * 4 + nu) where that has 16 and NH = 2 (Cout % 64 == 0): [phase][n / 64][step = c / 8][position][n / 32 % 2][lane = (c % 8 / 4) * 32 + n % 32][c % 4];
+// a block of 256 threads makes the 20 x 256 elements of (32 output channels, one 8-channel step).
 __device__ __forceinline__ void wino43_pack_block(const float* __restrict__ w, float* __restrict__ out, int Cout, int Cin, long long bl, int tid) {
     const int steps = Cin >> 3;
     const long long per = (long long)(Cout >> 5) * steps;             // blocks per phase filter
@@ -95,29 +114,17 @@ __device__ __forceinline__ void wino43_pack_block(const float* __restrict__ w, f
     const int nl = tid & 31, cc = tid >> 5;
     const int n = n32 * 32 + nl, c = step * 8 + cc;
     const int py = phase >> 1, px = phase & 1;
-    const double G4[5][2] = {{0.5, 0.0}, {-0.5, -0.5}, {-1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3}, {0.0, 1.0}};
-    const double G3[4][2] = {{1.0, 0.0}, {0.5, 0.5}, {0.5, -0.5}, {0.0, -1.0}};
     double g[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) g[a][b] = (double)w[(((long long)c * Cout + n) * 4 + (3 - py - 2 * a)) * 4 + (3 - px - 2 * b)];
     float* o = out + ((((long long)((n32 >> 1) * steps + step) * 20) * 2 + (n32 & 1)) * 64 + (cc >> 2) * 32 + nl) * 4 + (cc & 3);
-#pragma unroll
-    for (int xi = 0; xi < 5; ++xi)
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-            double v = 0.0;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) v += G4[xi][a] * g[a][b] * G3[nu][b];
-            o[(long long)(xi * 4 + nu) * 512] = (float)v;
-        }
+    wino43_store_u(g, o, 5);
 }
 
 // F(4x3,2x2) filter transform of the 3x3 / stride 2 / pad 1 conv summed over its four input phases (csrc/winograd_s2_43.hip): w = (Cout, Cin, 3, 3) padded to 4x4
-// with a zero last row and column, phase (by, bx): g[a][b] = w[n][c][2a + by][2b + bx], U = G4 g G3^T with the G4, G3 above.  The by = 1 phases have g[1][.] = 0
+// with a zero last row and column, phase (by, bx): g[a][b] = w[n][c][2a + by][2b + bx], U = G4 g G3^T as above.  The by = 1 phases have g[1][.] = 0
 // and G4's last row is [0 1], so their row position xi = 4 is identically zero and is NOT stored: 20 + 20 + 16 + 16 = 72 floats per channel pair.  The phases are
 // concatenated along the step index so that a block's filter stream is contiguous:
 //   [n / 64][by = 0: bx, step = c / 8, 20 positions xi * 4 + nu | by = 1: bx, step, 16 positions][n / 32 % 2][lane = (c % 8 / 4) * 32 + n % 32][c % 4]
@@ -132,8 +139,6 @@ __device__ __forceinline__ void wino_s2_43_pack_block(const float* __restrict__ 
     const int nl = tid & 31, cc = tid >> 5;
     const int n = n32 * 32 + nl, c = step * 8 + cc;
     const int by = phase >> 1, bx = phase & 1;
-    const double G4[5][2] = {{0.5, 0.0}, {-0.5, -0.5}, {-1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3}, {0.0, 1.0}};
-    const double G3[4][2] = {{1.0, 0.0}, {0.5, 0.5}, {0.5, -0.5}, {0.0, -1.0}};
     double g[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -143,19 +148,7 @@ __device__ __forceinline__ void wino_s2_43_pack_block(const float* __restrict__ 
     const long long gstep = (long long)bx * steps + step;
     float* o = out + (long long)(n32 >> 1) * steps * 36864 + (by ? (long long)steps * 20480 + gstep * 8192 : gstep * 10240) +
                ((n32 & 1) * 64 + (cc >> 2) * 32 + nl) * 4 + (cc & 3);
-#pragma unroll
-    for (int xi = 0; xi < 5; ++xi) {
-        if (by && xi == 4) continue;
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-            double v = 0.0;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b) v += G4[xi][a] * g[a][b] * G3[nu][b];
-            o[(long long)(xi * 4 + nu) * 512] = (float)v;
-        }
-    }
+    wino43_store_u(g, o, by ? 4 : 5);
 }
 
 // One 16-byte item of the F(4x4,3x3) filter transform U = G g G^T (csrc/winograd_f4.hip), shared by its pack kernel and the table-driven multi-pack launch.
