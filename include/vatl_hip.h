@@ -9,7 +9,8 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller (PyTorch allocator);
- *     the library never allocates, frees or synchronises;
+ *     the library never allocates, frees or synchronises (the host-only entries,
+ *     vatl_jpeg_probe / vatl_jpeg_entropy_decode among them, say so and take host pointers);
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *   - return 0 on success, a negative VATL_E* code on failure; the message of
  *     the last failure on the calling thread is vatl_last_error();
@@ -546,6 +547,51 @@ int vatl_gaussian_targets(const float* joints_xy, const float* vis, float* targe
  * return).  B <= 65535, out_w <= 4096, out_h * out_w < 2^20. */
 int vatl_crop_warp_affine(const uint8_t* arena, const int64_t* src_off, const int32_t* src_hwf, const double* minv, float* out,
                           int32_t* crop_max, int B, int out_h, int out_w, float mean0, float mean1, float mean2, void* stream);
+
+/* Hybrid JPEG decoder: what fills that arena from file bytes (alphapose/datasets/coco_video.py `_read_rgb`; the reference decodes
+ * with cv2.imread, posetrack21.py:141).  The host parses the markers and decodes the Huffman-coded segment into coefficient blocks
+ * (the two HOST-ONLY entries below: host pointers, no device touched, usable in a process without a GPU, callable from many
+ * threads at once); the device dequantises, runs libjpeg's integer "islow" inverse DCT, fancy-upsamples 4:2:0 chroma and converts
+ * YCbCr -> RGB for a whole BATCH of frames in two launches.  The bytes are those Pillow on libjpeg-turbo produces, bit for bit.
+ *
+ * Frame descriptor: VATL_JPEG_DESC_INTS int32 —
+ *   [0] admitted (1 / 0)   [1] refusal code VATL_JPEG_* (0 when admitted; the reason's text is vatl_last_error())
+ *   [2] height  [3] width  [4] components (1 / 3)  [5] sampling: 1 = every component 1x1 (4:4:4, grayscale), 2 = luma 2x2 (4:2:0)
+ *   [6] MCUs per row  [7] MCU rows  [8], [9] luma block grid (columns, rows)  [10], [11] chroma block grid (0, 0 for grayscale)
+ *   [12] blocks of all components (coefficients = 64 * blocks)  [13] restart interval in MCUs (0: none)
+ *   [14] byte offset of the entropy-coded segment  [15] reserved
+ * Admitted: baseline SOF0, 8 bit, 8-bit quantiser tables, one scan holding every component, 1 component or 3 YCbCr components sampled
+ * 4:4:4 or 4:2:0, height and width >= 8, at most 2^26 pixels, a scan of at least two bits per declared block, any restart interval.  Everything else — progressive, extended, arithmetic coding, other
+ * samplings, 4 components, several scans, no JPEG at all — is REFUSED with a reason, not an error: callers decode those with Pillow. */
+#define VATL_JPEG_DESC_INTS        16
+#define VATL_JPEG_NOT_JPEG          1
+#define VATL_JPEG_BAD_HEADER        2
+#define VATL_JPEG_NOT_BASELINE      3
+#define VATL_JPEG_PRECISION         4
+#define VATL_JPEG_COMPONENTS        5
+#define VATL_JPEG_SAMPLING          6
+#define VATL_JPEG_TOO_SMALL         7
+#define VATL_JPEG_MULTIPLE_SCANS    8
+#define VATL_JPEG_COLOUR_SPACE      9
+#define VATL_JPEG_QUANT_PRECISION  10
+#define VATL_JPEG_TOO_LARGE        11
+#define VATL_ESTREAM (-3)         /* corrupt / truncated entropy-coded data */
+/* bytes -> descriptor.  Returns 0 whenever the pointers are valid: refusal is desc[0] == 0, never a failure. */
+int vatl_jpeg_probe(const uint8_t* data, int64_t nbytes, int32_t* desc);
+/* bytes -> coef: int16 coefficients in natural (de-zigzagged) order, NOT dequantised, 64 per block, per component (Y, Cb, Cr) in
+ * block-raster order over the component's padded block grid (zero where the stream codes nothing); qt: 3 x 64 uint16 quantiser values per
+ * component in natural order; desc as above.  coef_capacity counts int16 elements and must hold 64 * desc[12] (ask vatl_jpeg_probe).
+ * Every stream read and every coefficient write is bounds-checked: VATL_EINVAL for a refused stream / a capacity too small,
+ * VATL_ESTREAM for a truncated or corrupt one (run past coefficient 63, missing table, bad restart marker, ...). */
+int vatl_jpeg_entropy_decode(const uint8_t* data, int64_t nbytes, int16_t* coef, int64_t coef_capacity, uint16_t* qt, int32_t* desc);
+/* DEVICE.  coef: the frames' coefficients back to back (64 * blocks int16, 16-byte aligned); qt: (frames, 3, 64) uint16; table:
+ * (frames + 1) rows of 12 int64 — first block of the frame in coef, first 12-byte store group, byte offset in the arena, height, width,
+ * components, sampling, luma block columns, rows, chroma block columns, rows, 0 — the last row holding the totals `blocks` and `groups`
+ * in its first two columns; a frame at arena offset o has ceil(((o & 3) + 3 h w) / 12) groups.  planes: 64 * blocks bytes of
+ * workspace (8-byte aligned).  arena (4-byte aligned): each frame lands as packed (h, w, 3) RGB at its offset, which need NOT be
+ * aligned; no byte outside the frames' ranges and none at or past arena_bytes is written. */
+int vatl_jpeg_pixels(const int16_t* coef, const uint16_t* qt, const int64_t* table, int frames, int64_t blocks, int64_t groups,
+                     uint8_t* planes, uint8_t* arena, int64_t arena_bytes, void* stream);
 
 /* One fine-tune step of the WholeBodyAE (ActiveLearning.py:905-925: AE forward, MSELoss(output, input), backward,
  * torch.optim.Adam) on a mini-batch feat (B, D), B <= 12 (the reference uses 10), in one launch.  ae / m / v: the packed parameters

@@ -189,13 +189,15 @@ class DecodeAhead:
     def submit(self, idxs):
         if self.pool is None:
             return
-        from alphapose.datasets.coco_video import _read_rgb
+        from alphapose.datasets.coco_video import frame_loader
+        load = frame_loader(self.dataset)                     # Pillow, or read-file + Huffman decode (the data set's DECODER)
         for path in self.dataset.uncached_frames(idxs):
             if path not in self.futures:
-                self.futures[path] = self.pool.submit(_read_rgb, path)
+                self.futures[path] = self.pool.submit(load, path)
 
     def collect(self):
-        """Hand the decoded frames to the data set's cache (on the calling thread: the cache is not shared with the pool)."""
+        """Hand the decoded frames to the data set's cache (on the calling thread: the cache is not shared with the pool; with device
+        decoding this is where the batch's coefficient frames become pixels, in one call)."""
         if self.futures:
             self.dataset.cache_frames({path: fut.result() for path, fut in self.futures.items()})
         self.futures = {}

@@ -28,19 +28,35 @@ def _device():
 
 
 class FrameArena:
-    """uint8 frames packed back to back in one device buffer — what ``vatl_crop_warp_affine`` reads."""
+    """uint8 frames packed back to back in one device buffer — what ``vatl_crop_warp_affine`` reads.
+
+    ``frames``: (h, w, 3) uint8 numpy arrays (uploaded together, once) and / or uint8 DEVICE tensors of that shape (frames the hybrid
+    JPEG decoder left in HBM, ``vh.jpeg_decode_batch``): those are concatenated on the device, no host round trip."""
 
     def __init__(self, frames, device=None):
         dev = device or _device()
-        frames = [np.ascontiguousarray(f) for f in frames]
-        for f in frames:
-            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-                raise ValueError(f"frames must be (h, w, 3) uint8, got {f.dtype} {f.shape}")
-        sizes = np.array([f.size for f in frames], np.int64)
+        on_device = [torch.is_tensor(f) and f.is_cuda for f in frames]
+        frames = [f if d else np.ascontiguousarray(f) for f, d in zip(frames, on_device)]
+        for f, d in zip(frames, on_device):
+            if f.dtype != (torch.uint8 if d else np.uint8) or f.ndim != 3 or f.shape[2] != 3:
+                raise ValueError(f"frames must be (h, w, 3) uint8, got {f.dtype} {tuple(f.shape)}")
+        sizes = np.array([int(f.shape[0]) * int(f.shape[1]) * 3 for f in frames], np.int64)
         self.offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
         self.hw = np.array([f.shape[:2] for f in frames], np.int32).reshape(-1, 2)
-        host = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])) if frames else torch.empty(0, dtype=torch.uint8)
-        self.data = host.to(dev, non_blocking=False)
+        host_frames = [f for f, d in zip(frames, on_device) if not d]
+        host = torch.from_numpy(np.concatenate([f.reshape(-1) for f in host_frames])) if host_frames else torch.empty(0, dtype=torch.uint8)
+        if not any(on_device):
+            self.data = host.to(dev, non_blocking=False)
+            return
+        uploaded = iter(torch.split(vh.upload(host, dev), [f.size for f in host_frames])) if host_frames else iter(())
+        self.data = torch.cat([f.to(dev).reshape(-1) if d else next(uploaded) for f, d in zip(frames, on_device)])
+
+    @classmethod
+    def from_packed(cls, data, offsets, hw):
+        """An arena over bytes that are packed already (``vh.jpeg_decode_batch``'s result): nothing is copied."""
+        self = cls.__new__(cls)
+        self.data, self.offsets, self.hw = data, np.asarray(offsets, np.int64), np.asarray(hw, np.int32).reshape(-1, 2)
+        return self
 
 
 class SimpleTransform(object):

@@ -159,6 +159,9 @@ SIGNATURES = {
     "vatl_l1_joint_regression_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "vatl_gaussian_targets": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "vatl_crop_warp_affine": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _p]),
+    "vatl_jpeg_probe": (_i, [_p, _i64, _p]),
+    "vatl_jpeg_entropy_decode": (_i, [_p, _i64, _p, _i64, _p, _p]),
+    "vatl_jpeg_pixels": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _p, _i64, _p]),
     "vatl_ae_train_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _d, _i, _p, _p]),
     "vatl_ae_grad_workspace_floats": (_i64, [_i, _i, _i]),
     "vatl_ae_backward": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
@@ -1650,6 +1653,133 @@ def crop_warp_affine(arena, src_off, src_hwf, minv, out_hw=(256, 192), mean=PIXE
                                        float(mean[0]), float(mean[1]), float(mean[2]), _stream()),
            "vatl_crop_warp_affine")
     return out, cmax
+
+
+# ----------------------------------------------------------------------------
+# hybrid JPEG decoder: Huffman pass on the host, pixels on the device
+# ----------------------------------------------------------------------------
+
+JPEG_DESC_INTS = 16                     # include/vatl_hip.h: the frame descriptor
+JPEG_REFUSALS = ("admitted", "not_jpeg", "bad_header", "not_baseline", "precision", "components", "sampling", "too_small", "multiple_scans",
+                 "colour_space", "quant_precision", "too_large")          # VATL_JPEG_* codes of include/vatl_hip.h, in order (tests/test_jpeg_tables.py)
+JPEG_TABLE_COLS = 12                    # csrc/jpeg.hip: one int64 row per frame of a batch
+
+
+class JpegInfo:
+    """What `jpeg_probe` says about a stream: ``admitted`` (the device path decodes it) or not, with ``reason`` (the refusal's name,
+    one of JPEG_REFUSALS) and ``detail`` (its text); for streams whose frame header was read also height, width, components,
+    ``sampling`` ("gray" / "4:4:4" / "4:2:0" / None), ``blocks`` per component and the coefficient count."""
+
+    def __init__(self, desc, detail=""):
+        d = [int(v) for v in desc]
+        self.desc = desc
+        self.admitted = bool(d[0])
+        self.reason = JPEG_REFUSALS[d[1]] if 0 <= d[1] < len(JPEG_REFUSALS) else f"code_{d[1]}"
+        self.detail = detail
+        self.height, self.width, self.components = d[2], d[3], d[4]
+        self.sampling = None if not d[5] else "gray" if d[4] == 1 else "4:4:4" if d[5] == 1 else "4:2:0"
+        self.blocks = (d[8] * d[9],) + ((d[10] * d[11],) * 2 if d[4] == 3 else ())
+        self.coefficients = 64 * d[12]
+        self.restart_interval = d[13]
+
+    def __repr__(self):
+        what = "admitted" if self.admitted else f"refused: {self.reason} ({self.detail})"
+        return f"JpegInfo({self.height}x{self.width}, {self.components} components, {self.sampling}, {what})"
+
+
+class JpegCoefficients:
+    """One frame after the host pass: ``coef`` int16 (64 * blocks,) host tensor — natural order, not dequantised, per component in
+    block-raster order, pinned when a device is present —, ``qt`` (3, 64) uint16 quantiser tables per component, ``desc`` the descriptor."""
+
+    def __init__(self, coef, qt, desc):
+        self.coef, self.qt, self.desc = coef, qt, desc
+        self.height, self.width, self.blocks = int(desc[2]), int(desc[3]), int(desc[12])
+
+
+def _host_bytes(data):
+    import numpy as np
+    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, np.uint8)
+    if a.dtype != np.uint8 or a.ndim != 1 or not a.flags.c_contiguous:
+        raise VatlError("a JPEG stream is bytes (or a contiguous 1-D uint8 array)")
+    return a
+
+
+def jpeg_probe(data) -> JpegInfo:
+    """File bytes -> JpegInfo.  Host only (works without a GPU); a stream the device path does not decode — progressive, 4:2:2,
+    under 8 px, no JPEG at all — is refused with a reason, never an error."""
+    import numpy as np
+    a = _host_bytes(data)
+    desc = np.zeros(JPEG_DESC_INTS, np.int32)
+    _check(lib().vatl_jpeg_probe(a.ctypes.data, a.size, desc.ctypes.data), "vatl_jpeg_probe")
+    return JpegInfo(desc, "" if desc[0] else lib().vatl_last_error().decode())
+
+
+def jpeg_entropy_decode(data) -> JpegCoefficients:
+    """File bytes of an ADMITTED stream -> JpegCoefficients.  Host only; the call releases the GIL, so a thread pool decodes in
+    parallel.  Raises VatlError for a refused stream and for a truncated / corrupt one."""
+    import numpy as np
+    a = _host_bytes(data)
+    info = jpeg_probe(a)
+    if not info.admitted:
+        raise VatlError(f"vatl_jpeg_entropy_decode: stream refused ({info.reason}): {info.detail}")
+    coef = torch.empty(info.coefficients, dtype=torch.int16, pin_memory=torch.cuda.is_available())
+    qt = np.zeros((3, 64), np.uint16)
+    desc = np.zeros(JPEG_DESC_INTS, np.int32)
+    _check(lib().vatl_jpeg_entropy_decode(a.ctypes.data, a.size, coef.data_ptr(), coef.numel(), qt.ctypes.data, desc.ctypes.data), "vatl_jpeg_entropy_decode")
+    return JpegCoefficients(coef, qt, desc)
+
+
+def jpeg_decode_batch(frames, device=None, out=None, marks=None):
+    """Coefficient frames of a whole batch -> pixels, in ONE call (two launches): returns (data, offsets, hw) in FrameArena's layout —
+    ``data`` a uint8 device tensor with the frames as packed (h, w, 3) RGB back to back, ``offsets`` (n,) int64 byte offsets,
+    ``hw`` (n, 2) int32.  ``out``: a uint8 device tensor of at least sum(h * w * 3) bytes to write into (nothing past that sum is touched).
+    ``marks``: a list that receives three timing events of the stream — before the uploads, between uploads and launches, after the
+    launches (tools/jpeg_decode_bench.py splits the call's device time with them)."""
+    import numpy as np
+    frames = list(frames)
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda":
+        raise VatlError("jpeg_decode_batch writes a device arena; there is no CPU path")
+    n = len(frames)
+    hw = np.array([[f.height, f.width] for f in frames], np.int32).reshape(-1, 2)
+    sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+    ends = np.cumsum(sizes)
+    offsets = (ends - sizes).astype(np.int64)
+    total = int(ends[-1]) if n else 0
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < total or not out.is_contiguous():
+        raise VatlError(f"jpeg_decode_batch: `out` must be a contiguous 1-D uint8 device tensor of >= {total} bytes")
+    if n == 0:
+        return out, offsets, hw
+    table = np.zeros((n + 1, JPEG_TABLE_COLS), np.int64)
+    blocks = np.array([f.blocks for f in frames], np.int64)
+    groups = ((offsets & 3) + sizes + 11) // 12
+    table[1:, 0], table[1:, 1] = np.cumsum(blocks), np.cumsum(groups)
+    table[:n, 2] = offsets
+    for k, f in enumerate(frames):
+        d = f.desc
+        table[k, 3:11] = (d[2], d[3], d[4], d[5], d[8], d[9], d[10], d[11])
+    nblocks, ngroups = int(table[n, 0]), int(table[n, 1])
+    def mark():
+        if marks is not None:
+            marks.append(torch.cuda.Event(enable_timing=True))
+            marks[-1].record()
+    with torch.cuda.device(device):
+        coef = torch.empty(nblocks * 64, dtype=torch.int16, device=device)
+        mark()
+        for k, f in enumerate(frames):
+            if f.coef.numel() != 64 * f.blocks:
+                raise VatlError("jpeg_decode_batch: a frame's coefficient count does not match its descriptor")
+            coef[int(table[k, 0]) * 64:int(table[k + 1, 0]) * 64].copy_(f.coef, non_blocking=True)
+        qt = upload(np.stack([f.qt for f in frames]).view(np.int16), device)
+        tab = upload(table, device)
+        planes = torch.empty(nblocks * 64, dtype=torch.uint8, device=device)
+        mark()
+        _check(lib().vatl_jpeg_pixels(_ptr(coef, torch.int16), _ptr(qt, torch.int16), _ptr(tab, torch.int64), n, nblocks, ngroups,
+                                      _ptr(planes, torch.uint8), _ptr(out, torch.uint8), total, _stream()), "vatl_jpeg_pixels")
+        mark()
+    return out, offsets, hw
 
 
 def ae_train_step(ae_flat, m, v, feat, d: int, z: int, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
