@@ -10,7 +10,7 @@
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller (PyTorch allocator);
  *     the library never allocates, frees or synchronises (the host-only entries,
- *     vatl_jpeg_probe / vatl_jpeg_entropy_decode among them, say so and take host pointers);
+ *     vatl_jpeg_probe / vatl_jpeg_entropy_decode / vatl_jpeg_pack among them, say so and take host pointers);
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *   - return 0 on success, a negative VATL_E* code on failure; the message of
  *     the last failure on the calling thread is vatl_last_error();
@@ -592,6 +592,58 @@ int vatl_jpeg_entropy_decode(const uint8_t* data, int64_t nbytes, int16_t* coef,
  * aligned; no byte outside the frames' ranges and none at or past arena_bytes is written. */
 int vatl_jpeg_pixels(const int16_t* coef, const uint16_t* qt, const int64_t* table, int frames, int64_t blocks, int64_t groups,
                      uint8_t* planes, uint8_t* arena, int64_t arena_bytes, void* stream);
+
+/* Huffman decoding on the device: the coefficients above without the host's Huffman pass.  The host only PACKS a stream (markers parsed,
+ * byte stuffing removed, restart markers checked); the device decodes the packed scans of a whole batch into exactly the coefficients
+ * vatl_jpeg_entropy_decode gives, ready for vatl_jpeg_pixels.  The scan is cut into subsequences of VATL_JHUFF_SUB_BYTES, one lane
+ * each, VATL_JHUFF_BLOCK_SUBS to a thread block; the lanes find their entry states through the self-synchronisation of JPEG's Huffman
+ * codes, from the scan's start and from every restart marker, so streams WITHOUT restart markers decode in parallel too, and the result
+ * is exact however long the synchronisation takes.
+ *
+ * vatl_jpeg_pack_size / vatl_jpeg_pack: HOST-ONLY like vatl_jpeg_probe (host pointers, many threads at once).  pack_size gives the
+ * capacities pack needs: scan bytes (an upper bound) and segment rows.  pack writes
+ *   scan      the entropy-coded data with FF00 turned into FF, cut at the markers, every segment zero-padded to whole subsequences
+ *             (used[0] bytes, a multiple of VATL_JHUFF_SUB_BYTES)
+ *   segments  used[1] rows of 4 int32 — byte offset in scan, real bit length, first MCU, MCU count: one row for a stream without
+ *             restart markers, one per restart interval otherwise
+ *   huff      VATL_JHUFF_HUFF_BYTES: per component its DC and its AC table as the kernels probe them (csrc/jpeg_pack.h HuffDev)
+ *   qt, desc  as vatl_jpeg_entropy_decode gives them
+ * It admits what the probe admits, with one more refusal: a segment of more than 768 KiB (desc[1] = VATL_JPEG_SEGMENT_TOO_LONG; in the
+ * worst case one lane walks a whole segment).  VATL_EINVAL for a refused stream / capacities too small, VATL_ESTREAM for an undefined
+ * table or a missing / misnumbered restart marker. */
+#define VATL_JPEG_SEGMENT_TOO_LONG 12
+#define VATL_JHUFF_SUB_BYTES   (128)
+#define VATL_JHUFF_BLOCK_SUBS  (256)
+#define VATL_JHUFF_HUFF_BYTES  (8544)
+#define VATL_JHUFF_TABLE_COLS  (16)
+int vatl_jpeg_pack_size(const uint8_t* data, int64_t nbytes, int64_t* scan_capacity, int64_t* segment_rows);
+int vatl_jpeg_pack(const uint8_t* data, int64_t nbytes, uint8_t* scan, int64_t scan_capacity, int32_t* segments, int64_t segment_capacity,
+                   uint8_t* huff, uint16_t* qt, int32_t* desc, int64_t* used);
+/* DEVICE.  Every frame's scan starts on a thread block's boundary: frame f at byte table[f][0] * 32768 of `scan`, whose size is
+ * thread_blocks * 32768 bytes (bytes behind a frame's own are not read).  segments: the frames' rows back to back; huff: (frames)
+ * x VATL_JHUFF_HUFF_BYTES; table: (frames + 1) rows of VATL_JHUFF_TABLE_COLS int64 — first thread block, subsequences, first segment
+ * row, segment rows, first coefficient block, blocks, components, sampling, MCUs per row, MCU rows, luma block columns, rows, chroma
+ * block columns, rows, 0, 0 — the last row holding the totals in columns 0, 2 and 4.  launches: the most thread blocks any segment of
+ * the batch spans (one synchronisation launch per block boundary a state may have to cross; a launch whose blocks have nothing new to
+ * do returns at once).  coef: coef_elems int16, zero-filled here, then every frame's coefficients at 64 * its first block, in
+ * vatl_jpeg_entropy_decode's layout and with its values.  status: one int32 per frame — 0, or why the frame's stream is rejected
+ * (VATL_JHUFF_*: the conditions vatl_jpeg_entropy_decode answers with VATL_ESTREAM); a rejected frame's coefficients are undefined, the
+ * other frames are not affected.  No store leaves a frame's own coefficients, whatever its stream holds.  workspace:
+ * vatl_jpeg_huffman_workspace_bytes(thread_blocks, segment_rows) bytes (host-only query; 0 for arguments out of range).  Its LAST
+ * VATL_JHUFF_ACTIVE_WORDS uint32 are part of the interface: word r holds how many thread blocks did work in synchronisation launch r
+ * (the last word: in that launch and every later one) — one atomic add per working block and launch, what tools/jpeg_decode_bench.py
+ * and the tests read to tell how far states travelled.  Never allocates, never synchronises. */
+#define VATL_JHUFF_ACTIVE_WORDS (64)
+#define VATL_JHUFF_BAD_DC          (1)
+#define VATL_JHUFF_BAD_AC          (2)
+#define VATL_JHUFF_ZERO_RUN        (3)
+#define VATL_JHUFF_ENDS_EARLY      (4)
+#define VATL_JHUFF_BLOCKS_SHORT    (5)
+#define VATL_JHUFF_RESTART_UNREAD  (6)
+int64_t vatl_jpeg_huffman_workspace_bytes(int64_t thread_blocks, int64_t segment_rows);
+int vatl_jpeg_huffman(const uint8_t* scan, const int32_t* segments, const uint8_t* huff, const int64_t* table, int frames, int64_t thread_blocks,
+                      int64_t segment_rows, int launches, int16_t* coef, int64_t coef_elems, int32_t* status, void* workspace, int64_t workspace_bytes,
+                      void* stream);
 
 /* One fine-tune step of the WholeBodyAE (ActiveLearning.py:905-925: AE forward, MSELoss(output, input), backward,
  * torch.optim.Adam) on a mini-batch feat (B, D), B <= 12 (the reference uses 10), in one launch.  ae / m / v: the packed parameters

@@ -71,9 +71,25 @@ def _read_coefficients(path):
     return _read_rgb(path)
 
 
+def _read_packed(path):
+    """The worker's share when the Huffman pass runs on the device too (DECODER = "device-huffman"): file bytes -> the packed scan
+    (`vh.jpeg_pack`: markers parsed, byte stuffing removed).  A file that does not pack — refused by the probe, more than 768 KiB between
+    restart markers, a restart marker missing — goes the way of `_read_coefficients`, which carries the host decoder's verdict and
+    after it Pillow's."""
+    import vatl_hip as vh
+    try:
+        with open(path, "rb") as f:
+            data = f.read()
+        return vh.jpeg_pack(data)                                # (raises for a stream the probe refuses: the header is parsed here alone)
+    except (OSError, vh.VatlError):
+        pass
+    return _read_coefficients(path)
+
+
 def frame_loader(dataset):
     """The function that turns one frame path into what `dataset.cache_frames` takes (looked up per call: tests replace `_read_rgb`)."""
-    return _read_rgb if getattr(dataset, "DECODER", "host") == "host" else _read_coefficients
+    decoder = getattr(dataset, "DECODER", "host")
+    return _read_rgb if decoder == "host" else _read_packed if decoder == "device-huffman" else _read_coefficients
 
 
 class _CocoVideo(FrameVideo):
@@ -86,7 +102,10 @@ class _CocoVideo(FrameVideo):
     # grayscale JPEG files (`vh.jpeg_probe`) are Huffman-decoded on the host and turned into pixels on the device, one
     # `vh.jpeg_decode_batch` call per batch, and cached as device tensors; every other file goes through Pillow.  "auto": the same as
     # "device".  The batches are the same bit for bit; profiles/jpeg_decode_notes.md has the measurement behind the default
-    # (1280x720 frames on eight threads: 3.4x the frames/s of the Pillow path, 1.8x the training steps/s).
+    # (1280x720 frames on eight threads: 3.4x the frames/s of the Pillow path, 1.8x the training steps/s).  "device-huffman" (opt-in):
+    # the Huffman pass runs on the device as well — the workers only pack the scan (`vh.jpeg_pack`), `vh.jpeg_decode_packed_batch` decodes a
+    # batch's frames, and a frame whose stream the device rejects is read again through the "device" path; the batches are the same
+    # again (profiles/jpeg_huffman_notes.md).
     DECODER = "auto"
 
     def __init__(self, train=True, dpg=False, skip_empty=True, lazy_import=False, get_prenext=False, **cfg):
@@ -160,6 +179,12 @@ class _CocoVideo(FrameVideo):
         arrive as coefficient blocks (device decoding) become pixels here, all of them in ONE `vh.jpeg_decode_batch` call on the
         calling thread, and are cached as device tensors."""
         import vatl_hip as vh
+        packed = [(path, f) for path, f in frames.items() if isinstance(f, vh.JpegPacked)]
+        if packed:                                                   # Huffman decoding on the device: one call, one status read-back for the batch
+            data, offsets, hw, status = vh.jpeg_decode_packed_batch([f for _, f in packed])
+            frames = dict(frames)
+            for (path, _), off, (h, w), bad in zip(packed, offsets.tolist(), hw.tolist(), status.tolist()):
+                frames[path] = _read_coefficients(path) if bad else data[off:off + h * w * 3].view(h, w, 3).clone()
         pending = [(path, f) for path, f in frames.items() if isinstance(f, vh.JpegCoefficients)]
         if pending:
             data, offsets, hw = vh.jpeg_decode_batch([f for _, f in pending])

@@ -162,6 +162,10 @@ SIGNATURES = {
     "vatl_jpeg_probe": (_i, [_p, _i64, _p]),
     "vatl_jpeg_entropy_decode": (_i, [_p, _i64, _p, _i64, _p, _p]),
     "vatl_jpeg_pixels": (_i, [_p, _p, _p, _i, _i64, _i64, _p, _p, _i64, _p]),
+    "vatl_jpeg_pack_size": (_i, [_p, _i64, _p, _p]),
+    "vatl_jpeg_pack": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "vatl_jpeg_huffman_workspace_bytes": (_i64, [_i64, _i64]),
+    "vatl_jpeg_huffman": (_i, [_p, _p, _p, _p, _i, _i64, _i64, _i, _p, _i64, _p, _p, _i64, _p]),
     "vatl_ae_train_step": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _d, _i, _p, _p]),
     "vatl_ae_grad_workspace_floats": (_i64, [_i, _i, _i]),
     "vatl_ae_backward": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
@@ -1661,7 +1665,7 @@ def crop_warp_affine(arena, src_off, src_hwf, minv, out_hw=(256, 192), mean=PIXE
 
 JPEG_DESC_INTS = 16                     # include/vatl_hip.h: the frame descriptor
 JPEG_REFUSALS = ("admitted", "not_jpeg", "bad_header", "not_baseline", "precision", "components", "sampling", "too_small", "multiple_scans",
-                 "colour_space", "quant_precision", "too_large")          # VATL_JPEG_* codes of include/vatl_hip.h, in order (tests/test_jpeg_tables.py)
+                 "colour_space", "quant_precision", "too_large", "segment_too_long")          # VATL_JPEG_* codes of include/vatl_hip.h, in order (tests/test_jpeg_tables.py)
 JPEG_TABLE_COLS = 12                    # csrc/jpeg.hip: one int64 row per frame of a batch
 
 
@@ -1780,6 +1784,157 @@ def jpeg_decode_batch(frames, device=None, out=None, marks=None):
                                       _ptr(planes, torch.uint8), _ptr(out, torch.uint8), total, _stream()), "vatl_jpeg_pixels")
         mark()
     return out, offsets, hw
+
+
+# ----------------------------------------------------------------------------
+# Huffman decoding on the device: the host only packs the stream
+# ----------------------------------------------------------------------------
+
+JPEG_SUB_BYTES = 128                    # include/vatl_hip.h VATL_JHUFF_*: one lane's share of a scan,
+JPEG_BLOCK_SUBS = 256                   # lanes per thread block,
+JPEG_HUFF_BYTES = 8544                  # a frame's six Huffman tables,
+JPEG_HUFF_TABLE_COLS = 16               # one int64 row per frame of a batch,
+JPEG_HUFF_ACTIVE_WORDS = 64             # the workspace's last words: thread blocks that worked in each synchronisation launch
+JPEG_HUFFMAN_STATUS = ("ok", "bad_dc_code", "bad_ac_code", "zero_run_past_63", "data_ends_early", "blocks_short", "restart_marker_unread")
+
+
+class JpegPacked:
+    """One frame after `jpeg_pack`: ``scan`` uint8 host tensor — the entropy-coded data without byte stuffing, cut at the restart markers,
+    each segment padded to whole 128-byte subsequences; pinned when a device is present —, ``segments`` (n, 4) int32 rows {byte offset in
+    scan, real bit length, first MCU, MCU count}, ``huff`` the frame's Huffman tables as the kernels probe them (JPEG_HUFF_BYTES uint8),
+    ``qt`` (3, 64) uint16 and ``desc`` as `jpeg_entropy_decode` gives them."""
+
+    def __init__(self, scan, segments, huff, qt, desc):
+        self.scan, self.segments, self.huff, self.qt, self.desc = scan, segments, huff, qt, desc
+        self.height, self.width, self.blocks = int(desc[2]), int(desc[3]), int(desc[12])
+
+
+def jpeg_pack(data) -> JpegPacked:
+    """File bytes of an ADMITTED stream -> JpegPacked: everything the host still does when the Huffman pass runs on the device.  Host
+    only; the call releases the GIL.  Raises VatlError for a refused stream (what `jpeg_probe` refuses, and a stream with more than
+    768 KiB between restart markers: "segment_too_long"), for an undefined table and for a missing or misnumbered restart marker."""
+    import numpy as np
+    a = _host_bytes(data)
+    cap = np.zeros(2, np.int64)
+    if lib().vatl_jpeg_pack_size(a.ctypes.data, a.size, cap[0:].ctypes.data, cap[1:].ctypes.data) != 0:
+        info = jpeg_probe(a)
+        raise VatlError(f"vatl_jpeg_pack: stream refused ({info.reason}): {info.detail}")
+    scan = torch.empty(int(cap[0]), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    segments = np.zeros((int(cap[1]), 4), np.int32)
+    huff, qt, desc, used = np.zeros(JPEG_HUFF_BYTES, np.uint8), np.zeros((3, 64), np.uint16), np.zeros(JPEG_DESC_INTS, np.int32), np.zeros(2, np.int64)
+    rc = lib().vatl_jpeg_pack(a.ctypes.data, a.size, scan.data_ptr(), scan.numel(), segments.ctypes.data, segments.shape[0], huff.ctypes.data, qt.ctypes.data,
+                              desc.ctypes.data, used.ctypes.data)
+    if rc != 0 and not desc[0] and 0 < desc[1] < len(JPEG_REFUSALS):
+        raise VatlError(f"vatl_jpeg_pack: stream refused ({JPEG_REFUSALS[desc[1]]}): {lib().vatl_last_error().decode()}")
+    _check(rc, "vatl_jpeg_pack")
+    return JpegPacked(scan[:int(used[0])], segments[:int(used[1])], huff, qt, desc)
+
+
+def jpeg_huffman_batch(frames, device=None, marks=None, stats=None, coef=None):
+    """Packed frames of a whole batch -> their coefficients on the device, Huffman-decoded there: returns (coef, table, status) —
+    ``coef`` an int16 device tensor with every frame's coefficients back to back in `jpeg_entropy_decode`'s layout, ``table`` the
+    (n + 1, JPEG_HUFF_TABLE_COLS) int64 host table (column 4: a frame's first coefficient block), ``status`` an (n,) int32 DEVICE tensor
+    — 0, or an index into JPEG_HUFFMAN_STATUS for a stream the host decoder rejects too.  ``marks`` receives timing events like
+    `jpeg_decode_batch`'s; ``stats``: a dict that receives "launches" and, read back (a synchronisation), "active_blocks" per launch;
+    ``coef``: an int16 device tensor of at least 64 * sum(blocks) elements to decode into (nothing past that count is touched)."""
+    import numpy as np
+    frames = list(frames)
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda":
+        raise VatlError("jpeg_huffman_batch decodes on the device; there is no CPU path")
+    n = len(frames)
+    if n == 0:
+        raise VatlError("jpeg_huffman_batch: no frames")
+    block_bytes = JPEG_SUB_BYTES * JPEG_BLOCK_SUBS
+    table = np.zeros((n + 1, JPEG_HUFF_TABLE_COLS), np.int64)
+    launches = 1
+    for k, f in enumerate(frames):
+        d, subs = f.desc, f.scan.numel() // JPEG_SUB_BYTES
+        if f.scan.numel() != subs * JPEG_SUB_BYTES or subs == 0 or f.segments.shape[0] == 0 or f.huff.size != JPEG_HUFF_BYTES:
+            raise VatlError("jpeg_huffman_batch: a frame is not what jpeg_pack returns")
+        table[k, 1], table[k, 3] = subs, f.segments.shape[0]
+        table[k, 5:14] = (d[12], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11])
+        table[k + 1, 0] = table[k, 0] + -(-subs // JPEG_BLOCK_SUBS)
+        table[k + 1, 2] = table[k, 2] + f.segments.shape[0]
+        table[k + 1, 4] = table[k, 4] + int(d[12])
+        first = f.segments[:, 0].astype(np.int64) // JPEG_SUB_BYTES                  # a segment's first and last subsequence -> the thread blocks it spans
+        last = np.append(first[1:], subs) - 1
+        launches = max(launches, int((last // JPEG_BLOCK_SUBS - first // JPEG_BLOCK_SUBS).max()) + 1)
+    tbs, nseg, nblocks = int(table[n, 0]), int(table[n, 2]), int(table[n, 4])
+    def mark():
+        if marks is not None:
+            marks.append(torch.cuda.Event(enable_timing=True))
+            marks[-1].record()
+    with torch.cuda.device(device):
+        scan = torch.empty(tbs * block_bytes, dtype=torch.uint8, device=device)
+        mark()
+        for k, f in enumerate(frames):
+            at = int(table[k, 0]) * block_bytes
+            scan[at:at + f.scan.numel()].copy_(f.scan, non_blocking=True)
+        segs = upload(np.concatenate([f.segments for f in frames]), device)
+        huff = upload(np.concatenate([f.huff for f in frames]), device)
+        tab = upload(table, device)
+        if coef is None:
+            coef = torch.empty(nblocks * 64, dtype=torch.int16, device=device)
+        elif not coef.is_cuda or coef.dtype != torch.int16 or coef.dim() != 1 or coef.numel() < nblocks * 64 or not coef.is_contiguous():
+            raise VatlError(f"jpeg_huffman_batch: `coef` must be a contiguous 1-D int16 device tensor of >= {nblocks * 64} elements")
+        status = torch.empty(n, dtype=torch.int32, device=device)
+        need = int(lib().vatl_jpeg_huffman_workspace_bytes(tbs, nseg))
+        if need <= 0:
+            raise VatlError(f"jpeg_huffman_batch: a batch of {tbs} thread blocks and {nseg} segments is out of range")
+        ws = torch.empty(need // 4, dtype=torch.int32, device=device)
+        mark()
+        _check(lib().vatl_jpeg_huffman(_ptr(scan, torch.uint8), _ptr(segs, torch.int32), _ptr(huff, torch.uint8), _ptr(tab, torch.int64), n, tbs, nseg, launches,
+                                       _ptr(coef, torch.int16), nblocks * 64, _ptr(status, torch.int32), _ptr(ws, torch.int32), need, _stream()), "vatl_jpeg_huffman")
+        mark()
+        if stats is not None:
+            stats["launches"] = launches
+            stats["active_blocks"] = ws[-JPEG_HUFF_ACTIVE_WORDS:][:min(launches, JPEG_HUFF_ACTIVE_WORDS)].tolist()
+    return coef, table, status
+
+
+def jpeg_decode_packed_batch(frames, device=None, out=None, marks=None, stats=None):
+    """`jpeg_decode_batch` for JpegPacked frames: Huffman decoding (`jpeg_huffman_batch`) and the pixel stage in one go, nothing read
+    back.  Returns (data, offsets, hw, status): the first three as `jpeg_decode_batch`, ``status`` the (n,) int32 device tensor of
+    `jpeg_huffman_batch` — the pixels of a frame whose status is not 0 mean nothing (the caller decodes that file another way).
+    ``marks`` receives five events: before the uploads, before the Huffman launches, after them, before and after the pixel launches."""
+    import numpy as np
+    frames = list(frames)
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    n = len(frames)
+    hw = np.array([[f.height, f.width] for f in frames], np.int32).reshape(-1, 2)
+    sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+    ends = np.cumsum(sizes)
+    offsets = (ends - sizes).astype(np.int64)
+    total = int(ends[-1]) if n else 0
+    if out is None:
+        out = torch.empty(total, dtype=torch.uint8, device=device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < total or not out.is_contiguous():
+        raise VatlError(f"jpeg_decode_packed_batch: `out` must be a contiguous 1-D uint8 device tensor of >= {total} bytes")
+    if n == 0:
+        return out, offsets, hw, torch.empty(0, dtype=torch.int32, device=device)
+    coef, htable, status = jpeg_huffman_batch(frames, device, marks, stats)
+    table = np.zeros((n + 1, JPEG_TABLE_COLS), np.int64)
+    groups = ((offsets & 3) + sizes + 11) // 12
+    table[:, 0], table[1:, 1] = htable[:, 4], np.cumsum(groups)
+    table[:n, 2] = offsets
+    for k, f in enumerate(frames):
+        d = f.desc
+        table[k, 3:11] = (d[2], d[3], d[4], d[5], d[8], d[9], d[10], d[11])
+    nblocks, ngroups = int(table[n, 0]), int(table[n, 1])
+    with torch.cuda.device(device):
+        qt = upload(np.stack([f.qt for f in frames]).view(np.int16), device)
+        tab = upload(table, device)
+        planes = torch.empty(nblocks * 64, dtype=torch.uint8, device=device)
+        if marks is not None:
+            marks.append(torch.cuda.Event(enable_timing=True))
+            marks[-1].record()
+        _check(lib().vatl_jpeg_pixels(_ptr(coef, torch.int16), _ptr(qt, torch.int16), _ptr(tab, torch.int64), n, nblocks, ngroups,
+                                      _ptr(planes, torch.uint8), _ptr(out, torch.uint8), total, _stream()), "vatl_jpeg_pixels")
+        if marks is not None:
+            marks.append(torch.cuda.Event(enable_timing=True))
+            marks[-1].record()
+    return out, offsets, hw, status
 
 
 def ae_train_step(ae_flat, m, v, feat, d: int, z: int, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
