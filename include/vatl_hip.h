@@ -511,6 +511,39 @@ int vatl_relu_bwd(const float* dy, const float* y, float* dx, int64_t n, void* s
 int vatl_col_sum(const float* x, int64_t M, int C, float* out, double* workspace, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * Deformable 3x3 convolution, DCN v1 / v2 (csrc/deform_conv.hip; the reference's Bottleneck.conv2 under cfg['DCN'],
+ * layers/SE_Resnet.py:59-137, layers/Resnet.py:57-128, whose own implementation is layers/dcn/src)
+ * ------------------------------------------------------------------------ *
+ * pad 1, dilation 1, groups 1, stride 1 or 2; x (N,H,W,C) NHWC, output grid Ho = (H - 1) / stride + 1, Wo likewise, p = the flat
+ * output pixel (n, y, x).  For channel c with deformable group g = c / (C / dg) and tap t = 3 i + j:
+ *     dy = offset[p * offset_stride + 18 g + 2 t],  dx = offset[p * offset_stride + 18 g + 2 t + 1],
+ *     m  = mask[p * mask_stride + 9 g + t]  (mask NULL: 1; mask_is_logits != 0: its sigmoid),
+ *     out[p][o] = sum_c sum_t w[o][c][i][j] * m * S(x[n,:,:,c], y * stride - 1 + i + dy, x * stride - 1 + j + dx)
+ * with S the bilinear sample of csrc/deform_sample.h: 0 unless -1 < py < H and -1 < px < W (NaN and infinities fail), corners outside
+ * the image contribute 0, no address outside the image is formed.  The strides let offsets and mask logits stay inside conv2_offset's
+ * NHWC output ([18 dg | 9 dg] channels per pixel).  Served (vatl_deform_conv2d_supported): C and Cout multiples of 16, dg in {1, 2, 4}.
+ *
+ * vatl_deform_conv2d_fwd: the fused forward (gather + blend into the A operand of v_mfma_f32_32x32x2f32), y (N,Ho,Wo,Cout) =
+ *   act(out * scale + bias), scale / bias may be NULL; w_tcc is the filter as [tap][C][Cout] (w.permute(2, 3, 1, 0)).
+ * vatl_deform_columns: col[p][t * C + c] = m * S(...), row stride col_stride >= 9 C (a multiple of 4; the padding columns are
+ *   zeroed), which a 1x1 GEMM with the filter as [Cout][t * C + c] turns into `out` (training forward; second implementation).
+ * vatl_deform_columns_bwd: from dcol (same layout) the gradients dx (N,H,W,C; zeroed here, then accumulated with float atomics: its
+ *   summation order, and so its last bits, vary from run to run), d_offset[p * d_offset_stride + 18 g + 2 t (+ 1)] and
+ *   d_mask[p * d_mask_stride + 9 g + t] (with mask_is_logits: the gradient of the logit), both reduced over the group's channels in a
+ *   fixed order; 0 where S is 0 by the validity rule.  d_mask is NULL exactly when mask is. */
+int vatl_deform_conv2d_supported(int C, int Cout, int stride, int deform_groups);
+int vatl_deform_conv2d_fwd(const float* x, const float* w_tcc, const float* offset, int offset_stride, const float* mask_or_null,
+                           int mask_stride, int mask_is_logits, const float* scale, const float* bias, float* y, int N, int H, int W,
+                           int C, int Cout, int stride, int deform_groups, int relu, void* stream);
+int vatl_deform_columns(const float* x, const float* offset, int offset_stride, const float* mask_or_null, int mask_stride,
+                        int mask_is_logits, float* col, int col_stride, int N, int H, int W, int C, int stride, int deform_groups,
+                        void* stream);
+int vatl_deform_columns_bwd(const float* dcol, int col_stride, const float* x, const float* offset, int offset_stride,
+                            const float* mask_or_null, int mask_stride, int mask_is_logits, float* dx, float* d_offset,
+                            int d_offset_stride, float* d_mask_or_null, int d_mask_stride, int N, int H, int W, int C, int stride,
+                            int deform_groups, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * Fine-tune step pieces (ActiveLearning.py:662-677)
  * ------------------------------------------------------------------------ */
 

@@ -17,10 +17,11 @@ class FastPose(nn.Module):
         super().__init__()
         self._preset_cfg = cfg["PRESET"]
         self.conv_dim = cfg.get("CONV_DIM", 128)
-        if "DCN" in cfg:
-            raise NotImplementedError("DCN is outside the hot path (no shipped config uses it; SURVEY.md §2.1 row 3)")
         assert cfg["NUM_LAYERS"] in [18, 34, 50, 101, 152]
-        self.preact = SEResnet(f"resnet{cfg['NUM_LAYERS']}")
+        if "DCN" in cfg:                              # deformable conv2 in the stages STAGE_WITH_DCN names (fastpose.py:24-28 of the reference)
+            self.preact = SEResnet(f"resnet{cfg['NUM_LAYERS']}", dcn=cfg["DCN"], stage_with_dcn=cfg["STAGE_WITH_DCN"])
+        else:
+            self.preact = SEResnet(f"resnet{cfg['NUM_LAYERS']}")
         self._imagenet_init(cfg["NUM_LAYERS"])
         self.suffle1 = nn.PixelShuffle(2)
         self.duc1 = DUC(512, 1024, upscale_factor=2, norm_layer=norm_layer)

@@ -122,6 +122,39 @@ class _Conv:
                              residual=residual, out_nchw=out_nchw, out=out, u_s2=us2)
 
 
+# Deformable conv2 of a DCN bottleneck (csrc/deform_conv.hip).  False = the column route: deform_columns + the 1x1 GEMM with bn2 + ReLU in its epilogue.
+# True = the fused launch (gather + blend straight into the MFMA operand).  The column route is the default ON MEASUREMENT: at 256 and 1024 crops it takes
+# 0.6 - 0.95 / 2.1 - 3.7 ms per layer of stages 2 - 4 against 1.6 - 2.2 / 6.1 - 10.6 ms fused (profiles/dcn_notes.md); the fused launch stays as the
+# tested second implementation.  Read when a plan is built.
+DEFORM_FUSED = False
+
+
+class _DeformConv:
+    """conv2_offset (a plain biased 3x3 conv on the existing routes; its odd channel counts are served like the 17-joint head's) and the
+    deformable conv2 + folded bn2 (+ ReLU) that reads offsets — and, MODULATED, the mask logits behind them — straight from its NHWC output."""
+    __slots__ = ("off", "w", "wg", "scale", "bias", "cout", "stride", "dg", "mask")
+
+    def __init__(self, blk):
+        conv = blk.conv2
+        self.off = _Conv(blk.conv2_offset, None)
+        self.cout, cin = conv.weight.shape[:2]
+        self.stride, self.dg = blk.stride, blk.deformable_groups
+        self.mask = True if blk.with_modulated_dcn else None      # True: sigmoid of the logits that follow the offsets
+        if getattr(conv, "bias", None) is not None or not vh.deform_conv2d_supported(cin, self.cout, self.stride, self.dg):
+            raise NotImplementedError(f"no HIP plan for a deformable conv2 {cin} -> {self.cout}, stride {self.stride}, {self.dg} deformable groups, bias {getattr(conv, 'bias', None) is not None}")
+        self.w = vh.pack_deform_weight(conv.weight.detach()) if DEFORM_FUSED else None
+        self.wg = None if DEFORM_FUSED else vh.pack_conv_weight(vh.deform_gemm_weight(conv.weight.detach()))
+        bn = blk.bn2
+        self.scale, self.bias = vh.bn_fold(_d(bn.weight), _d(bn.bias), bn.running_mean, bn.running_var, bn.eps)
+
+    def __call__(self, x, relu, out=None):
+        o = self.off(x, relu=False)
+        if self.w is not None:
+            return vh.deform_conv2d_fwd(x, self.w, o, self.mask, self.scale, self.bias, self.stride, self.dg, relu, out=out)
+        col = vh.deform_columns(x, o, self.mask, self.stride, self.dg)
+        return vh.conv2d_fwd(col, self.wg, self.scale, self.bias, self.cout, 1, 1, 1, 0, relu, out=out)
+
+
 class _Deconv:
     __slots__ = ("w", "u", "u43", "wsrc", "d43", "scale", "bias", "cout")
 
@@ -156,7 +189,7 @@ FUSE_PROJ = True
 class _BottleneckPlan:
     def __init__(self, blk):
         self.c1 = _Conv(blk.conv1, blk.bn1)
-        self.c2 = _Conv(blk.conv2, blk.bn2)
+        self.c2 = _DeformConv(blk) if getattr(blk, "with_dcn", False) else _Conv(blk.conv2, blk.bn2)     # (conv1 / conv3 and their fusions are untouched by a deformable conv2)
         self.c3 = _Conv(blk.conv3, blk.bn3)
         self.proj = _Conv(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None
         self.dual = None

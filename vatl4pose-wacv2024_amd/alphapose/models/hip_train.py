@@ -371,6 +371,83 @@ class _ConvBN:
         return dx
 
 
+class _DeformConvBN:
+    """conv2_offset + deformable conv2 (DCN v1 / v2) + BatchNorm2d(train) + ReLU of a DCN bottleneck, on the column route
+    (csrc/deform_conv.hip): forward = offset conv (bias, no BatchNorm), deform_columns, the 1x1 GEMM with the batch statistics from its
+    epilogue; backward = BatchNorm backward, weight and data gradient of the GEMM, deform_columns_bwd (dx by float atomics: a DCN
+    network's step is reproducible in value, not in bits), then the offset conv's bias, weight and data gradients — the last one takes
+    the deformable dx as its epilogue residual, so the sum is the gradient of the tensor both convs read."""
+
+    def __init__(self, blk):
+        self.conv, self.off, self.bn = blk.conv2, blk.conv2_offset, blk.bn2
+        self.cout, self.cin = self.conv.weight.shape[:2]
+        self.stride, self.dg = blk.stride, blk.deformable_groups
+        self.mask = True if blk.with_modulated_dcn else None
+        self.offc = self.off.weight.shape[0]
+        if self.cin % 32 or self.cout % 32 or not vh.deform_conv2d_supported(self.cin, self.cout, self.stride, self.dg):
+            raise NotImplementedError(f"no training-mode HIP path for a deformable conv2 {self.cin} -> {self.cout} (multiples of 32), "
+                                      f"stride {self.stride}, {self.dg} deformable groups")
+
+    def forward(self, x):
+        from .layers.dcn import columns_forward
+        bn = self.bn
+        _, ob = vh.bn_fold(None, None, None, None, 0.0, self.off.bias.detach(), channels=self.offc)
+        o = vh.conv2d_fwd(x, vh.pack_conv_weight(self.off.weight.detach()), None, ob, self.offc, 3, 3, self.stride, 1, False)
+        col, wg = columns_forward(x, o, self.mask, self.conv.weight.detach(), self.stride, self.dg)
+        z, mean, invstd, scale, bias = vh.conv2d_fwd_bnstats(col, vh.pack_conv_weight(wg, planned=False), self.cout, 1, 1, 1, 0, bn.weight.detach(),
+                                                             bn.bias.detach(), bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+        _count_batch(bn)
+        y = _tap(vh.scale_bias_act(z, scale, bias, None, True))
+        self.saved = (x, o, col, z, mean, invstd, (scale, bias))
+        return y
+
+    def bn_spec(self):
+        if not _FUSE_BN_BWD or self.cout < _FUSE_BN_MIN_C:
+            return None
+        z, mean, invstd, mask = self.saved[3:]
+        return vh.BnBwdSpec(z, mean, invstd, scale=mask[0], bias=mask[1])
+
+    def backward(self, dy, grads, pre=None, consumer=None):
+        """-> (gradient of the block's conv1 output, None).  ``consumer`` is not served: the caller runs conv1's BatchNorm backward unfused."""
+        from .layers.dcn import columns_backward
+        assert consumer is None
+        x, o, col, z, mean, invstd, mask = self.saved
+        self.saved = None
+        og, ob = _gout(grads, self.bn.weight), _gout(grads, self.bn.bias)
+        if pre is not None:
+            dz, dgamma, dbeta = vh.bn_bwd_from_stats(pre, dy, self.bn.weight.detach(), dgamma=og, dbeta=ob)
+        else:
+            dz, dgamma, dbeta = vh.bn_train_bwd_relu(dy, mask[0], mask[1], z, self.bn.weight.detach(), mean, invstd, dgamma=og, dbeta=ob)
+        grads[self.bn.weight] = dgamma
+        grads[self.bn.bias] = dbeta
+        wt = self.conv.weight.detach()
+        gpad = (self.offc + 31) // 32 * 32                  # the offset conv's output gradient, zero behind its channels (as the 17-joint head's)
+        dxd, d_off, _, dw = columns_backward(dz, col, vh.deform_gemm_weight(wt), x, o, self.mask, wt, self.stride, self.dg, grad_channels=gpad,
+                                             dw_out=_gout(grads, self.conv.weight))
+        grads[self.conv.weight] = dw
+        grads[self.off.bias] = vh.col_sum(d_off)[:self.offc].contiguous()
+        grads[self.off.weight] = vh.conv2d_wgrad(x, d_off, self.offc, self.cin, 3, 3, self.stride, 1, out=_gout(grads, self.off.weight))
+        ow = self.off.weight.detach()
+        n, h, w, cin = x.shape
+        ho, wo = d_off.shape[1], d_off.shape[2]
+        if self.stride == 1:
+            wd = vh.pack_dgrad_weight(ow, _flipped_taps(3, 3), cout_k=gpad)
+            return vh.conv2d_fwd_ex(d_off, wd, cin, 3, 3, 1, 1, 1, h, w, h, w, 1, 1, 0, 0, residual=dxd), None
+        assert h == 2 * ho and w == 2 * wo
+        dx = torch.empty((n, h, w, cin), device=x.device, dtype=torch.float32)
+        for py in (0, 1):                                 # input-pixel parity -> which filter rows reach it (as _ConvBN._dgrad)
+            rows = [1] if py == 0 else [2, 0]
+            for px in (0, 1):
+                cols = [1] if px == 0 else [2, 0]
+                wd = vh.pack_dgrad_weight(ow, [(a, b) for a in rows for b in cols], cout_k=gpad)
+                vh.conv2d_fwd_ex(d_off, wd, cin, len(rows), len(cols), 1, 0, 0, ho, wo, h, w, 2, 2, py, px, out=dx, residual=dxd)
+        return dx, None
+
+
+def _conv2_of(blk):
+    return _DeformConvBN(blk) if getattr(blk, "with_dcn", False) else _ConvBN(blk.conv2, blk.bn2, True)
+
+
 class _DeconvBN:
     """ConvTranspose2d(4,2,1, bias-free) + BatchNorm2d(train) + ReLU."""
 
@@ -428,7 +505,7 @@ class _DeconvBN:
 class _BottleneckT:
     def __init__(self, blk):
         self.c1 = _ConvBN(blk.conv1, blk.bn1, True)
-        self.c2 = _ConvBN(blk.conv2, blk.bn2, True)
+        self.c2 = _conv2_of(blk)
         self.c3 = _ConvBN(blk.conv3, blk.bn3, True)
         self.proj = _ConvBN(blk.downsample[0], blk.downsample[1], False) if blk.downsample is not None else None
 
@@ -441,7 +518,7 @@ class _BottleneckT:
         return self.c3.bn_spec()
 
     def backward(self, dy, grads, pre=None, consumer=None):
-        s2, s1 = self.c2.bn_spec(), self.c1.bn_spec()
+        s2, s1 = self.c2.bn_spec(), (None if isinstance(self.c2, _DeformConvBN) else self.c1.bn_spec())
         db, g = self.c3.backward(dy, grads, pre=pre, consumer=s2)        # g = gradient of the skip input (masked dy)
         da, _ = self.c2.backward(db, grads, pre=s2, consumer=s1)
         dskip = g if self.proj is None else self.proj.backward(g, grads)[0]
@@ -572,7 +649,7 @@ class _SEBottleneckT:
 
     def __init__(self, blk):
         self.c1 = _ConvBN(blk.conv1, blk.bn1, True)
-        self.c2 = _ConvBN(blk.conv2, blk.bn2, True)
+        self.c2 = _conv2_of(blk)
         self.c3 = _ConvBN(blk.conv3, blk.bn3, False)
         self.proj = _ConvBN(blk.downsample[0], blk.downsample[1], False)
         self.fc1, self.fc2 = _LinearT(blk.se.fc[0], True), _LinearT(blk.se.fc[2], False)
@@ -590,7 +667,7 @@ class _SEBottleneckT:
         dgate = vh.se_bwd_gate(dy, y, u, gate)
         dpool = self.fc1.backward(self.fc2.backward(dgate, grads), grads)
         du, gm = vh.se_bwd_apply(dy, y, gate, dpool)
-        s2, s1 = self.c2.bn_spec(), self.c1.bn_spec()
+        s2, s1 = self.c2.bn_spec(), (None if isinstance(self.c2, _DeformConvBN) else self.c1.bn_spec())
         db, _ = self.c3.backward(du, grads, consumer=s2)
         da, _ = self.c2.backward(db, grads, pre=s2, consumer=s1)
         dskip, _ = self.proj.backward(gm, grads)

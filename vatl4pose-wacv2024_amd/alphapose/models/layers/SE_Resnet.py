@@ -32,7 +32,7 @@ class SEResnet(_PlainResNet):
         if stride != 1 or self.inplanes != planes * block.expansion:
             proj = nn.Sequential(nn.Conv2d(self.inplanes, planes * block.expansion, kernel_size=1, stride=stride, bias=False),
                                  self._norm_layer(planes * block.expansion, momentum=0.1))
-        seq = [block(self.inplanes, planes, stride, proj, reduction=proj is not None, norm_layer=self._norm_layer)]
+        seq = [block(self.inplanes, planes, stride, proj, reduction=proj is not None, norm_layer=self._norm_layer, dcn=dcn)]
         self.inplanes = planes * block.expansion
-        seq += [block(self.inplanes, planes, norm_layer=self._norm_layer) for _ in range(1, blocks)]
+        seq += [block(self.inplanes, planes, norm_layer=self._norm_layer, dcn=dcn) for _ in range(1, blocks)]       # every block of a DCN stage
         return nn.Sequential(*seq)

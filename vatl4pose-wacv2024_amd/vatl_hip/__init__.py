@@ -154,6 +154,10 @@ SIGNATURES = {
     "vatl_se_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "vatl_relu_bwd": (_i, [_p, _p, _p, _i64, _p]),
     "vatl_col_sum": (_i, [_p, _i64, _i, _p, _p, _p]),
+    "vatl_deform_conv2d_supported": (_i, [_i, _i, _i, _i]),
+    "vatl_deform_conv2d_fwd": (_i, [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p] + [_i] * 8 + [_p]),
+    "vatl_deform_columns": (_i, [_p, _p, _i, _p, _i, _i, _p, _i] + [_i] * 6 + [_p]),
+    "vatl_deform_columns_bwd": (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i] + [_i] * 6 + [_p]),
     "vatl_masked_mse_workspace_floats": (_i64, [_i64]),
     "vatl_masked_mse_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "vatl_l1_joint_regression_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
@@ -556,8 +560,9 @@ def _winograd_fields(kind: int, cout: int, cin: int, k: int, inner: int):
     return (kind, cout, cin, k, k, pad, 1 if pad <= 32 else 2, inner, ())
 
 
-def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
-    """(Cout,Cin,R,S) -> [CoutPad][R][Spad][CinPad]; the 3-channel stem is padded to 4 channels x 8 taps."""
+def pack_conv_weight(w: torch.Tensor, planned: bool = True) -> torch.Tensor:
+    """(Cout,Cin,R,S) -> [CoutPad][R][Spad][CinPad]; the 3-channel stem is padded to 4 channels x 8 taps.  ``planned=False`` keeps the
+    call out of the thread's PackPlan (a source that is a temporary, not a parameter)."""
     cout, cin, r, s = w.shape
     cpad = conv_cout_pad(cout)
     if r == 1 and s == 1 and cpad == cout and cin != 3 and w.is_contiguous() and w.dtype == torch.float32:
@@ -565,10 +570,10 @@ def pack_conv_weight(w: torch.Tensor) -> torch.Tensor:
     spad, cinpad = (8, 4) if cin == 3 else (s, cin)
     return _pack(("conv", w.data_ptr(), tuple(w.shape)), w, lambda: (
         (cpad, r, spad, cinpad), "vatl_pack_conv_weight", (cout, cin, r, s, cpad, spad, cinpad),
-        (_PACK_CONV, cout, cin, r, s, cpad, spad, cinpad, ())))
+        (_PACK_CONV, cout, cin, r, s, cpad, spad, cinpad, ())), planned=planned)
 
 
-def pack_dgrad_weight(w: torch.Tensor, taps, cout_k: int | None = None) -> torch.Tensor:
+def pack_dgrad_weight(w: torch.Tensor, taps, cout_k: int | None = None, planned: bool = True) -> torch.Tensor:
     """(Cout,Cin,R,S) -> [CinPad][len(taps)][CoutK] with out[c][t][n] = w[n][c][taps[t]]."""
     cout, cin, r, s = w.shape
     cinpad = conv_cout_pad(cin)
@@ -581,7 +586,7 @@ def pack_dgrad_weight(w: torch.Tensor, taps, cout_k: int | None = None) -> torch
         return ((cinpad, len(taps), cout_k), "vatl_pack_dgrad_weight",
                 (cout, cin, r, s, cinpad, cout_k, len(taps), C.cast(tr, C.c_void_p), C.cast(ts, C.c_void_p)),
                 (_PACK_DGRAD, cout, cin, r, s, cinpad, cout_k, len(taps), tuple(taps)))
-    return _pack(("dgrad", w.data_ptr(), tuple(w.shape), tuple(taps), cout_k), w, job, planned=len(taps) <= 16)     # VatlPackJob holds 16 taps
+    return _pack(("dgrad", w.data_ptr(), tuple(w.shape), tuple(taps), cout_k), w, job, planned=planned and len(taps) <= 16)     # VatlPackJob holds 16 taps
 
 
 def pack_deconv_weight(w: torch.Tensor) -> torch.Tensor:
@@ -1595,6 +1600,105 @@ def col_sum(x2d):
     out = torch.empty(c, device=x2d.device, dtype=torch.float32)
     _check(lib().vatl_col_sum(_ptr(x2d), m, c, _ptr(out), _ptr(_col_ws(m, c, x2d.device), torch.float64), _stream()), "vatl_col_sum")
     return out
+
+
+# ----------------------------------------------------------------------------
+# deformable 3x3 convolution (DCN v1 / v2), csrc/deform_conv.hip
+# ----------------------------------------------------------------------------
+
+def deform_conv2d_supported(c: int, cout: int, stride: int, dg: int) -> bool:
+    return bool(lib().vatl_deform_conv2d_supported(c, cout, stride, dg))
+
+
+def pack_deform_weight(w: torch.Tensor) -> torch.Tensor:
+    """(Cout,C,3,3) -> [tap][C][Cout], the filter layout of the fused deformable forward."""
+    cout, c, r, s = w.shape
+    if (r, s) != (3, 3):
+        raise VatlError("deformable convolutions are 3x3")
+    return w.detach().permute(2, 3, 1, 0).contiguous().view(9, c, cout)
+
+
+def deform_col_stride(c: int) -> int:
+    """Row length of the column matrix: 9 * C rounded up to the 32-float K step of the GEMMs that read it."""
+    return (9 * c + 31) // 32 * 32
+
+
+def deform_gemm_weight(w: torch.Tensor) -> torch.Tensor:
+    """(Cout,C,3,3) -> (Cout,K,1,1) with K = deform_col_stride(C), column t * C + c (zeros behind 9 * C): the filter as the 1x1 conv that
+    multiplies the column matrix."""
+    cout, c = w.shape[:2]
+    k = deform_col_stride(c)
+    out = torch.zeros((cout, k, 1, 1), device=w.device, dtype=torch.float32)
+    out[:, :9 * c, 0, 0] = w.detach().permute(0, 2, 3, 1).reshape(cout, 9 * c)
+    return out
+
+
+def _deform_args(who: str, x, offset, mask, stride: int, dg: int, mask_logits: bool):
+    """Geometry and the (offset, mask) pointer arguments of the deformable entry points.  ``offset`` (N,Ho,Wo,>= 18 dg) NHWC; ``mask`` is
+    None (DCN v1), a (N,Ho,Wo,>= 9 dg) tensor, or True: the mask logits follow the offsets inside ``offset`` (conv2_offset's output)."""
+    n, h, w, c = x.shape
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    if tuple(offset.shape[:3]) != (n, ho, wo) or offset.shape[3] < (27 if mask is True else 18) * dg:
+        raise VatlError(f"{who}: offset tensor {tuple(offset.shape)} does not fit x {tuple(x.shape)}, stride {stride}, {dg} deformable groups")
+    optr = _ptr(offset)
+    if mask is None:
+        margs = (None, 0, 0)
+    elif mask is True:
+        margs = (optr + 72 * dg, offset.shape[3], 1)
+    else:
+        if tuple(mask.shape[:3]) != (n, ho, wo) or mask.shape[3] < 9 * dg:
+            raise VatlError(f"{who}: mask tensor {tuple(mask.shape)} does not fit")
+        margs = (_ptr(mask), mask.shape[3], int(mask_logits))
+    return (n, h, w, c, ho, wo), (optr, offset.shape[3]) + margs
+
+
+def deform_conv2d_fwd(x, w_tcc, offset, mask, scale, bias, stride: int, dg: int, relu: bool, mask_logits: bool = False, out=None):
+    """Fused deformable conv + folded scale / bias (+ ReLU): x (N,H,W,C) NHWC, w_tcc from pack_deform_weight -> (N,Ho,Wo,Cout)."""
+    (n, h, w, c, ho, wo), oargs = _deform_args("deform_conv2d_fwd", x, offset, mask, stride, dg, mask_logits)
+    cout = w_tcc.shape[2]
+    if tuple(w_tcc.shape) != (9, c, cout):
+        raise VatlError(f"deform_conv2d_fwd: filter {tuple(w_tcc.shape)} for {c} input channels")
+    y = out if out is not None else torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
+    if tuple(y.shape) != (n, ho, wo, cout):
+        raise VatlError("deform_conv2d_fwd: out has the wrong shape")
+    _check(lib().vatl_deform_conv2d_fwd(_ptr(x), _ptr(w_tcc), *oargs, _ptr(scale), _ptr(bias), _ptr(y), n, h, w, c, cout, stride, dg, int(relu),
+                                        _stream()), "vatl_deform_conv2d_fwd")
+    return y
+
+
+def deform_columns(x, offset, mask, stride: int, dg: int, mask_logits: bool = False):
+    """The sampled, mask-weighted column matrix (N,Ho,Wo,deform_col_stride(C)), column t * C + c."""
+    (n, h, w, c, ho, wo), oargs = _deform_args("deform_columns", x, offset, mask, stride, dg, mask_logits)
+    k = deform_col_stride(c)
+    col = torch.empty((n, ho, wo, k), device=x.device, dtype=torch.float32)
+    _check(lib().vatl_deform_columns(_ptr(x), *oargs, _ptr(col), k, n, h, w, c, stride, dg, _stream()), "vatl_deform_columns")
+    return col
+
+
+def deform_columns_bwd(dcol, x, offset, mask, stride: int, dg: int, mask_logits: bool = False, grad_channels: int | None = None):
+    """Backward of deform_columns -> (dx, d_offset, d_mask).  d_offset is (N,Ho,Wo,grad_channels or offset's channel count), zero
+    behind the gradients; with ``mask is True`` the logit gradients follow the offset gradients inside it (the layout of ``offset``) and
+    d_mask is None.  dx comes from float atomics: equal in value from run to run, not in bits."""
+    (n, h, w, c, ho, wo), oargs = _deform_args("deform_columns_bwd", x, offset, mask, stride, dg, mask_logits)
+    k = deform_col_stride(c)
+    if tuple(dcol.shape) != (n, ho, wo, k):
+        raise VatlError(f"deform_columns_bwd: dcol {tuple(dcol.shape)}, expected {(n, ho, wo, k)}")
+    gc = grad_channels or offset.shape[3]
+    if gc < (27 if mask is True else 18) * dg:
+        raise VatlError("deform_columns_bwd: grad_channels too small")
+    dx = torch.empty_like(x)
+    d_off = torch.zeros((n, ho, wo, gc), device=x.device, dtype=torch.float32)
+    d_mask = None
+    if mask is True:
+        dm = (_ptr(d_off) + 72 * dg, gc)
+    elif mask is not None:
+        d_mask = torch.empty((n, ho, wo, 9 * dg), device=x.device, dtype=torch.float32)
+        dm = (_ptr(d_mask), 9 * dg)
+    else:
+        dm = (None, 0)
+    _check(lib().vatl_deform_columns_bwd(_ptr(dcol), k, _ptr(x), *oargs, _ptr(dx), _ptr(d_off), gc, *dm, n, h, w, c, stride, dg, _stream()),
+           "vatl_deform_columns_bwd")
+    return dx, d_off, d_mask
 
 
 # ----------------------------------------------------------------------------
