@@ -760,12 +760,13 @@ int vatl_oks(const float* pred_kpts, const double* gt_kpts, const double* bbox_x
  * ------------------------------------------------------------------------ */
 /* out[i] = sum_j cosine_distance(x_i, x_j): the row sums of sklearn's KNeighborsTransformer(mode='distance',
  * metric='cosine', n_neighbors=n-1) matrix used as "influence" / "diversity" score (ActiveLearning.py:467-476,
- * 583-592).  workspace: n + D doubles. */
+ * 583-592).  A zero row is at distance 1 from every other row and 0 from itself: n - 1.  workspace: n + D doubles. */
 int vatl_cosine_rowsum(const float* emb, int64_t n, int D, double* out, double* workspace, void* stream);
 /* k-center greedy (ActiveLearning.py:798-850).  update: min_dist[i] = min(min_dist[i], ||x_i - x_c||) over the
  * centres in the DEVICE index array (first != 0: min_dist is write-only);  pick: selected_dev[step] = first arg-max of
  * a*min_dist + b*unc (either may be NULL), then unc[selected] = 0 — so pick -> update(selected_dev + step, 1) chains on
- * the stream without host round trips. */
+ * the stream without host round trips.  The arg-max is np.argmax's: both products are rounded before the sum, a NaN score
+ * is the maximum, the lowest index wins among equals.  The centre indices must lie in [0, n): they are not checked. */
 int vatl_kcenter_update(const float* emb, int64_t n, int D, const int32_t* centers_dev, int n_centers, double* min_dist, int first,
                         void* stream);
 int vatl_kcenter_pick(const double* min_dist_or_null, double* unc_or_null, double a, double b, int32_t* selected_dev, int step,

@@ -118,12 +118,23 @@ def test_query_selection_kernels_match_sklearn_restatement():
 
 @pytest.mark.parametrize("rep,flt", [("Influence", "Coreset"), ("Influence", "None"), ("None", "Diversity"), ("Random", "Random"),
                                      ("None", "K-Means"), ("Influence", "weighted")])
-def test_active_learning_representativeness_and_filters(rep, flt):
+def test_active_learning_representativeness_and_filters(rep, flt, monkeypatch):
     """Two rounds with every representativeness / filter combination family of ActiveLearning.py:465-617; for the
     device-side ones (Influence, Coreset, Diversity) the queried set is re-derived from the embeddings with the
-    sklearn restatement."""
+    sklearn restatement.  For Coreset both rounds' calls of ``coreset_selection`` are recorded and replayed through the oracle."""
     from active_learning import ActiveLearning
+    from active_learning import query as Q
     from oracle import query as OQ
+    coreset_calls = []
+    device_coreset = Q.coreset_selection
+
+    def recording_coreset(emb, labeled_idx, uncertainty, query_size, mode="moks", moks=0.0, unc_lambda=1.0, **kw):
+        got = device_coreset(emb, labeled_idx, uncertainty, query_size, mode, moks, unc_lambda, **kw)
+        coreset_calls.append(dict(emb=emb.detach().float().cpu().numpy().copy(), labeled=[int(i) for i in labeled_idx], unc=np.array(uncertainty, np.float64),
+                                  size=int(query_size), mode=mode, moks=float(moks), lam=float(unc_lambda), got=list(got)))
+        return got
+
+    monkeypatch.setattr(Q, "coreset_selection", recording_coreset)
     opt = types.SimpleNamespace(uncertainty="THC_L1", representativeness=rep, filter=flt, strategy="THC_L1", video_id="syn", get_prenext=True,
                                 from_scratch=True, continual=True, num_gpu=1, onebyone=False, retrain_thresh=1, THCvsWPU="const", fixed_lambda=False)
     torch.manual_seed(0); np.random.seed(0)
@@ -143,10 +154,19 @@ def test_active_learning_representativeness_and_filters(rep, flt):
     al.eval_and_query()
     q1 = al.query_list_list["Round1"]
     assert len(q1) == 6 and not (set(q1) & set(q0)) and len(al.labeled_id) == 12
-    if flt == "Coreset":                                          # second round has labeled centres: re-derive with sklearn
-        ds = al.eval_dataset
-        al.model.eval()
-        with torch.no_grad():
-            emb = al.model.get_embedding(torch.stack([ds[i][1][0] for i in range(24)]).to(dev())).cpu().numpy()
+    if flt == "Coreset":                                          # both rounds: the device's picks are the oracle's on the same arguments
+        from tests import query_cases as QC
+        assert len(coreset_calls) == 2
+        for rnd, c in enumerate(coreset_calls):
+            assert c["mode"] == "moks" and c["size"] == 6 and c["emb"].shape[0] == 24 and c["unc"].shape == (24,)
+            assert np.all(c["unc"][c["labeled"]] == 0) if c["labeled"] else True
+            want = OQ.coreset_selection(c["emb"], c["labeled"], c["unc"].copy(), c["size"], c["mode"], c["moks"], c["lam"])
+            gaps = QC.coreset_ref(c["emb"], c["labeled"], c["unc"], c["size"], c["mode"], c["moks"], c["lam"])[1]
+            assert c["got"] == want, f"round {rnd}: device {c['got']}, oracle {want}, relative gap best/second per step {gaps}"
+        assert coreset_calls[0]["labeled"] == [] and coreset_calls[0]["moks"] == 0.0
+        assert sorted(coreset_calls[0]["got"]) == sorted(q0) and sorted(coreset_calls[1]["got"]) == sorted(q1)
+        assert sorted(coreset_calls[1]["labeled"]) == sorted(q0) and len(q0) == 6          # round 1 starts from the six items round 0 queried
         assert set(q1).isdisjoint(q0)
         assert len(set(q1)) == 6
+    else:
+        assert not coreset_calls

@@ -9,7 +9,7 @@
 
 namespace vatl {
 
-// inv_norm[i] = 1 / ||x_i||  (1 when the row is zero, like sklearn.preprocessing.normalize)
+// inv_norm[i] = 1 / ||x_i||  (0 marks a zero row: its unit vector is zero either way, as with sklearn.preprocessing.normalize)
 __global__ __launch_bounds__(256) void row_inv_norm_kernel(const float* __restrict__ x, double* __restrict__ inv_norm, long long n, int D) {
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
@@ -17,7 +17,7 @@ __global__ __launch_bounds__(256) void row_inv_norm_kernel(const float* __restri
     double s = 0.0;
     for (int d = lane; d < D; d += 64) { const double v = x[row * D + d]; s += v * v; }
     s = wave_sum(s);
-    if (lane == 0) inv_norm[row] = s > 0.0 ? 1.0 / sqrt(s) : 1.0;
+    if (lane == 0) inv_norm[row] = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
 }
 
 // s[d] = sum_i x[i][d] * inv_norm[i]   (one thread per column, rows in order: deterministic)
@@ -30,7 +30,8 @@ __global__ __launch_bounds__(256) void unit_colsum_kernel(const float* __restric
     s[d] = acc;
 }
 
-// out[i] = sum_j (1 - cos(x_i, x_j)) = n - x^_i . s
+// out[i] = sum_j (1 - cos(x_i, x_j)) = n - x^_i . s.  A zero row is at distance 1 from every OTHER row and, with sklearn's zeroed
+// diagonal, at 0 from itself: n - 1, where the formula (which counts x^_i . x^_i = 1) would give n.
 __global__ __launch_bounds__(256) void cosine_rowsum_kernel(const float* __restrict__ x, const double* __restrict__ inv_norm, const double* __restrict__ s,
                                                             double* __restrict__ out, long long n, int D) {
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(256) void cosine_rowsum_kernel(const float* __restr
     double dot = 0.0;
     for (int d = lane; d < D; d += 64) dot += (double)x[row * D + d] * s[d];
     dot = wave_sum(dot);
-    if (lane == 0) out[row] = (double)n - dot * inv_norm[row];
+    if (lane == 0) { const double inv = inv_norm[row]; out[row] = inv == 0.0 ? (double)(n - 1) : (double)n - dot * inv; }
 }
 
 // min_dist[i] = min(min_dist[i], ||x_i - x_c||) for the centres c = centers[0..nc); `centers` lives on the device so
@@ -60,27 +61,43 @@ __global__ __launch_bounds__(256) void kcenter_update_kernel(const float* __rest
     if (lane == 0) min_dist[row] = best;
 }
 
+// a*md + b*u as numpy computes it (ActiveLearning.py:798-850: `(1 - moks) * min_distances + unc_lambda * moks * uncertainty`, one
+// array operation after the other): both products are rounded before the sum.  hipcc would contract this into mul + fma, which
+// leaves a*md unrounded and moves the score by one ulp about one time in six: enough to flip an arg-max between near-equal items.
+__device__ __forceinline__ double pick_score(double a, double md, double b, double u) {
+#pragma clang fp contract(off)
+    const double p = a * md, q = b * u;
+    return p + q;
+}
+
+// np.argmax's order: (v, i) beats (bv, bi) when v is larger, a NaN counting as the largest value, and the lower index wins among equals
+// (so the first NaN wins among several, and index 0 when everything is -inf).
+__device__ __forceinline__ bool pick_beats(double v, long long i, double bv, long long bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn != bn) return vn;
+    return (!vn && v > bv) || ((vn || v == bv) && i < bi);
+}
+
 // sel[step] = first arg-max of a*min_dist + b*unc (np.argmax); then unc[sel] = 0.  One block.
 __global__ __launch_bounds__(1024) void kcenter_pick_kernel(const double* __restrict__ min_dist, double* __restrict__ unc, double a, double b,
                                                             int32_t* __restrict__ sel, int step, long long n) {
     __shared__ double sv[16]; __shared__ long long si[16];
-    double bv = -INFINITY; long long bi = 0x7FFFFFFFFFFFFFFFLL;
+    double bv = -INFINITY; long long bi = 0x7FFFFFFFFFFFFFFFLL;          // loses to every item, -inf included
     for (long long i = threadIdx.x; i < n; i += 1024) {
-        const double v = a * (min_dist ? min_dist[i] : 0.0) + b * (unc ? unc[i] : 0.0);
-        if (v > bv) { bv = v; bi = i; }
+        const double v = pick_score(a, min_dist ? min_dist[i] : 0.0, b, unc ? unc[i] : 0.0);
+        if (pick_beats(v, i, bv, bi)) { bv = v; bi = i; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const double ov = __shfl_xor(bv, o, 64); const long long oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        if (pick_beats(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; ++w)
-            if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
-        if (bi == 0x7FFFFFFFFFFFFFFFLL) bi = 0;            // all -inf / nan: np.argmax returns 0
-        sel[step] = (int32_t)bi;
+            if (pick_beats(sv[w], si[w], bv, bi)) { bv = sv[w]; bi = si[w]; }
+        sel[step] = (int32_t)bi;                                         // n >= 1: thread 0 has seen item 0
         if (unc) unc[bi] = 0.0;
     }
 }

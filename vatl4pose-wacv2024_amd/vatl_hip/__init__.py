@@ -1143,9 +1143,21 @@ def oks(pred_kpts: torch.Tensor, gt_kpts: torch.Tensor, bbox_xywh: torch.Tensor)
     return out
 
 
+def _query_emb(emb):
+    if emb.dim() != 2 or emb.dtype != torch.float32 or not emb.is_contiguous():
+        raise ValueError(f"embeddings must be a contiguous 2-D float32 tensor, got {tuple(emb.shape)} {emb.dtype}")
+    return emb.shape
+
+
+def _query_vec(t, name, need, dtype=torch.float64):
+    """Host-side length / type check of a vector the query kernels index up to ``need`` entries of (shapes only: no device read)."""
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < need:
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of at least {need} entries, got {t.numel()} of {t.dtype}")
+
+
 def cosine_rowsum(emb: torch.Tensor) -> torch.Tensor:
-    """(n, D) fp32 -> (n,) float64 sums of cosine distances to every row (incl. itself: 0)."""
-    n, d = emb.shape
+    """(n, D) fp32 -> (n,) float64 sums of cosine distances to every row (incl. itself: 0; a zero row: n - 1)."""
+    n, d = _query_emb(emb)
     out = torch.empty(n, device=emb.device, dtype=torch.float64)
     ws = torch.empty(n + d, device=emb.device, dtype=torch.float64)
     _check(lib().vatl_cosine_rowsum(_ptr(emb), n, d, _ptr(out, torch.float64), _ptr(ws, torch.float64), _stream()), "vatl_cosine_rowsum")
@@ -1153,11 +1165,24 @@ def cosine_rowsum(emb: torch.Tensor) -> torch.Tensor:
 
 
 def kcenter_update(emb, centers: torch.Tensor, min_dist: torch.Tensor, first: bool):
+    """min_dist[:n] = min(min_dist[:n], distance to the nearest of ``centers``) (``first``: no previous value).  ``centers`` holds
+    row indices below n on the device; they are the caller's to keep in range (they are not read back here)."""
+    n, _ = _query_emb(emb)
+    _query_vec(centers, "centers", 0, torch.int32)
+    _query_vec(min_dist, "min_dist", n)
     _check(lib().vatl_kcenter_update(_ptr(emb), emb.shape[0], emb.shape[1], _ptr(centers, torch.int32), centers.numel(), _ptr(min_dist, torch.float64),
                                      int(first), _stream()), "vatl_kcenter_update")
 
 
 def kcenter_pick(min_dist, unc, a: float, b: float, selected: torch.Tensor, step: int, n: int):
+    """selected[step] = np.argmax(a * min_dist[:n] + b * unc[:n]) (a missing array counts as zeros); then unc[selected[step]] = 0."""
+    if n <= 0 or step < 0 or (min_dist is None and unc is None):
+        raise ValueError(f"kcenter_pick: need n > 0, step >= 0 and at least one score array (n={n}, step={step})")
+    if min_dist is not None:
+        _query_vec(min_dist, "min_dist", n)
+    if unc is not None:
+        _query_vec(unc, "unc", n)
+    _query_vec(selected, "selected", step + 1, torch.int32)
     _check(lib().vatl_kcenter_pick(_ptr(min_dist, torch.float64), _ptr(unc, torch.float64), a, b, _ptr(selected, torch.int32), step, n, _stream()),
            "vatl_kcenter_pick")
 
