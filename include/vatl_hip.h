@@ -528,9 +528,27 @@ int vatl_col_sum(const float* x, int64_t M, int C, float* out, double* workspace
  * vatl_deform_columns: col[p][t * C + c] = m * S(...), row stride col_stride >= 9 C (a multiple of 4; the padding columns are
  *   zeroed), which a 1x1 GEMM with the filter as [Cout][t * C + c] turns into `out` (training forward; second implementation).
  * vatl_deform_columns_bwd: from dcol (same layout) the gradients dx (N,H,W,C; zeroed here, then accumulated with float atomics: its
- *   summation order, and so its last bits, vary from run to run), d_offset[p * d_offset_stride + 18 g + 2 t (+ 1)] and
+ *   summation order, and so its last bits, vary from run to run — the default; vatl_deform_columns_bwd_ordered is the bit-reproducible
+ *   form), d_offset[p * d_offset_stride + 18 g + 2 t (+ 1)] and
  *   d_mask[p * d_mask_stride + 9 g + t] (with mask_is_logits: the gradient of the logit), both reduced over the group's channels in a
- *   fixed order; 0 where S is 0 by the validity rule.  d_mask is NULL exactly when mask is. */
+ *   fixed order; 0 where S is 0 by the validity rule.  d_mask is NULL exactly when mask is.
+ * vatl_deform_columns_bwd_ordered: the same call (same checks and refusals, same d_offset / d_mask bits: the same kernel code) with a
+ *   dx whose bits are the same on every run, opt-in.  No float atomic, no memset of dx: every element of dx is written once by a plain
+ *   store.  With w[k] the bilinear weight of corner k = 0..3 ((y0,x0) (y0,x1) (y1,x0) (y1,x1)) of tap t of output pixel p and m its
+ *   modulation, the CONTRIBUTIONS to dx[n][y][x][c] are the (p, t, k) of image n whose corner k is pixel (y, x) and whose
+ *   wk = w[k] * m (one multiply, rounded once) is != 0 — the test of the atomic entry.  They are summed in ascending order of
+ *       key = ((p_local * 9 + t) * 4 + k),   p_local = the output pixel's row-major index yo * Wo + xo inside image n,
+ *   as
+ *       acc = +0.0f;  for each contribution, ascending key:  acc = acc + (dcol[p][t * C + c] * wk);   dx = acc
+ *   with the product and the sum each rounded once to float32 (no fma).  An input pixel no tap reaches gets +0.0f.  This is the
+ *   per-term arithmetic of the atomic entry in one fixed order, so the two agree to the rounding of a float32 sum.
+ *   `workspace` (16-byte aligned device memory, contents ignored and overwritten) holds the inverted index: counts, list starts and
+ *   cursors (3 ints per list, one list per input pixel and deformable group, padded to 16 bytes) and room for the worst case of
+ *   4 * P * 9 * dg entries of 8 bytes {int key; float wk}:
+ *       vatl_deform_dx_index_bytes = (12 * N * H * W * dg + 15) / 16 * 16 + 8 * 4 * N * Ho * Wo * 9 * dg
+ *   (negative: the arguments are not served, or a count would reach 2^30).  A workspace smaller than that is refused with VATL_EINVAL
+ *   before anything is launched.  The kernels are separate launches on `stream`; the workspace may be reused by the next call on the
+ *   same stream. */
 int vatl_deform_conv2d_supported(int C, int Cout, int stride, int deform_groups);
 int vatl_deform_conv2d_fwd(const float* x, const float* w_tcc, const float* offset, int offset_stride, const float* mask_or_null,
                            int mask_stride, int mask_is_logits, const float* scale, const float* bias, float* y, int N, int H, int W,
@@ -542,6 +560,11 @@ int vatl_deform_columns_bwd(const float* dcol, int col_stride, const float* x, c
                             const float* mask_or_null, int mask_stride, int mask_is_logits, float* dx, float* d_offset,
                             int d_offset_stride, float* d_mask_or_null, int d_mask_stride, int N, int H, int W, int C, int stride,
                             int deform_groups, void* stream);
+int64_t vatl_deform_dx_index_bytes(int N, int H, int W, int stride, int deform_groups);
+int vatl_deform_columns_bwd_ordered(const float* dcol, int col_stride, const float* x, const float* offset, int offset_stride,
+                                    const float* mask_or_null, int mask_stride, int mask_is_logits, float* dx, float* d_offset,
+                                    int d_offset_stride, float* d_mask_or_null, int d_mask_stride, int N, int H, int W, int C, int stride,
+                                    int deform_groups, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Fine-tune step pieces (ActiveLearning.py:662-677)

@@ -374,9 +374,10 @@ class _ConvBN:
 class _DeformConvBN:
     """conv2_offset + deformable conv2 (DCN v1 / v2) + BatchNorm2d(train) + ReLU of a DCN bottleneck, on the column route
     (csrc/deform_conv.hip): forward = offset conv (bias, no BatchNorm), deform_columns, the 1x1 GEMM with the batch statistics from its
-    epilogue; backward = BatchNorm backward, weight and data gradient of the GEMM, deform_columns_bwd (dx by float atomics: a DCN
-    network's step is reproducible in value, not in bits), then the offset conv's bias, weight and data gradients — the last one takes
-    the deformable dx as its epilogue residual, so the sum is the gradient of the tensor both convs read."""
+    epilogue; backward = BatchNorm backward, weight and data gradient of the GEMM, deform_columns_bwd (dx by float atomics by default: a DCN
+    network's step is then reproducible in value, not in bits; with the ordered path — layers.dcn.set_deterministic, or torch's
+    deterministic flags, read when the backward runs — it is bit-reproducible), then the offset conv's bias, weight and data gradients —
+    the last one takes the deformable dx as its epilogue residual, so the sum is the gradient of the tensor both convs read."""
 
     def __init__(self, blk):
         self.conv, self.off, self.bn = blk.conv2, blk.conv2_offset, blk.bn2
@@ -409,7 +410,7 @@ class _DeformConvBN:
 
     def backward(self, dy, grads, pre=None, consumer=None):
         """-> (gradient of the block's conv1 output, None).  ``consumer`` is not served: the caller runs conv1's BatchNorm backward unfused."""
-        from .layers.dcn import columns_backward
+        from .layers.dcn import columns_backward, is_deterministic
         assert consumer is None
         x, o, col, z, mean, invstd, mask = self.saved
         self.saved = None
@@ -423,7 +424,7 @@ class _DeformConvBN:
         wt = self.conv.weight.detach()
         gpad = (self.offc + 31) // 32 * 32                  # the offset conv's output gradient, zero behind its channels (as the 17-joint head's)
         dxd, d_off, _, dw = columns_backward(dz, col, vh.deform_gemm_weight(wt), x, o, self.mask, wt, self.stride, self.dg, grad_channels=gpad,
-                                             dw_out=_gout(grads, self.conv.weight))
+                                             dw_out=_gout(grads, self.conv.weight), deterministic=is_deterministic())
         grads[self.conv.weight] = dw
         grads[self.off.bias] = vh.col_sum(d_off)[:self.offc].contiguous()
         grads[self.off.weight] = vh.conv2d_wgrad(x, d_off, self.offc, self.cin, 3, 3, self.stride, 1, out=_gout(grads, self.off.weight))

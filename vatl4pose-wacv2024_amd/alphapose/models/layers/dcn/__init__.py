@@ -4,11 +4,18 @@ groups 1 only (what the Bottleneck uses).  Deformable RoI pooling is not provide
 
 The modules work on their own with NCHW tensors and autograd: one ``torch.autograd.Function`` over the column route —
 ``deform_columns`` writes the sampled, mask-weighted matrix, the 1x1 GEMMs multiply it; backward = weight gradient and data
-gradient of that GEMM, then ``deform_columns_bwd``.  Its dx is accumulated with float atomics, so a gradient through a deformable
-layer is reproducible in value, not in bits.  Inside a pose network the inference plan (hip_engine) and the trainer (hip_train)
-call the same kernels on NHWC tensors directly, conv2_offset included.  The two ``...Pack`` classes own their offset conv as an
-ordinary ``nn.Conv2d`` and evaluate it with torch before the deformable kernels run; no network of this package uses them.
+gradient of that GEMM, then ``deform_columns_bwd``.  By default its dx is accumulated with float atomics, so a gradient through a
+deformable layer is reproducible in value, not in bits.  The ordered path sums the same terms through an inverted index in one fixed
+order: with it every gradient of a deformable layer, and so a DCN network's fine-tune step, is bit-reproducible.  It is switched on
+by ``set_deterministic(True)``, inside ``with deterministic():``, or — the switch's default, None — whenever
+``torch.are_deterministic_algorithms_enabled()`` or ``torch.backends.cudnn.deterministic`` is true (what the driver's ``--seedfix``
+sets); ``set_deterministic(False)`` keeps the atomics whatever torch says.  The switch is read when a backward runs.
+
+Inside a pose network the inference plan (hip_engine) and the trainer (hip_train) call the same kernels on NHWC tensors directly,
+conv2_offset included.  The two ``...Pack`` classes own their offset conv as an ordinary ``nn.Conv2d`` and evaluate it with torch
+before the deformable kernels run; no network of this package uses them.
 """
+import contextlib
 import math
 
 import torch
@@ -17,7 +24,30 @@ from torch.nn.modules.utils import _pair
 
 import vatl_hip as vh
 
-__all__ = ["DeformConv", "DeformConvPack", "ModulatedDeformConv", "ModulatedDeformConvPack", "deform_conv", "modulated_deform_conv"]
+__all__ = ["DeformConv", "DeformConvPack", "ModulatedDeformConv", "ModulatedDeformConvPack", "deform_conv", "modulated_deform_conv",
+           "set_deterministic", "is_deterministic", "deterministic"]
+
+
+def set_deterministic(mode):
+    """The process switch of the deformable backward's dx: True = the ordered, bit-reproducible path, False = float atomics, None (the
+    default) = follow torch (``torch.are_deterministic_algorithms_enabled()`` or ``torch.backends.cudnn.deterministic``)."""
+    vh.set_deform_deterministic(mode)
+
+
+def is_deterministic() -> bool:
+    """Whether a deformable backward that ran now would take the ordered path."""
+    return vh.deform_deterministic()
+
+
+@contextlib.contextmanager
+def deterministic(mode=True):
+    """``with deterministic():`` the ordered path (or ``mode``) for the backwards that run inside; the previous setting returns."""
+    before = vh.deform_deterministic_mode()
+    vh.set_deform_deterministic(mode)
+    try:
+        yield
+    finally:
+        vh.set_deform_deterministic(before)
 
 
 def _pad32(c: int) -> int:
@@ -37,8 +67,9 @@ def columns_forward(xh, oh, mask, weight, stride: int, dg: int):
     return vh.deform_columns(xh, oh, mask, stride, dg), vh.deform_gemm_weight(weight)
 
 
-def columns_backward(dzh, col, wg, xh, oh, mask, weight, stride: int, dg: int, grad_channels=None, dw_out=None):
-    """dzh (N,Ho,Wo,pad32(Cout)) NHWC, zero behind Cout -> (dx NHWC, d_offset, d_mask, dw (Cout,C,3,3))."""
+def columns_backward(dzh, col, wg, xh, oh, mask, weight, stride: int, dg: int, grad_channels=None, dw_out=None, deterministic=None):
+    """dzh (N,Ho,Wo,pad32(Cout)) NHWC, zero behind Cout -> (dx NHWC, d_offset, d_mask, dw (Cout,C,3,3)).  ``deterministic``: the
+    dx path (None = the process switch, resolved here)."""
     co, c = weight.shape[:2]
     k = wg.shape[1]
     n, ho, wo, _ = col.shape
@@ -51,7 +82,8 @@ def columns_backward(dzh, col, wg, xh, oh, mask, weight, stride: int, dg: int, g
         dw = dw.contiguous()
     wd = vh.pack_dgrad_weight(wg, [(0, 0)], cout_k=dzh.shape[3], planned=False)
     dcol = vh.conv2d_fwd_ex(dzh, wd, k, 1, 1, 1, 0, 0, ho, wo, ho, wo, 1, 1, 0, 0)
-    dx, d_off, d_mask = vh.deform_columns_bwd(dcol, xh, oh, mask, stride, dg, grad_channels=grad_channels)
+    dx, d_off, d_mask = vh.deform_columns_bwd(dcol, xh, oh, mask, stride, dg, grad_channels=grad_channels,
+                                              deterministic=is_deterministic() if deterministic is None else bool(deterministic))
     return dx, d_off, d_mask, dw
 
 
@@ -83,7 +115,7 @@ class _DeformConvFunction(torch.autograd.Function):
         with torch.no_grad():
             dzh = vh.nchw_to_nhwc(dy.detach().float().contiguous(), _pad32(co))
             wg = vh.deform_gemm_weight(weight.detach().float())
-            dxh, d_off, d_mask, dw = columns_backward(dzh, col, wg, xh, oh, mh, weight, stride, dg)
+            dxh, d_off, d_mask, dw = columns_backward(dzh, col, wg, xh, oh, mh, weight, stride, dg, deterministic=is_deterministic())
             dx = vh.nhwc_to_nchw(dxh)
             doff = vh.nhwc_to_nchw(d_off)[:, :off_ch]
             dmask = None if d_mask is None else vh.nhwc_to_nchw(d_mask)

@@ -5,37 +5,13 @@
 //   deform_columns_kernel      the sampled, mask-weighted matrix [pixels][9*C] that the 1x1 GEMMs then multiply (training forward, and
 //                              the second implementation the fused one is checked against);
 //   deform_columns_bwd_kernel  its backward: dx by float atomics (vector memory instructions), d_offset / d_mask by a fixed-order
-//                              reduction over the deformable group's channels.
+//                              reduction over the deformable group's channels.  The ordered, bit-reproducible dx is
+//                              deform_dx_ordered.hip's; it runs this kernel without the atomics for d_offset / d_mask.
 // Offsets and masks are read per pixel with a caller-given stride, so that they can stay inside conv2_offset's NHWC output
 // ([18*dg offsets | 9*dg mask logits] per pixel); a mask that arrives as logits gets its sigmoid here.
-#include "common.h"
-#include "deform_sample.h"
+#include "deform_tap.h"
 
 namespace vatl {
-
-struct DeformGeom {
-    int N, H, W, C, Ho, Wo, stride, dg, Cg;           // Cg = C / dg channels per deformable group
-    long long P;                                       // N * Ho * Wo output pixels
-    const float* offset; int off_stride;               // offset[p * off_stride + 18 g + 2 t (+1)]
-    const float* mask; int mask_stride, mask_logits;   // mask[p * mask_stride + 9 g + t], NULL = 1
-};
-
-struct DeformTap { DeformSample s; float m, raw; long long base; };   // base = n * H * W: pixel index of the image's first pixel
-
-// everything the three kernels need to know about (output pixel p, tap t, deformable group g)
-__device__ __forceinline__ DeformTap deform_tap(const DeformGeom& q, long long p, int t, int g) {
-    const int xo = (int)(p % q.Wo);
-    const long long r = p / q.Wo;
-    const int yo = (int)(r % q.Ho);
-    const long long n = r / q.Ho;
-    const float* o = q.offset + p * q.off_stride + 18 * g + 2 * t;
-    DeformTap d;
-    d.s = deform_sample(deform_pos(yo, q.stride, t / 3, o[0]), deform_pos(xo, q.stride, t % 3, o[1]), q.H, q.W);
-    d.raw = q.mask ? q.mask[p * q.mask_stride + 9 * g + t] : 1.f;
-    d.m = (q.mask && q.mask_logits) ? deform_sigmoid(d.raw) : d.raw;
-    d.base = n * q.H * q.W;
-    return d;
-}
 
 // ---- fused forward ------------------------------------------------------------------------------------------------------------
 // A block owns 32 output pixels x up to 128 output channels (4 waves x one 32x32 accumulator).  Phase 1: for every (pixel, tap,
@@ -141,8 +117,9 @@ __global__ void deform_columns_kernel(const float* __restrict__ x, DeformGeom q,
 // ---- backward of the columns --------------------------------------------------------------------------------------------------
 // 16 lanes own one (pixel, tap, deformable group): lane l takes the group's 4-channel runs l, l + 16, ...  Per channel with
 // v = dcol: dx[corner k] += v * m * w[k] (float atomics: the order in which pixels meet at a corner is not fixed, so dx is not
-// bit-reproducible); d_mask += v * S, d_py += v * m * sum_k gy[k] x_k, d_px likewise, summed per lane in channel order and then
+// bit-reproducible — kAddDx = false leaves dx alone: the ordered entry sums it through an index); d_mask += v * S, d_py += v * m * sum_k gy[k] x_k, d_px likewise, summed per lane in channel order and then
 // across the 16 lanes by a butterfly — a fixed order.  Where the position fails the validity rule all three are 0.
+template <bool kAddDx>
 __global__ void deform_columns_bwd_kernel(const float* __restrict__ dcol, int col_stride, const float* __restrict__ x, DeformGeom q,
                                           float* __restrict__ dx, float* __restrict__ d_offset, int d_off_stride,
                                           float* __restrict__ d_mask, int d_mask_stride) {
@@ -170,7 +147,7 @@ __global__ void deform_columns_bwd_kernel(const float* __restrict__ dcol, int co
                     s[c] = fmaf(d.s.w[k], xv[c], s[c]);
                     ty[c] = fmaf(d.s.gy[k], xv[c], ty[c]);
                     tx[c] = fmaf(d.s.gx[k], xv[c], tx[c]);
-                    if (wk != 0.f) unsafeAtomicAdd(dx + at + c, v[c] * wk);
+                    if (kAddDx && wk != 0.f) unsafeAtomicAdd(dx + at + c, v[c] * wk);
                 }
             }
 #pragma unroll
@@ -186,21 +163,29 @@ __global__ void deform_columns_bwd_kernel(const float* __restrict__ dcol, int co
     }
 }
 
-static int deform_geom(const char* who, DeformGeom& q, const float* offset, int off_stride, const float* mask, int mask_stride, int mask_logits,
-                       int N, int H, int W, int C, int stride, int dg) {
-    if (!offset || N <= 0 || H <= 0 || W <= 0) return fail(VATL_EINVAL, "%s: null pointer or empty tensor", who);
-    if (stride != 1 && stride != 2) return fail(VATL_EINVAL, "%s: stride %d (1 or 2)", who, stride);
-    if (dg != 1 && dg != 2 && dg != 4) return fail(VATL_EINVAL, "%s: %d deformable groups (1, 2 or 4)", who, dg);
-    if (C <= 0 || C % 16) return fail(VATL_EINVAL, "%s: C %d must be a multiple of 16", who, C);
-    if (off_stride < 18 * dg || (mask && mask_stride < 9 * dg)) return fail(VATL_EINVAL, "%s: offset / mask stride too small", who);
-    q.N = N; q.H = H; q.W = W; q.C = C; q.stride = stride; q.dg = dg; q.Cg = C / dg;
-    q.Ho = (H + 2 - 3) / stride + 1; q.Wo = (W + 2 - 3) / stride + 1;
-    q.P = (long long)N * q.Ho * q.Wo;
-    q.offset = offset; q.off_stride = off_stride; q.mask = mask; q.mask_stride = mask_stride; q.mask_logits = mask ? mask_logits : 0;
-    const long long lim = 1LL << 30;
-    if ((long long)N * H * W * C >= lim || q.P * 9 * C >= lim || q.P * (long long)off_stride >= lim || q.P * (long long)mask_stride >= lim)
-        return fail(VATL_EINVAL, "%s: a tensor exceeds 2^30 elements; split the batch", who);
+int deform_bwd_check(const char* who, DeformGeom& q, const float* dcol, int col_stride, const float* x, const float* offset, int offset_stride,
+                     const float* mask_or_null, int mask_stride, int mask_is_logits, const float* dx, const float* d_offset, int d_offset_stride,
+                     const float* d_mask_or_null, int d_mask_stride, int N, int H, int W, int C, int stride, int deform_groups) {
+    if (!dcol || !x || !dx || !d_offset) return fail(VATL_EINVAL, "%s: null pointer", who);
+    if ((mask_or_null == nullptr) != (d_mask_or_null == nullptr)) return fail(VATL_EINVAL, "%s: mask and d_mask go together", who);
+    if (int rc = deform_geom(who, q, offset, offset_stride, mask_or_null, mask_stride, mask_is_logits, N, H, W, C, stride, deform_groups)) return rc;
+    if (col_stride < 9 * C || (col_stride & 3) || q.P * col_stride >= (1LL << 30)) return fail(VATL_EINVAL, "%s: column stride %d invalid", who, col_stride);
+    if (d_offset_stride < 18 * deform_groups || (d_mask_or_null && d_mask_stride < 9 * deform_groups) || q.P * (long long)d_offset_stride >= (1LL << 30) ||
+        q.P * (long long)d_mask_stride >= (1LL << 30))
+        return fail(VATL_EINVAL, "%s: gradient stride invalid", who);
     return 0;
+}
+
+void deform_bwd_launch(bool add_dx, const float* dcol, int col_stride, const float* x, const DeformGeom& q, float* dx, float* d_offset,
+                       int d_offset_stride, float* d_mask_or_null, int d_mask_stride, hipStream_t st) {
+    const long long threads = q.P * 9 * q.dg * 16;
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (add_dx)
+        hipLaunchKernelGGL(deform_columns_bwd_kernel<true>, grid, dim3(256), 0, st, dcol, col_stride, x, q, dx, d_offset, d_offset_stride, d_mask_or_null,
+                           d_mask_stride);
+    else
+        hipLaunchKernelGGL(deform_columns_bwd_kernel<false>, grid, dim3(256), 0, st, dcol, col_stride, x, q, dx, d_offset, d_offset_stride, d_mask_or_null,
+                           d_mask_stride);
 }
 
 }  // namespace vatl
@@ -245,18 +230,12 @@ extern "C" int vatl_deform_columns_bwd(const float* dcol, int col_stride, const 
                                        const float* mask_or_null, int mask_stride, int mask_is_logits, float* dx, float* d_offset,
                                        int d_offset_stride, float* d_mask_or_null, int d_mask_stride, int N, int H, int W, int C, int stride,
                                        int deform_groups, void* stream) {
-    if (!dcol || !x || !dx || !d_offset) return fail(VATL_EINVAL, "deform_columns_bwd: null pointer");
-    if ((mask_or_null == nullptr) != (d_mask_or_null == nullptr)) return fail(VATL_EINVAL, "deform_columns_bwd: mask and d_mask go together");
     DeformGeom q{};
-    if (int rc = deform_geom("deform_columns_bwd", q, offset, offset_stride, mask_or_null, mask_stride, mask_is_logits, N, H, W, C, stride, deform_groups)) return rc;
-    if (col_stride < 9 * C || (col_stride & 3) || q.P * col_stride >= (1LL << 30)) return fail(VATL_EINVAL, "deform_columns_bwd: column stride %d invalid", col_stride);
-    if (d_offset_stride < 18 * deform_groups || (d_mask_or_null && d_mask_stride < 9 * deform_groups) || q.P * (long long)d_offset_stride >= (1LL << 30) ||
-        q.P * (long long)d_mask_stride >= (1LL << 30))
-        return fail(VATL_EINVAL, "deform_columns_bwd: gradient stride invalid");
+    if (int rc = deform_bwd_check("deform_columns_bwd", q, dcol, col_stride, x, offset, offset_stride, mask_or_null, mask_stride, mask_is_logits, dx, d_offset,
+                                  d_offset_stride, d_mask_or_null, d_mask_stride, N, H, W, C, stride, deform_groups))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(dx, 0, (size_t)N * H * W * C * sizeof(float), st) != hipSuccess) return fail(VATL_ELAUNCH, "deform_columns_bwd: memset failed");
-    const long long threads = q.P * 9 * deform_groups * 16;
-    hipLaunchKernelGGL(deform_columns_bwd_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, dcol, col_stride, x, q, dx, d_offset,
-                       d_offset_stride, d_mask_or_null, d_mask_stride);
+    deform_bwd_launch(true, dcol, col_stride, x, q, dx, d_offset, d_offset_stride, d_mask_or_null, d_mask_stride, st);
     return check_launch("deform_columns_bwd");
 }

@@ -158,6 +158,8 @@ SIGNATURES = {
     "vatl_deform_conv2d_fwd": (_i, [_p, _p, _p, _i, _p, _i, _i, _p, _p, _p] + [_i] * 8 + [_p]),
     "vatl_deform_columns": (_i, [_p, _p, _i, _p, _i, _i, _p, _i] + [_i] * 6 + [_p]),
     "vatl_deform_columns_bwd": (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i] + [_i] * 6 + [_p]),
+    "vatl_deform_dx_index_bytes": (_i64, [_i] * 5),
+    "vatl_deform_columns_bwd_ordered": (_i, [_p, _i, _p, _p, _i, _p, _i, _i, _p, _p, _i, _p, _i] + [_i] * 6 + [_p, _i64, _p]),
     "vatl_masked_mse_workspace_floats": (_i64, [_i64]),
     "vatl_masked_mse_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "vatl_l1_joint_regression_fwd_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
@@ -1700,10 +1702,46 @@ def deform_columns(x, offset, mask, stride: int, dg: int, mask_logits: bool = Fa
     return col
 
 
-def deform_columns_bwd(dcol, x, offset, mask, stride: int, dg: int, mask_logits: bool = False, grad_channels: int | None = None):
+# Process switch of the deformable backward's dx (public face: alphapose.models.layers.dcn.set_deterministic / is_deterministic /
+# deterministic): True = the ordered, bit-reproducible entry, False = float atomics, None (the default) = follow torch.
+_deform_deterministic = None
+
+
+def set_deform_deterministic(mode):
+    global _deform_deterministic
+    if mode not in (True, False, None):
+        raise ValueError(f"deterministic mode {mode!r}: True, False or None (follow torch)")
+    _deform_deterministic = mode
+
+
+def deform_deterministic_mode():
+    """The switch as it was set: True, False or None."""
+    return _deform_deterministic
+
+
+def deform_deterministic() -> bool:
+    """The switch resolved now: with None the ordered path is on when torch.are_deterministic_algorithms_enabled() or
+    torch.backends.cudnn.deterministic is."""
+    if _deform_deterministic is None:
+        return bool(torch.are_deterministic_algorithms_enabled() or torch.backends.cudnn.deterministic)
+    return _deform_deterministic
+
+
+def deform_dx_index_bytes(n: int, h: int, w: int, stride: int, dg: int) -> int:
+    """Workspace bytes of the ordered dx (the inverted index): include/vatl_hip.h states the formula."""
+    b = int(lib().vatl_deform_dx_index_bytes(n, h, w, stride, dg))
+    if b < 0:
+        _check(b, "vatl_deform_dx_index_bytes")
+    return b
+
+
+def deform_columns_bwd(dcol, x, offset, mask, stride: int, dg: int, mask_logits: bool = False, grad_channels: int | None = None,
+                       deterministic: bool | None = None):
     """Backward of deform_columns -> (dx, d_offset, d_mask).  d_offset is (N,Ho,Wo,grad_channels or offset's channel count), zero
     behind the gradients; with ``mask is True`` the logit gradients follow the offset gradients inside it (the layout of ``offset``) and
-    d_mask is None.  dx comes from float atomics: equal in value from run to run, not in bits."""
+    d_mask is None.  ``deterministic``: False = dx from float atomics (equal in value from run to run, not in bits); True = the ordered
+    entry, whose dx has the same bits on every run (its index workspace comes from torch's allocator, per call: stream-safe); None =
+    the process switch (``deform_deterministic()``).  d_offset and d_mask have the same bits either way."""
     (n, h, w, c, ho, wo), oargs = _deform_args("deform_columns_bwd", x, offset, mask, stride, dg, mask_logits)
     k = deform_col_stride(c)
     if tuple(dcol.shape) != (n, ho, wo, k):
@@ -1711,6 +1749,8 @@ def deform_columns_bwd(dcol, x, offset, mask, stride: int, dg: int, mask_logits:
     gc = grad_channels or offset.shape[3]
     if gc < (27 if mask is True else 18) * dg:
         raise VatlError("deform_columns_bwd: grad_channels too small")
+    if deterministic is None:
+        deterministic = deform_deterministic()
     dx = torch.empty_like(x)
     d_off = torch.zeros((n, ho, wo, gc), device=x.device, dtype=torch.float32)
     d_mask = None
@@ -1721,8 +1761,12 @@ def deform_columns_bwd(dcol, x, offset, mask, stride: int, dg: int, mask_logits:
         dm = (_ptr(d_mask), 9 * dg)
     else:
         dm = (None, 0)
-    _check(lib().vatl_deform_columns_bwd(_ptr(dcol), k, _ptr(x), *oargs, _ptr(dx), _ptr(d_off), gc, *dm, n, h, w, c, stride, dg, _stream()),
-           "vatl_deform_columns_bwd")
+    args = (_ptr(dcol), k, _ptr(x), *oargs, _ptr(dx), _ptr(d_off), gc, *dm, n, h, w, c, stride, dg)
+    if deterministic:
+        ws = torch.empty(deform_dx_index_bytes(n, h, w, stride, dg), device=x.device, dtype=torch.uint8)
+        _check(lib().vatl_deform_columns_bwd_ordered(*args, _ptr(ws, torch.uint8), ws.numel(), _stream()), "vatl_deform_columns_bwd_ordered")
+    else:
+        _check(lib().vatl_deform_columns_bwd(*args, _stream()), "vatl_deform_columns_bwd")
     return dx, d_off, d_mask
 
 
