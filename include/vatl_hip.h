@@ -926,6 +926,38 @@ int vatl_conv3x3_winograd_fwd_bnbwd(const float* x, const float* u, const float*
 int64_t vatl_checksum_block_words(void);
 int vatl_checksum_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, uint64_t* out, void* stream);
 
+/* FLOAT64 REFERENCE FORWARD (csrc/conv_f64.hip, csrc/glue_f64.hip; alphapose/models/hip_engine_f64.py).  The yardstick the fp32 routes
+ * are measured against, on the device: no product plan takes these entry points, they feed no FLOP meter and have no tuning knob.
+ * Every tensor is float64 NHWC unless stated; any channel count >= 1 is served and no padding is visible to the caller.
+ *
+ * vatl_pack_conv_weight_f64: nn.Conv2d weight (Cout,Cin,R,S) fp32 -> [Cout][R][S][Cin] float64 (exact).
+ * vatl_pack_deconv4x4s2_weight_f64: nn.ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) fp32 -> four 2x2 phase filters
+ *   [phase = py*2+px][Cout][ty][tx][Cin] float64 with ky = 3-py-2*ty, kx = 3-px-2*tx.
+ * vatl_conv2d_fwd_f64: implicit GEMM on v_mfma_f64_16x16x4_f64, M = N*Ho*Wo, N = Cout, K = R*S*Cin summed in ONE order (tap-major,
+ *   channels ascending; no split-K, no atomics): a pixel's bits depend on its receptive field only, not on its batch or position.
+ *   R, S <= 7, stride 1 or 2, any pad >= 0.  y = fma(acc, scale[c], bias[c]) (+ residual, laid out like y) (ReLU); scale / bias NULL =
+ *   1 / 0; out_nchw != 0 writes (N,Cout,Ho,Wo).
+ * vatl_deconv4x4s2_fwd_f64: x (N,H,W,Cin) -> y (N,2H,2W,Cout) as the four phases on the same kernel (K = 4*Cin each), same write-out. */
+int vatl_pack_conv_weight_f64(const float* w_oihw, double* w_packed, int Cout, int Cin, int R, int S, void* stream);
+int vatl_pack_deconv4x4s2_weight_f64(const float* w_iohw, double* w_packed, int Cin, int Cout, void* stream);
+int vatl_conv2d_fwd_f64(const double* x, const double* w, const double* scale, const double* bias, const double* residual, double* y,
+                        int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int relu, int out_nchw, void* stream);
+int vatl_deconv4x4s2_fwd_f64(const double* x, const double* w, const double* scale, const double* bias, double* y,
+                             int N, int H, int W, int Cin, int Cout, int relu, void* stream);
+/* Glue of the same forward, one thread per output element, every sum in one fixed order:
+ *   (N,C,H,W) fp32 (src_is_f64 == 0, converted exactly) or float64 -> (N,H,W,C) float64, and back;
+ *   MaxPool2d(3,2,1); AdaptiveAvgPool2d(1) -> (N,C), pixels summed in order; PixelShuffle(2), C % 4 == 0;
+ *   y = relu(x * sigmoid(gate[n][c]) + residual), gate (N,C) the second SE Linear's output before its sigmoid;
+ *   y = act(base + sum_k nearest_up(z_k, 2^shift_k)), up to three sources added in argument order (NULL = absent). */
+int vatl_nchw_to_nhwc_f64(const void* src, int src_is_f64, double* dst, int N, int C, int H, int W, void* stream);
+int vatl_nhwc_to_nchw_f64(const double* src, double* dst, int N, int C, int H, int W, void* stream);
+int vatl_maxpool3x3s2_fwd_f64(const double* x, double* y, int N, int H, int W, int C, void* stream);
+int vatl_gap_fwd_f64(const double* x, double* y, int N, int HW, int C, void* stream);
+int vatl_pixelshuffle2_fwd_f64(const double* x, double* y, int N, int H, int W, int C, void* stream);
+int vatl_se_scale_add_relu_f64(const double* x, const double* gate, const double* residual, double* y, int N, int HW, int C, void* stream);
+int vatl_fuse_upsample_add_f64(const double* base, const double* z0, int shift0, const double* z1, int shift1, const double* z2, int shift2,
+                               double* y, int N, int H, int W, int C, int relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

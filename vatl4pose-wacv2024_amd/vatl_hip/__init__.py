@@ -194,6 +194,17 @@ SIGNATURES = {
     "vatl_rmsprop_step": (_i, [_p, _p, _p, _i64, _d, _d, _d, _d, _p]),
     "vatl_rmsprop_step_multi": (_i, [_p, _i, _i64, _d, _d, _d, _d, _p]),
     "vatl_sgd_step": (_i, [_p, _p, _p, _i64, _d, _d, _d, _i, _p]),
+    "vatl_pack_conv_weight_f64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "vatl_pack_deconv4x4s2_weight_f64": (_i, [_p, _p, _i, _i, _p]),
+    "vatl_conv2d_fwd_f64": (_i, [_p] * 6 + [_i] * 11 + [_p]),
+    "vatl_deconv4x4s2_fwd_f64": (_i, [_p] * 5 + [_i] * 6 + [_p]),
+    "vatl_nchw_to_nhwc_f64": (_i, [_p, _i, _p, _i, _i, _i, _i, _p]),
+    "vatl_nhwc_to_nchw_f64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "vatl_maxpool3x3s2_fwd_f64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "vatl_gap_fwd_f64": (_i, [_p, _p, _i, _i, _i, _p]),
+    "vatl_pixelshuffle2_fwd_f64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "vatl_se_scale_add_relu_f64": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "vatl_fuse_upsample_add_f64": (_i, [_p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib = None
@@ -2254,3 +2265,121 @@ def sgd_step(p, g, buf, step: int, lr: float, momentum: float = 0.9, weight_deca
 def adamw_step(p, g, m, v, step: int, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8):
     _check(lib().vatl_adamw_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, betas[0], betas[1], eps, weight_decay, step, _stream()),
            "vatl_adamw_step")
+
+
+# ----------------------------------------------------------------------------
+# float64 reference forward (csrc/conv_f64.hip, csrc/glue_f64.hip): NHWC float64 tensors, any channel count
+# ----------------------------------------------------------------------------
+
+def _new_f64(shape, like):
+    return torch.empty(shape, device=like.device, dtype=torch.float64)
+
+
+def pack_conv_weight_f64(w: torch.Tensor) -> torch.Tensor:
+    """(Cout,Cin,R,S) fp32 -> [Cout][R][S][Cin] float64 (exact)."""
+    cout, cin, r, s = w.shape
+    out = _new_f64((cout, r, s, cin), w)
+    _check(lib().vatl_pack_conv_weight_f64(_ptr(w.contiguous()), _f64(out), cout, cin, r, s, _stream()), "vatl_pack_conv_weight_f64")
+    return out
+
+
+def pack_deconv_weight_f64(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) fp32 -> four 2x2 phase filters [4][Cout][2][2][Cin] float64 (exact)."""
+    cin, cout, kh, kw = w.shape
+    if (kh, kw) != (4, 4):
+        raise VatlError(f"pack_deconv_weight_f64: a 4x4 filter is needed, got {kh}x{kw}")
+    out = _new_f64((4, cout, 2, 2, cin), w)
+    _check(lib().vatl_pack_deconv4x4s2_weight_f64(_ptr(w.contiguous()), _f64(out), cin, cout, _stream()), "vatl_pack_deconv4x4s2_weight_f64")
+    return out
+
+
+def conv2d_fwd_f64(x, w_packed, scale, bias, stride: int, pad: int, relu: bool, residual=None, out_nchw: bool = False, out=None):
+    """x (N,H,W,Cin) float64, w_packed from pack_conv_weight_f64 -> (N,Ho,Wo,Cout) float64 (or NCHW)."""
+    n, h, w, cin = x.shape
+    cout, r, s, cin_w = w_packed.shape
+    if cin_w != cin:
+        raise VatlError(f"conv2d_fwd_f64: input has {cin} channels, the filter {cin_w}")
+    ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+    shape = (n, cout, ho, wo) if out_nchw else (n, ho, wo, cout)
+    if out is None:
+        out = _new_f64(shape, x)
+    elif tuple(out.shape) != shape:
+        raise VatlError(f"conv2d_fwd_f64: out has shape {tuple(out.shape)}, expected {shape}")
+    if residual is not None and tuple(residual.shape) != shape:
+        raise VatlError(f"conv2d_fwd_f64: residual has shape {tuple(residual.shape)}, expected {shape}")
+    _check(lib().vatl_conv2d_fwd_f64(_f64(x), _f64(w_packed), _f64(scale), _f64(bias), _f64(residual), _f64(out), n, h, w, cin, cout, r, s, stride, pad,
+                                     int(relu), int(out_nchw), _stream()), "vatl_conv2d_fwd_f64")
+    return out
+
+
+def deconv4x4s2_fwd_f64(x, w_packed, scale, bias, relu: bool):
+    n, h, w, cin = x.shape
+    cout = w_packed.shape[1]
+    if w_packed.shape[-1] != cin:
+        raise VatlError(f"deconv4x4s2_fwd_f64: input has {cin} channels, the filter {w_packed.shape[-1]}")
+    y = _new_f64((n, 2 * h, 2 * w, cout), x)
+    _check(lib().vatl_deconv4x4s2_fwd_f64(_f64(x), _f64(w_packed), _f64(scale), _f64(bias), _f64(y), n, h, w, cin, cout, int(relu), _stream()),
+           "vatl_deconv4x4s2_fwd_f64")
+    return y
+
+
+def nchw_to_nhwc_f64(x: torch.Tensor) -> torch.Tensor:
+    """(N,C,H,W) fp32 or float64 -> (N,H,W,C) float64; fp32 converts exactly."""
+    if x.dtype not in (torch.float32, torch.float64):
+        raise VatlError(f"nchw_to_nhwc_f64: expected fp32 or float64, got {x.dtype}")
+    n, c, h, w = x.shape
+    y = _new_f64((n, h, w, c), x)
+    _check(lib().vatl_nchw_to_nhwc_f64(_ptr(x, x.dtype), int(x.dtype == torch.float64), _f64(y), n, c, h, w, _stream()), "vatl_nchw_to_nhwc_f64")
+    return y
+
+
+def nhwc_to_nchw_f64(x: torch.Tensor) -> torch.Tensor:
+    n, h, w, c = x.shape
+    y = _new_f64((n, c, h, w), x)
+    _check(lib().vatl_nhwc_to_nchw_f64(_f64(x), _f64(y), n, c, h, w, _stream()), "vatl_nhwc_to_nchw_f64")
+    return y
+
+
+def maxpool3x3s2_fwd_f64(x):
+    n, h, w, c = x.shape
+    y = _new_f64((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), x)
+    _check(lib().vatl_maxpool3x3s2_fwd_f64(_f64(x), _f64(y), n, h, w, c, _stream()), "vatl_maxpool3x3s2_fwd_f64")
+    return y
+
+
+def gap_fwd_f64(x):
+    n, h, w, c = x.shape
+    y = _new_f64((n, c), x)
+    _check(lib().vatl_gap_fwd_f64(_f64(x), _f64(y), n, h * w, c, _stream()), "vatl_gap_fwd_f64")
+    return y
+
+
+def pixelshuffle2_fwd_f64(x):
+    n, h, w, c = x.shape
+    y = _new_f64((n, 2 * h, 2 * w, c // 4), x)
+    _check(lib().vatl_pixelshuffle2_fwd_f64(_f64(x), _f64(y), n, h, w, c, _stream()), "vatl_pixelshuffle2_fwd_f64")
+    return y
+
+
+def se_scale_add_relu_f64(x, gate, residual):
+    n, h, w, c = x.shape
+    if tuple(gate.shape) != (n, c) or residual.shape != x.shape:
+        raise VatlError("se_scale_add_relu_f64: gate must be (N,C) and the residual shaped like x")
+    y = torch.empty_like(x)
+    _check(lib().vatl_se_scale_add_relu_f64(_f64(x), _f64(gate), _f64(residual), _f64(y), n, h * w, c, _stream()), "vatl_se_scale_add_relu_f64")
+    return y
+
+
+def fuse_upsample_add_f64(base, ups, relu: bool):
+    """base (N,H,W,C); ups = [(z, shift)] with z (N,H>>shift,W>>shift,C), at most 3, added in list order."""
+    n, h, w, c = base.shape
+    if len(ups) > 3:
+        raise VatlError("fuse_upsample_add_f64: at most three up-sampled sources")
+    for z, sh in ups:
+        if tuple(z.shape) != (n, h >> sh, w >> sh, c):
+            raise VatlError(f"fuse_upsample_add_f64: source {tuple(z.shape)} does not match {tuple(base.shape)} >> {sh}")
+    y = torch.empty_like(base)
+    a = list(ups) + [(None, 0)] * (3 - len(ups))
+    _check(lib().vatl_fuse_upsample_add_f64(_f64(base), _f64(a[0][0]), a[0][1], _f64(a[1][0]), a[1][1], _f64(a[2][0]), a[2][1], _f64(y),
+                                            n, h, w, c, int(relu), _stream()), "vatl_fuse_upsample_add_f64")
+    return y
