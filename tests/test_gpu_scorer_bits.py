@@ -5,15 +5,17 @@
                          bn_train.hip): the fused stem tail relies on the pool kernels agreeing bit for bit, and the step on being reproducible.
   tests/wino43_cases.py  tests/golden/wino43_bits.npz  the F(4x3,2x2) Winograd kernels and their filter packs (csrc/winograd_deconv43.hip, winograd_s2_43.hip,
                          winograd43.h, winograd_stage.h, tile_order.h) and one layer per route of csrc/conv_winograd.hip's launcher.
+  tests/train_epilogue_cases.py  tests/golden/train_epilogue_bits.npz  the training write-outs of the convolutions (csrc/bn_epilogue.h in conv_igemm.h,
+                         conv_winograd.hip, winograd_f4.hip): stored tensor, float64 (sum, sum^2) / (sum g, sum g * xhat) partials, block and route counts.
 Any moved bit is a failure, whatever moved it."""
 import numpy as np
 import pytest
 
-from tests import glue_cases, scorer_cases, wino43_cases
+from tests import glue_cases, scorer_cases, train_epilogue_cases, wino43_cases
 
 pytestmark = pytest.mark.gpu
 
-MODULES = (scorer_cases, glue_cases, wino43_cases)
+MODULES = (scorer_cases, glue_cases, wino43_cases, train_epilogue_cases)
 assert len({name for m in MODULES for name in m.CASES}) == sum(len(m.CASES) for m in MODULES)
 
 

@@ -2,10 +2,11 @@
 
     VATL_HIP_LIB=/path/to/parent/libvatl_hip.so python tools/make_scorer_bits.py <parent commit hash> [out.npz] [--cases tests.glue_cases]
 
-A cases module has ``CASES`` (name -> case), ``GOLDEN`` (the fixture's path) and ``run(vatl_hip, name) -> {key: bits}``.  There are three:
+A cases module has ``CASES`` (name -> case), ``GOLDEN`` (the fixture's path) and ``run(vatl_hip, name) -> {key: bits}``.  There are four:
   tests.scorer_cases (the default)  tests/golden/scorer_bits.npz   csrc/decode.hip, localpeak.hip, heatmap_criteria.hip, pose_feature.hip, scorer_common.h
   tests.glue_cases                  tests/golden/glue_bits.npz     csrc/layout.hip, pool.hip, fusion.hip, pack.hip (bn_fold), bn_train.hip, glue_common.h
   tests.wino43_cases                tests/golden/wino43_bits.npz   csrc/winograd_deconv43.hip, winograd_s2_43.hip, winograd43.h, winograd_stage.h, tile_order.h, conv_winograd.hip (launcher)
+  tests.train_epilogue_cases        tests/golden/train_epilogue_bits.npz  csrc/bn_epilogue.h and the training write-outs of conv_igemm.h, conv_winograd.hip, winograd_f4.hip
 
 Run on the MI355X against a library built from the commit BEFORE a change to those kernels, never against the tree's own library: the
 fixture exists so that a change of their arithmetic — a compiler upgrade, an edit — shows as a failure of tests/test_gpu_scorer_bits.py.

@@ -8,6 +8,7 @@
 //   per-channel column sums (conv bias gradient).
 // Reductions are two-stage (per-block double partials, then a finalize kernel): deterministic.
 #include "pool.h"
+#include "bn_epilogue.h"
 
 namespace vatl {
 
@@ -74,11 +75,6 @@ __device__ __forceinline__ void col_store(const ColLane& L, f32x4 s, f32x4 q, do
         }
     }
 }
-// one row of the backward reduction: (sum g, sum g * xhat)
-__device__ __forceinline__ void fold_g_xhat(f32x4& s, f32x4& q, f32x4 g, f32x4 zz, f32x4 mu, f32x4 is) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { s[e] += g[e]; q[e] += g[e] * ((zz[e] - mu[e]) * is[e]); }
-}
 // dz = A[c]*g + B[c]*z + C[c] for the four channels of column c4
 __device__ __forceinline__ f32x4 bn_dz(f32x4 g, f32x4 zz, const float* __restrict__ A, const float* __restrict__ B, const float* __restrict__ Cc, int c4) {
     const f32x4 a = *reinterpret_cast<const f32x4*>(A + c4 * 4);
@@ -99,10 +95,7 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict
     const int c4 = L.c4, rstep = L.rstep;
     f32x4 s = {0.f, 0.f, 0.f, 0.f}, q = {0.f, 0.f, 0.f, 0.f};
     if (L.active(C)) {
-        f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = {1.f, 1.f, 1.f, 1.f};
-        f32x4 msc = {0.f, 0.f, 0.f, 0.f}, mbi = {1.f, 1.f, 1.f, 1.f};
-        if (MODE == 1) { mu = *reinterpret_cast<const f32x4*>(mean + c4 * 4); is = *reinterpret_cast<const f32x4*>(invstd + c4 * 4); }
-        if (MODE == 1 && mscale) { msc = *reinterpret_cast<const f32x4*>(mscale + c4 * 4); mbi = *reinterpret_cast<const f32x4*>(mbias + c4 * 4); }
+        const BnConsts bk = bn_consts(mean, invstd, mscale, mbias, c4 * 4, MODE == 1);
         const f32x4* __restrict__ a4 = reinterpret_cast<const f32x4*>(a);
         const f32x4* __restrict__ y4 = reinterpret_cast<const f32x4*>(y);
         const f32x4* __restrict__ z4 = reinterpret_cast<const f32x4*>(z);
@@ -111,12 +104,11 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict
         // flight per step); the accumulation order is the plain row order either way
         auto fold = [&](f32x4 v, f32x4 yy, f32x4 zz) {
             if (MODE == 0) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { s[e] += v[e]; q[e] += v[e] * v[e]; }
+                fold_stats(s, q, v);
             } else {
                 if (y) v = relu_mask(yy, v);
-                if (mscale) v = relu_mask(zz, msc, mbi, v);
-                fold_g_xhat(s, q, v, zz, mu, is);
+                if (mscale) v = relu_mask(zz, bk.msc, bk.mbi, v);
+                fold_g_xhat(s, q, v, zz, bk.mu, bk.is);
             }
         };
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "buffer.h"
+#include "bn_epilogue.h"
 
 namespace vatl {
 
@@ -134,6 +135,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
             const __amdgpu_buffer_rsrc_t mr = buf_rsrc(p.bmy, p.bmy ? p.y_bytes : 0u);
             const int n = n0 + c4 * 4;
             const bool nv = n < p.Cout;                    // Cout % 4 == 0 on this path: the float4 is in range or entirely out
+            // (bn_epilogue.h's bn_consts, kept as text here: through the function the 128x32 instantiation spills 6 instead of 2 scalar registers)
             const f32x4 one = {1.f, 1.f, 1.f, 1.f}, nul = {0.f, 0.f, 0.f, 0.f};
             const f32x4 mu = nv ? *reinterpret_cast<const f32x4*>(p.bmu + n) : nul, is = nv ? *reinterpret_cast<const f32x4*>(p.bis + n) : nul;
             const f32x4 msc = (nv && p.bsc) ? *reinterpret_cast<const f32x4*>(p.bsc + n) : nul;
@@ -148,11 +150,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
 #pragma unroll
             for (int u = 0; u < NP; ++u) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(&Cs[(r0 + u * RPP) * LDC + c4 * 4]);
+                // (bn_epilogue.h's bn_masked_grad, kept as text here: through the function the 128x128 instantiation takes 243 instead of 238 VGPRs
+                // and its 1024 -> 256 data gradient at 120 crops measured 1.7 % slower; the bit fixture pins that the product below fuses into the sum)
                 f32x4 g;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float d = v[c] + rsv[u][c];
-                    const bool on = p.bmy ? yt[u][c] > 0.f : fmaf(zt[u][c], msc[c], mbi[c]) > 0.f;
+                    const bool on = p.bmy ? yt[u][c] > 0.f : relu_on(zt[u][c], msc[c], mbi[c]);
                     g[c] = on ? d : 0.f;
                     ssum[c] += g[c];
                     ssq[c] += g[c] * ((zt[u][c] - mu[c]) * is[c]);       // rows >= M: d = 0 exactly
@@ -167,38 +171,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x16 (&acc)
 #pragma unroll
             for (int c = 0; c < 4; ++c) o[c] = fmaxf(v[c] + rsv[u][c], lo);
             buf_store4(yr, offv[u], o);
-            if (p.stats) {
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { ssum[c] += o[c]; ssq[c] += o[c] * o[c]; }   // rows >= M hold exact zeros
-            }
+            if (p.stats) fold_stats(ssum, ssq, o);     // rows >= M hold exact zeros
         }
         }
         if (p.stats) {
             // BatchNorm batch statistics of the tile just stored (training forward): per-thread fp32 sums over NP rows,
             // combined over the RPP row groups in double, one (sum, sum^2) pair per (row block, channel) — the layout
             // bn_train_finalize_kernel reduces in a fixed order (deterministic, no atomics).
-            lds_barrier();                                 // every thread is done reading Cs (LDS hand-off only: __syncthreads() would wait for the tile's stores)
-            f32x4* sh = reinterpret_cast<f32x4*>(smem);
-            sh[tid] = ssum; sh[NT + tid] = ssq;
-            lds_barrier();
-            if (tid < C4) {
-                double ds[4] = {0, 0, 0, 0}, dq[4] = {0, 0, 0, 0};
-#pragma unroll 2                                           // (full unrolling cost the 128x32 kernel 256 VGPRs and spills)
-                for (int k = 0; k < RPP; ++k) {
-                    const f32x4 a = sh[k * C4 + tid], b = sh[NT + k * C4 + tid];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) { ds[c] += a[c]; dq[c] += b[c]; }
-                }
-                const long long rb = (long long)blockIdx.y * p.m_tiles + m0 / BM;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int n = n0 + tid * 4 + c;
-                    if (n < p.Cout) {
-                        p.stats[(rb * p.Cout + n) * 2 + 0] = ds[c];
-                        p.stats[(rb * p.Cout + n) * 2 + 1] = dq[c];
-                    }
-                }
-            }
+            // (every thread is done reading Cs once it is past the combine's first barrier)
+            stats_block_store<NT, C4>(smem, tid, ssum, ssq, p.stats, (long long)blockIdx.y, p.m_tiles, m0 / BM, n0, p.Cout);
         }
     } else {
         // NCHW output (heat-map head) or a channel count that is not a multiple of 4:

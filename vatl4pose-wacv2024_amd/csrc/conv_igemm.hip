@@ -918,9 +918,7 @@ static int conv2d_fwd_ex_impl(const float* x, const float* w, const float* scale
     if (xe >= (1LL << 30) || ye >= (1LL << 30) || we >= (1LL << 30))
         return fail(VATL_EINVAL, "conv2d_fwd_ex: a tensor exceeds 2^30 elements (32-bit buffer offsets); split the batch");
     p.x_bytes = (unsigned)(xe * 4); p.y_bytes = (unsigned)(ye * 4); p.w_bytes = (unsigned)(we * 4);
-    if (bn_z) {
-        if (!stats || !row_blocks_used || !bn_mean || !bn_invstd || relu || scale || bias || (bn_scale && !bn_bias))
-            return fail(VATL_EINVAL, "conv2d_fwd_ex_bnbwd: needs z, mean, invstd, a statistics buffer; no scale / bias / ReLU of its own");
+    if (bn_z) {                                           // (vatl_conv2d_fwd_ex_bnbwd, which checked the fusion arguments and passes no scale / bias / ReLU)
         p.bz = bn_z; p.bmy = bn_mask_y; p.bsc = bn_scale; p.bbi = bn_bias; p.bmu = bn_mean; p.bis = bn_invstd; p.stats = stats;
     }
     return dispatch(p, 1, false, (hipStream_t)stream, row_blocks_used);
@@ -942,7 +940,7 @@ extern "C" int vatl_conv2d_fwd_ex_bnbwd(const float* x, const float* w, const fl
                                         int CoutPad, int R, int S, int stride, int pad_y, int pad_x, int Ho, int Wo, int OH, int OW, int osy, int osx,
                                         int ooy, int oox, const float* bn_z, const float* bn_mask_y, const float* bn_scale, const float* bn_bias,
                                         const float* bn_mean, const float* bn_invstd, double* stats, int64_t* row_blocks_used, void* stream) {
-    if (!bn_z) return fail(VATL_EINVAL, "conv2d_fwd_ex_bnbwd: null bn_z");
+    if (int rc = bnbwd_args_check("conv2d_fwd_ex_bnbwd", bn_z, bn_scale, bn_bias, bn_mean, bn_invstd, stats, row_blocks_used)) return rc;
     return conv2d_fwd_ex_impl(x, w, nullptr, nullptr, residual, y, N, H, W, Cin, Cout, CoutPad, R, S, stride, pad_y, pad_x, Ho, Wo, OH, OW, osy, osx, ooy,
                               oox, 0, bn_z, bn_mask_y, bn_scale, bn_bias, bn_mean, bn_invstd, stats, row_blocks_used, stream);
 }

@@ -40,6 +40,7 @@
 // The per-output arithmetic depends only on the tile's own pixels: results are independent of the batch position (SURVEY.md §7 hard part 3).
 #include "common.h"
 #include "buffer.h"
+#include "bn_epilogue.h"
 #include "tile_order.h"
 #include "tune.h"
 #include "winograd_stage.h"
@@ -410,14 +411,12 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
         const bool nv = n < p.Cout;
         const f32x4 one = {1.f, 1.f, 1.f, 1.f}, nul = {0.f, 0.f, 0.f, 0.f};
         const float lo = p.relu ? 0.f : -INFINITY;
-        f32x4 sc = one, bi = nul, mu = nul, is = nul, msc = nul, mbi = one;       // no mask: 0 * z + 1 > 0
+        f32x4 sc = one, bi = nul;
+        BnConsts bk;
         auto request_consts = [&]() {
             if (nv && p.scale) sc = *reinterpret_cast<const f32x4*>(p.scale + n);
             if (nv && p.bias) bi = *reinterpret_cast<const f32x4*>(p.bias + n);
-            if (BNB && nv) {
-                mu = *reinterpret_cast<const f32x4*>(p.bmu + n); is = *reinterpret_cast<const f32x4*>(p.bis + n);
-                if (p.bsc) { msc = *reinterpret_cast<const f32x4*>(p.bsc + n); mbi = *reinterpret_cast<const f32x4*>(p.bbi + n); }
-            }
+            bk = bn_consts(p.bmu, p.bis, p.bsc, p.bbi, n, BNB && nv);
         };
         unsigned off[MO][MO];                                  // [pass u][output row a] of the thread's (tile, output column, channel quad)
         f32x4 rs[MO][MO];
@@ -503,18 +502,8 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
                     else { zt[a] = buf_load4(zr, off[u][a]); yt[a] = p.bmy ? buf_load4(mr, off[u][a]) : nul; }
                 }
     #pragma unroll
-                for (int a = 0; a < MO; ++a) {
-                    f32x4 gq;
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const float d = yv[a][c] + rs[u][a][c];
-                        const bool on = p.bmy ? yt[a][c] > 0.f : fmaf(zt[a][c], msc[c], mbi[c]) > 0.f;
-                        gq[c] = (on && off[u][a] != WOOB) ? d : 0.f;
-                        ssum[c] += gq[c];
-                        ssq[c] += gq[c] * ((zt[a][c] - mu[c]) * is[c]);
-                    }
-                    buf_store4(yr, off[u][a], gq);
-                }
+                for (int a = 0; a < MO; ++a)
+                    buf_store4(yr, off[u][a], bn_masked_grad(yv[a] + rs[u][a], zt[a], yt[a], p.bmy != nullptr, bk, ssum, ssq, off[u][a] != WOOB));
             } else {
     #pragma unroll
                 for (int a = 0; a < MO; ++a) {
@@ -522,38 +511,12 @@ __device__ __forceinline__ void winograd_body(const WinoParams& p, float* smem, 
     #pragma unroll
                     for (int c = 0; c < 4; ++c) o[c] = fmaxf(yv[a][c] * sc[c] + bi[c] + rs[u][a][c], lo);
                     buf_store4(yr, off[u][a], o);
-                    if (p.stats && off[u][a] != WOOB) {
-    #pragma unroll
-                        for (int c = 0; c < 4; ++c) { ssum[c] += o[c]; ssq[c] += o[c] * o[c]; }
-                    }
+                    if (p.stats && off[u][a] != WOOB) fold_stats(ssum, ssq, o);
                 }
             }
         }
-        if (p.stats) {
-            // BatchNorm batch statistics of the pixels just stored: one (sum, sum^2) double pair per (row block, channel), fixed order
-            lds_barrier();
-            f32x4* sh = reinterpret_cast<f32x4*>(smem);
-            sh[tid] = ssum; sh[NT + tid] = ssq;
-            lds_barrier();
-            if (tid < C4) {
-                double ds[4] = {0, 0, 0, 0}, dq[4] = {0, 0, 0, 0};
-    #pragma unroll 2
-                for (int k = 0; k < NT / C4; ++k) {
-                    const f32x4 a = sh[k * C4 + tid], b = sh[NT + k * C4 + tid];
-    #pragma unroll
-                    for (int c = 0; c < 4; ++c) { ds[c] += a[c]; dq[c] += b[c]; }
-                }
-                const long long rb = (long long)phase * p.m_tiles + m_tile;
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int nn = n0h + tid * 4 + c;
-                    if (nn < p.Cout) {
-                        p.stats[(rb * p.Cout + nn) * 2 + 0] = ds[c];
-                        p.stats[(rb * p.Cout + nn) * 2 + 1] = dq[c];
-                    }
-                }
-            }
-        }
+        // BatchNorm batch statistics of the pixels just stored: one (sum, sum^2) double pair per (row block, channel), fixed order
+        if (p.stats) stats_block_store<NT, C4>(smem, tid, ssum, ssq, p.stats, (long long)phase, p.m_tiles, m_tile, n0h, p.Cout);
         if (NB > 1 && hh + 1 < NB) lds_barrier();          // the next half's tiles go where this one's were read (this half's stores stay in flight)
     }
 }
@@ -1142,8 +1105,7 @@ extern "C" int vatl_conv3x3_winograd_fwd_stats(const float* x, const float* u, f
 extern "C" int vatl_conv3x3_winograd_fwd_bnbwd(const float* x, const float* u, const float* residual, float* y, int N, int H, int W, int Cin, int Cout,
                                                const float* bn_z, const float* bn_mask_y, const float* bn_scale, const float* bn_bias,
                                                const float* bn_mean, const float* bn_invstd, double* stats, int64_t* row_blocks_used, void* stream) {
-    if (!bn_z || !stats || !row_blocks_used || !bn_mean || !bn_invstd || (bn_scale && !bn_bias))
-        return fail(VATL_EINVAL, "conv3x3_winograd_fwd_bnbwd: needs z, mean, invstd and a statistics buffer");
+    if (int rc = bnbwd_args_check("conv3x3_winograd_fwd_bnbwd", bn_z, bn_scale, bn_bias, bn_mean, bn_invstd, stats, row_blocks_used)) return rc;
     const WinoBn bn{bn_z, bn_mask_y, bn_scale, bn_bias, bn_mean, bn_invstd};
     return winograd_impl(2, x, u, nullptr, nullptr, residual, y, stats, row_blocks_used, N, H, W, Cin, Cout, 0, stream, &bn);
 }
@@ -1185,8 +1147,7 @@ extern "C" int vatl_deconv4x4s2_winograd_dgrad_bnbwd(const float* dz, const floa
                                                      int Cout, const float* bn_z, const float* bn_mask_y, const float* bn_scale,
                                                      const float* bn_bias, const float* bn_mean, const float* bn_invstd, double* stats,
                                                      int64_t* row_blocks_used, void* stream) {
-    if (!bn_z || !stats || !row_blocks_used || !bn_mean || !bn_invstd || (bn_scale && !bn_bias))
-        return fail(VATL_EINVAL, "deconv4x4s2_winograd_dgrad_bnbwd: needs z, mean, invstd and a statistics buffer");
+    if (int rc = bnbwd_args_check("deconv4x4s2_winograd_dgrad_bnbwd", bn_z, bn_scale, bn_bias, bn_mean, bn_invstd, stats, row_blocks_used)) return rc;
     const WinoBn bn{bn_z, bn_mask_y, bn_scale, bn_bias, bn_mean, bn_invstd};
     return winograd_impl(3, dz, u, nullptr, nullptr, residual, dx, stats, row_blocks_used, N, H, W, Cout, Cin, 0, stream, &bn, true);
 }

@@ -28,6 +28,7 @@
 // The per-output arithmetic depends only on the tile's own pixels: results do not depend on the batch position.
 #include "common.h"
 #include "buffer.h"
+#include "bn_epilogue.h"
 #include "winograd_pack.h"
 
 #include <atomic>
@@ -322,11 +323,9 @@ __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_ti
         const f32x4 one = {1.f, 1.f, 1.f, 1.f}, nul = {0.f, 0.f, 0.f, 0.f};
         const f32x4 sc = (MODE == 0 && p.scale) ? *reinterpret_cast<const f32x4*>(p.scale + n) : one;
         const f32x4 bi = (MODE == 0 && p.bias) ? *reinterpret_cast<const f32x4*>(p.bias + n) : nul;
-        f32x4 mu = nul, is = nul, msc = nul, mbi = one;    // MODE 2 (no mask given: 0 * z + 1 > 0)
+        const BnConsts bk = bn_consts(p.bmu, p.bis, p.bsc, p.bbi, n, MODE == 2);
         __amdgpu_buffer_rsrc_t zr = yr, mr = yr;
         if constexpr (MODE == 2) {
-            mu = *reinterpret_cast<const f32x4*>(p.bmu + n); is = *reinterpret_cast<const f32x4*>(p.bis + n);
-            if (p.bsc) { msc = *reinterpret_cast<const f32x4*>(p.bsc + n); mbi = *reinterpret_cast<const f32x4*>(p.bbi + n); }
             zr = buf_rsrc(p.bz, p.y_bytes);
             mr = buf_rsrc(p.bmy ? p.bmy : p.bz, p.bmy ? p.y_bytes : 0u);
         }
@@ -361,19 +360,12 @@ __device__ __forceinline__ void f4_body(const F4Params& p, float* smem, int m_ti
             o[3] = d12 + 8.f * d34 + z5;
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
-                f32x4 v;
+                f32x4 v = o[a];
+                if constexpr (MODE == 0) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if constexpr (MODE == 0) v[c] = fmaxf(fmaf(o[a][c], sc[c], bi[c]) + rs[a][c], lo);
-                    else if constexpr (MODE == 1) { v[c] = o[a][c]; s1[c] += v[c]; s2[c] += v[c] * v[c]; }       // tiles past the end: exact zeros
-                    else {
-                        const float d = o[a][c] + rs[a][c];
-                        const bool on = p.bmy ? yt[a][c] > 0.f : fmaf(zt[a][c], msc[c], mbi[c]) > 0.f;
-                        v[c] = on ? d : 0.f;
-                        s1[c] += v[c];
-                        s2[c] += v[c] * ((zt[a][c] - mu[c]) * is[c]);
-                    }
-                }
+                    for (int c = 0; c < 4; ++c) v[c] = fmaxf(fmaf(o[a][c], sc[c], bi[c]) + rs[a][c], lo);
+                } else if constexpr (MODE == 1) fold_stats(s1, s2, v);                                          // tiles past the end: exact zeros
+                else v = bn_masked_grad(o[a] + rs[a], zt[a], yt[a], p.bmy != nullptr, bk, s1, s2);
                 buf_store4(yr, ok ? base + a * rowb : 0xFFFFFFF0u, v);
             }
         }
@@ -478,8 +470,6 @@ static int f4_impl(int mode, const float* x, const float* u, const float* scale,
     if (!vatl_conv3x3_winograd_f4_supported(N, H, W, Cin, Cout))
         return fail(VATL_EINVAL, "conv3x3_winograd_f4: serves H, W multiples of 4, Cin >= 64 a multiple of 16, Cout a multiple of 64 (got %d x %d, %d -> %d)", H, W, Cin, Cout);
     if (mode != 0 && !stats) return fail(VATL_EINVAL, "conv3x3_winograd_f4: the training epilogues need a statistics buffer");
-    if (mode == 2 && (!fuse || !fuse->z || !fuse->mean || !fuse->invstd || (!fuse->scale != !fuse->bias)))
-        return fail(VATL_EINVAL, "conv3x3_winograd_f4_fwd_bnbwd: needs the consumer layer's conv output and saved statistics (and scale WITH bias, or neither)");
     F4Params p{};
     p.x = x; p.u = u; p.scale = scale; p.bias = bias; p.res = residual; p.y = y; p.stats = stats;
     if (fuse) { p.bz = fuse->z; p.bmy = fuse->mask_y; p.bsc = fuse->scale; p.bbi = fuse->bias; p.bmu = fuse->mean; p.bis = fuse->invstd; }
@@ -530,6 +520,7 @@ extern "C" int vatl_conv3x3_winograd_f4_fwd_stats(const float* x, const float* u
 extern "C" int vatl_conv3x3_winograd_f4_fwd_bnbwd(const float* x, const float* u, const float* residual, float* y, int N, int H, int W, int Cin, int Cout, const float* bn_z,
                                                   const float* bn_mask_y, const float* bn_scale, const float* bn_bias, const float* bn_mean, const float* bn_invstd,
                                                   double* stats, int64_t* row_blocks_used, void* stream) {
+    if (int rc = bnbwd_args_check("conv3x3_winograd_f4_fwd_bnbwd", bn_z, bn_scale, bn_bias, bn_mean, bn_invstd, stats, row_blocks_used)) return rc;
     const F4Fuse f{bn_z, bn_mask_y, bn_scale, bn_bias, bn_mean, bn_invstd};
     return f4_impl(2, x, u, nullptr, nullptr, residual, y, stats, row_blocks_used, &f, N, H, W, Cin, Cout, 0, stream);
 }
