@@ -2,11 +2,13 @@
 SimpleBaseline-R50 256x192 at B = 120 and FastPose-R152 384x288 at B = 32 through bench.finetune_step_fn's exact sequence
 (arena.begin -> Trainer.backward(arena, overlap=True) -> finish -> attach -> AdamW; reference: ActiveLearning.py:657-673).
 
-The small-batch tests (tests/test_gpu_train.py) pin every kernel instantiation on its own; at these sizes the dispatch rules pick
-routes no small batch reaches — Winograd weight gradients with two gradient halves per block (>= 256 channels), their
-staging-address tables, two-half forward blocks (launches of >= 400 blocks), the two-stream weight gradients — and this file
-asserts the COMPOSITION: values against the float64 oracle graph on the same batch, bit-reproducibility, stream-order
-independence, and (through the library's route counters) that those routes really ran.
+The small-batch tests pin every kernel instantiation on its own (tests/test_gpu_train.py; the weight gradients, tile by tile and
+branch by branch, in tests/test_gpu_wgrad.py: the Winograd weight gradient with two gradient halves per block depends on the channel
+counts alone (>= 256) and is held to float64 there on 2 x 8 x 6 batches, its staging-address tables included).  At these sizes the
+dispatch rules also pick routes no small batch reaches — two-half forward blocks (launches of >= 400 blocks), the two-stream weight
+gradients — and this file asserts the COMPOSITION: values against the float64 oracle graph on the same batch, bit-reproducibility,
+stream-order independence, and (through the library's route counters) that those routes, the two-half weight gradient among them,
+really ran.
 
 Gradient yardstick: with the bench's default initialisation the trunk gradients are ill-conditioned — torch's own fp32 run of the
 same graph is 2e-2 (R50) / 1.2e-1 (R152) away from the float64 gradients in the trunk, 6e-7 in the head (measured on MI355X's host,

@@ -1483,9 +1483,22 @@ def _grad_out(who: str, out, shape, ws_floats: int, device):
     return dw, torch.empty(int(ws_floats), device=device, dtype=torch.float32)
 
 
+def _check_grad_pair(who: str, x, g, cx: int, grid):
+    """The two operands of a weight-gradient launch describe the same batch: x (N,H,W,cx) and the gradient (N,*grid,C).  The kernels
+    take the pixel grid from x and the filter geometry alone; a gradient of another grid would be read with the wrong strides."""
+    if x.dim() != 4 or g.dim() != 4:
+        raise VatlError(f"{who}: operands must be NHWC (4-D), got {tuple(x.shape)} and {tuple(g.shape)}")
+    if x.shape[3] != cx:
+        raise VatlError(f"{who}: input has {x.shape[3]} channels, the layer reads {cx}")
+    if min(grid) < 1 or (g.shape[0], g.shape[1], g.shape[2]) != (x.shape[0], *grid):
+        raise VatlError(f"{who}: gradient {tuple(g.shape)} does not match the batch {x.shape[0]} and the grid {grid[0]}x{grid[1]} that the "
+                        f"input {tuple(x.shape)} gives")
+
+
 def conv2d_wgrad(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: int, out=None) -> torch.Tensor:
     """x NHWC (N,H,W,Cin or 4 for the stem), dz NHWC (N,Ho,Wo,CoutG) -> dw (Cout,Cin,R,S) (written into ``out`` when
     given: a slice of the flat gradient arena)."""
+    _check_grad_pair("conv2d_wgrad", x, dz, 4 if cin == 3 else cin, ((x.shape[1] + 2 * pad - r) // stride + 1, (x.shape[2] + 2 * pad - s) // stride + 1))
     n, h, w, _ = x.shape
     m = n * dz.shape[1] * dz.shape[2]
     dw, ws = _grad_out("conv2d_wgrad", out, (cout, cin, r, s), lib().vatl_conv2d_wgrad_workspace_floats(cout, cin, r, s, m), x.device)
@@ -1496,6 +1509,7 @@ def conv2d_wgrad(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: i
 
 def conv3x3_winograd_wgrad(x, dz, out=None) -> torch.Tensor:
     """Weight gradient of a 3x3 / stride 1 / pad 1 conv on the Winograd route: x (N,H,W,Cin), dz (N,H,W,Cout) -> dw (Cout,Cin,3,3)."""
+    _check_grad_pair("conv3x3_winograd_wgrad", x, dz, x.shape[-1], tuple(x.shape[1:3]))
     n, h, w, cin = x.shape
     cout = dz.shape[3]
     dw, ws = _grad_out("conv3x3_winograd_wgrad", out, (cout, cin, 3, 3), lib().vatl_conv3x3_winograd_wgrad_workspace_floats(cout, cin, n, h, w), x.device)
@@ -1505,6 +1519,7 @@ def conv3x3_winograd_wgrad(x, dz, out=None) -> torch.Tensor:
 
 def deconv4x4s2_winograd_wgrad(x, dy, out=None) -> torch.Tensor:
     """Weight gradient of ConvTranspose2d(4,2,1) on the Winograd route: x (N,H,W,Cin), dy (N,2H,2W,Cout) -> dw (Cin,Cout,4,4)."""
+    _check_grad_pair("deconv4x4s2_winograd_wgrad", x, dy, x.shape[-1], (2 * x.shape[1], 2 * x.shape[2]))
     n, h, w, cin = x.shape
     cout = dy.shape[3]
     dw, ws = _grad_out("deconv4x4s2_winograd_wgrad", out, (cin, cout, 4, 4), lib().vatl_deconv4x4s2_winograd_wgrad_workspace_floats(cin, cout, n, h, w), x.device)
@@ -1513,6 +1528,8 @@ def deconv4x4s2_winograd_wgrad(x, dy, out=None) -> torch.Tensor:
 
 
 def deconv4x4s2_wgrad(x, dy, out=None) -> torch.Tensor:
+    """Weight gradient of ConvTranspose2d(4,2,1) as an implicit GEMM: x (N,H,W,Cin), dy (N,2H,2W,Cout) -> dw (Cin,Cout,4,4)."""
+    _check_grad_pair("deconv4x4s2_wgrad", x, dy, x.shape[-1], (2 * x.shape[1], 2 * x.shape[2]))
     n, h, w, cin = x.shape
     cout = dy.shape[3]
     dw, ws = _grad_out("deconv4x4s2_wgrad", out, (cin, cout, 4, 4), lib().vatl_deconv4x4s2_wgrad_workspace_floats(cin, cout, n * h * w), x.device)
