@@ -958,6 +958,42 @@ int vatl_se_scale_add_relu_f64(const double* x, const double* gate, const double
 int vatl_fuse_upsample_add_f64(const double* base, const double* z0, int shift0, const double* z1, int shift1, const double* z2, int shift2,
                                double* y, int N, int H, int W, int C, int relu, void* stream);
 
+/* 16-BIT INFERENCE ROUTE (csrc/conv_h16.hip, csrc/glue_h16.hip; alphapose/models/hip_engine_h16.py).  Opt-in (cfg.VAL.PRECISION): no
+ * product plan of the fp32 path takes these entry points, they feed no FLOP meter and have no tuning knob.  "T" is the 16-bit storage
+ * type named by `dtype`: 0 = float16, 1 = bfloat16.  Operands and stored activations are T, every product is accumulated in fp32, the
+ * write-out is computed in fp32 and rounded once to T (round to nearest even, IEEE overflow to infinity: no saturation).  Tensors are
+ * T NHWC and 16-byte aligned unless stated.  Contract: Cin % 8 == 0 (a 3-channel input is padded to 8 with zeros by
+ * vatl_nchw_to_nhwc_h16 and the filter packers pad Cin to match), Cout % 8 == 0 for T output, any Cout >= 1 for the fp32 NCHW
+ * write-out; anything else returns VATL_EINVAL and launches nothing.
+ *
+ * vatl_pack_conv_weight_h16: nn.Conv2d weight (Cout,Cin,R,S) fp32 -> [Cout][R][S][Cin8] T, Cin8 = Cin rounded up to 8, the padding zero.
+ * vatl_pack_deconv4x4s2_weight_h16: nn.ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) fp32 -> four 2x2 phase filters
+ *   [phase = py*2+px][Cout][ty][tx][Cin8] T with ky = 3-py-2*ty, kx = 3-px-2*tx.
+ * vatl_conv2d_fwd_h16: implicit GEMM on v_mfma_f32_16x16x32_{f16,bf16}, M = N*Ho*Wo, N = Cout, K = R*S*Cin summed in ONE order
+ *   (tap-major, channels ascending; no split-K, no atomics): a pixel's bits depend on its receptive field only, not on its batch or
+ *   position.  R, S <= 7, stride 1 or 2, any pad >= 0.  y = fmaf(acc, scale[c], bias[c]) (+ residual, T (N,Ho,Wo,Cout), added in fp32)
+ *   (ReLU); scale / bias fp32, NULL = 1 / 0; out_f32_nchw != 0 leaves the result fp32 and writes (N,Cout,Ho,Wo).
+ * vatl_deconv4x4s2_fwd_h16: x (N,H,W,Cin) -> y (N,2H,2W,Cout) T as the four phases on the same kernel (K = 4*Cin each), same write-out. */
+int vatl_pack_conv_weight_h16(const float* w_oihw, void* w_packed, int Cout, int Cin, int R, int S, int dtype, void* stream);
+int vatl_pack_deconv4x4s2_weight_h16(const float* w_iohw, void* w_packed, int Cin, int Cout, int dtype, void* stream);
+int vatl_conv2d_fwd_h16(const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y,
+                        int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int relu, int out_f32_nchw, int dtype, void* stream);
+int vatl_deconv4x4s2_fwd_h16(const void* x, const void* w, const float* scale, const float* bias, void* y,
+                             int N, int H, int W, int Cin, int Cout, int relu, int dtype, void* stream);
+/* Glue of the same route, C % 8 == 0 for every T NHWC tensor (a thread moves eight channels), every sum in fp32 in one fixed order:
+ *   (N,C,H,W) fp32 -> (N,H,W,C8) T with zero padding channels; (N,H,W,C) T -> (N,C,H,W) fp32 (exact, any C);
+ *   MaxPool2d(3,2,1); AdaptiveAvgPool2d(1) -> fp32 (N,C), pixels summed in order (any C); PixelShuffle(2), C % 4 == 0;
+ *   y = relu(x * sigmoid(gate[n][c]) + residual), gate fp32 (N,C) the second SE Linear's output before its sigmoid;
+ *   y = act(base + sum_k nearest_up(z_k, 2^shift_k)), up to three sources added in argument order (NULL = absent). */
+int vatl_nchw_to_nhwc_h16(const float* src, void* dst, int N, int C, int H, int W, int dtype, void* stream);
+int vatl_nhwc_to_nchw_h16(const void* src, float* dst, int N, int C, int H, int W, int dtype, void* stream);
+int vatl_maxpool3x3s2_fwd_h16(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
+int vatl_gap_fwd_h16(const void* x, float* y, int N, int HW, int C, int dtype, void* stream);
+int vatl_pixelshuffle2_fwd_h16(const void* x, void* y, int N, int H, int W, int C, int dtype, void* stream);
+int vatl_se_scale_add_relu_h16(const void* x, const float* gate, const void* residual, void* y, int N, int HW, int C, int dtype, void* stream);
+int vatl_fuse_upsample_add_h16(const void* base, const void* z0, int shift0, const void* z1, int shift1, const void* z2, int shift2,
+                               void* y, int N, int H, int W, int C, int relu, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

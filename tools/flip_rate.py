@@ -1,6 +1,12 @@
 """Arg-max flip rate of the timed fp32 stream route against the float64 reference ON THE DEVICE, on thousands of fresh crops.
 
     python tools/flip_rate.py --net simplepose_r50|fastpose_r50|hrnet_w32|fastpose_r152_384 [--crops N] [--seed S] [--out FILE]
+                              [--route stream|fp16|bf16]
+
+``--route fp16`` / ``bf16`` judges the opt-in 16-bit route (``hip_engine_h16.forward_h16``) instead of the stream route, against the same
+float64 reference on the same crops: the same fields (``crops_per_s_route`` and ``idx_route`` in place of the ``fp32`` names), plus
+``route`` and ``nonfinite_planes`` (planes of the route that hold an inf or a NaN), appended to profiles/h16_flips.jsonl by default; its flipped
+planes are counted, not listed one by one.
 
 The model gets torch's default initialisation under ``--seed``, BatchNorm running statistics are randomised (mean 0.1 * N(0,1), variance
 U(0.5, 1.5)), crops are ``rand - pixel mean``.  Both routes run on the same crops, block by block: ``hip_engine.forward_into`` (the route
@@ -41,6 +47,7 @@ NETS = {   # name: (MODEL cfg, input size, default crops)
 }
 BLOCK = 512          # crops generated, uploaded and run at a time
 MAX_LISTED = 512     # flipped planes listed one by one (the count is always complete)
+MAX_LISTED_H16 = 0    # ... of a 16-bit route, which flips thousands of near-ties: counted, not listed
 
 
 def build(name, seed):
@@ -133,9 +140,15 @@ def main():
     ap.add_argument("--net", required=True, choices=list(NETS))
     ap.add_argument("--crops", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "f64_reference_flips.jsonl"))
+    ap.add_argument("--route", default="stream", choices=["stream", "fp16", "bf16"])
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    from alphapose.models import hip_engine, hip_engine_f64
+    h16 = {"fp16": torch.float16, "bf16": torch.bfloat16}.get(args.route)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "f64_reference_flips.jsonl" if h16 is None else "h16_flips.jsonl")
+    from alphapose.models import hip_engine, hip_engine_f64, hip_engine_h16
+    route = hip_engine.forward_into if h16 is None else (lambda mod, t, out: hip_engine_h16.forward_h16(mod, t, out, dtype=h16))
+    tag = "fp32" if h16 is None else "route"
     cfg, hw, default_crops = NETS[args.net]
     n = args.crops or default_crops
     dev = torch.device("cuda:0")
@@ -147,7 +160,7 @@ def main():
     hm_hw = (hw[0] // 4, hw[1] // 4)
 
     t32 = t64 = 0.0
-    planes = flipped = 0
+    planes = flipped = nonfinite = 0
     flips = []
     min_gap_rel, max_diff, max_ref = float("inf"), 0.0, 0.0
     first = None
@@ -158,9 +171,9 @@ def main():
             x = x_host.to(dev)
             out32 = torch.empty((b - a, 17) + hm_hw, device=dev)
             if a == 0:                                              # plan build, lazy filter packs, library load: not timed
-                hip_engine.forward_into(m, x[:8], out32[:8])
+                route(m, x[:8], out32[:8])
                 hip_engine_f64.forward_f64(m, x[:2])
-            _, dt = _timed(lambda: hip_engine.forward_into(m, x, out32))
+            _, dt = _timed(lambda: route(m, x, out32))
             t32 += dt
             h64, dt = _timed(lambda: hip_engine_f64.forward_f64(m, x))
             t64 += dt
@@ -171,13 +184,14 @@ def main():
             top = f64.topk(2, dim=2).values
             gap_rel = (top[..., 0] - top[..., 1]) / (f64.amax(2) - f64.amin(2)).clamp_min(1e-300)
             planes += i64.numel()
+            nonfinite += int((~torch.isfinite(out32).flatten(2).all(2)).sum())
             min_gap_rel = min(min_gap_rel, float(gap_rel.min()))
             max_diff = max(max_diff, float((out32.double() - h64).abs().max()))
             max_ref = max(max_ref, float(h64.abs().max()))
             for c, j in torch.nonzero(i32 != i64).tolist():
                 flipped += 1
-                if len(flips) < MAX_LISTED:
-                    flips.append({"crop": a + c, "joint": j, "idx_fp32": int(i32[c, j]), "idx_f64": int(i64[c, j]), "gap_rel": float(gap_rel[c, j])})
+                if len(flips) < (MAX_LISTED if h16 is None else MAX_LISTED_H16):
+                    flips.append({"crop": a + c, "joint": j, f"idx_{tag}": int(i32[c, j]), "idx_f64": int(i64[c, j]), "gap_rel": float(gap_rel[c, j])})
             del x, out32, h64, f64, top, gap_rel
 
     # the host float64 path, once, on 16 crops
@@ -194,9 +208,11 @@ def main():
 
     row = {"net": args.net, "input": list(hw), "crops": n, "block": BLOCK, "seed": args.seed, "planes": planes, "flipped": flipped, "flip_rate": flipped / planes,
            "flips": flips, "flips_listed": len(flips), "min_gap_rel": min_gap_rel, "route_rel_err": max_diff / max_ref,
-           "crops_per_s_fp32": n / t32, "crops_per_s_f64": n / t64, "host_crops": k, "host_threads": threads, "host_crops_per_s": k / t_host,
+           f"crops_per_s_{tag}": n / t32, "crops_per_s_f64": n / t64, "host_crops": k, "host_threads": threads, "host_crops_per_s": k / t_host,
            "device_f64_over_host_f64": (n / t64) / (k / t_host), "device_f64_vs_host_rel_err": host_rel, "device_f64_vs_host_argmax_moved": host_moved,
            "device": torch.cuda.get_device_name(0)}
+    if h16 is not None:
+        row = dict(row, route=args.route, nonfinite_planes=nonfinite)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a") as f:
         f.write(json.dumps(row) + "\n")

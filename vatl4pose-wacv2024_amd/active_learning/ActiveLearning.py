@@ -55,6 +55,16 @@ def uncertainty_kind(name: str) -> str:
     raise ValueError("Uncertainty type is not supported")
 
 
+def precision_dtype(name):
+    """``cfg.VAL.PRECISION`` -> the storage type of the evaluation pass's forwards: None for "fp32" (the stream route of
+    ``hip_engine``: the default, and what every shipped yaml takes), torch.float16 / torch.bfloat16 for "fp16" / "bf16" (the
+    opt-in 16-bit route of ``hip_engine_h16``).  Fine-tuning and ``model(x)`` are fp32 whatever this says."""
+    table = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}
+    if not isinstance(name, str) or name not in table:
+        raise ValueError(f"VAL.PRECISION must be one of {sorted(table)}, got {name!r}")
+    return table[name]
+
+
 def _collective(fn):
     """Public entry points run on every rank in lock-step.  On the driver process that owns worker processes, the outermost
     call is announced to them first (active_learning/worker.py); under torchrun every rank calls the method itself."""
@@ -101,6 +111,8 @@ class ActiveLearning:
         self.need_embedding = self.representativeness not in ("None", "Random") or self.filter not in ("None", "Random")
         self.w_unc = float(cfg.VAL.get("W_UNC", 1.0))
         self.unc_lambda = float(cfg.VAL.get("UNC_LAMBDA", 1.0))
+        self.precision = cfg.VAL.get("PRECISION", "fp32")             # of the evaluation pass's forwards only (_heatmaps)
+        self.precision_dtype = precision_dtype(self.precision)
         self.finish_margin = 0.05
         # one process per GPU: join the torchrun group, or (plain single process, opt.num_gpu > 1) start the worker ranks
         self._depth = 0
@@ -252,18 +264,27 @@ class ActiveLearning:
         m = self.model
         x = inps[:, 0].to(self.device, non_blocking=True)
         from alphapose.models import hip_engine
+        dt = self.precision_dtype
+        if dt is not None:                            # cfg.VAL.PRECISION = fp16 / bf16: the same three calls on the 16-bit route
+            from alphapose.models import hip_engine_h16
 
         def heatmaps(t):
             # the stream entry point, not `m(t)`: a crop's bits must not depend on the size of the loader batch or of the shard
             # it arrives in (a short last batch would otherwise take the small-batch split-K route of the module call)
             t = t.to(self.device)
-            return hip_engine.forward_into(m, t, torch.empty((t.shape[0], self.cfg.DATA_PRESET.NUM_JOINTS, *self.hm_size), device=self.device))
+            buf = torch.empty((t.shape[0], self.cfg.DATA_PRESET.NUM_JOINTS, *self.hm_size), device=self.device)
+            return hip_engine.forward_into(m, t, buf) if dt is None else hip_engine_h16.forward_h16(m, t, buf, dtype=dt)
         with torch.no_grad():
             cur = out if out is not None else torch.empty((x.shape[0], self.cfg.DATA_PRESET.NUM_JOINTS, *self.hm_size), device=self.device)
             if emb_out is not None:                   # heat-maps and get_embedding from one trunk pass
-                hip_engine.forward_with_embedding(m, x, cur, emb_out)
-            else:
+                if dt is None:
+                    hip_engine.forward_with_embedding(m, x, cur, emb_out)
+                else:
+                    hip_engine_h16.forward_with_embedding_h16(m, x, cur, emb_out, dtype=dt)
+            elif dt is None:
                 hip_engine.forward_into(m, x, cur)
+            else:
+                hip_engine_h16.forward_h16(m, x, cur, dtype=dt)
             if not self.get_prenext or self.dedup:
                 return cur, None, None
             return cur, heatmaps(inps[:, 1]), heatmaps(inps[:, 2])
@@ -412,6 +433,8 @@ class ActiveLearning:
             self.flush_records()                                   # a user evaluator may read predicted_kpt.json / GT_kpt.json of THIS round
         res = evaluate(kp_all, self) if evaluate else (dict(tp["res"], mOKS=fallback["mOKS"]) if tp.get("res") else fallback)
         res_ann = res if (evaluate or not tp.get("res_ann")) else dict(tp["res_ann"], mOKS=fallback["mOKS"])
+        if self.precision_dtype is not None:                       # a 16-bit evaluation pass says so in its round's entry; fp32 entries are as they always were
+            res, res_ann = (dict(r, precision=self.precision) if isinstance(r, dict) else r for r in (res, res_ann))
         self.percentage.append(len(self.labeled_id) / n * 100)
         self.performance.append(res)
         self.performance_ann.append(res_ann)

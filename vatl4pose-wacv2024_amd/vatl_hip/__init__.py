@@ -205,6 +205,17 @@ SIGNATURES = {
     "vatl_pixelshuffle2_fwd_f64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "vatl_se_scale_add_relu_f64": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "vatl_fuse_upsample_add_f64": (_i, [_p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_pack_conv_weight_h16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_pack_deconv4x4s2_weight_h16": (_i, [_p, _p, _i, _i, _i, _p]),
+    "vatl_conv2d_fwd_h16": (_i, [_p] * 6 + [_i] * 12 + [_p]),
+    "vatl_deconv4x4s2_fwd_h16": (_i, [_p] * 5 + [_i] * 7 + [_p]),
+    "vatl_nchw_to_nhwc_h16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_nhwc_to_nchw_h16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_maxpool3x3s2_fwd_h16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_gap_fwd_h16": (_i, [_p, _p, _i, _i, _i, _i, _p]),
+    "vatl_pixelshuffle2_fwd_h16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_se_scale_add_relu_h16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "vatl_fuse_upsample_add_h16": (_i, [_p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib = None
@@ -2399,4 +2410,152 @@ def fuse_upsample_add_f64(base, ups, relu: bool):
     a = list(ups) + [(None, 0)] * (3 - len(ups))
     _check(lib().vatl_fuse_upsample_add_f64(_f64(base), _f64(a[0][0]), a[0][1], _f64(a[1][0]), a[1][1], _f64(a[2][0]), a[2][1], _f64(y),
                                             n, h, w, c, int(relu), _stream()), "vatl_fuse_upsample_add_f64")
+    return y
+
+
+# ----------------------------------------------------------------------------
+# 16-bit inference route (csrc/conv_h16.hip, csrc/glue_h16.hip): NHWC float16 / bfloat16 tensors, channels in multiples of 8
+# ----------------------------------------------------------------------------
+
+H16_DTYPES = {torch.float16: 0, torch.bfloat16: 1}          # the `dtype` argument of every vatl_*_h16 entry point
+
+
+def _h16_code(dtype) -> int:
+    if dtype not in H16_DTYPES:
+        raise VatlError(f"the 16-bit route serves torch.float16 and torch.bfloat16, got {dtype}")
+    return H16_DTYPES[dtype]
+
+
+def _new_like(shape, like, dtype=None):
+    return torch.empty(shape, device=like.device, dtype=dtype or like.dtype)
+
+
+def pack_conv_weight_h16(w: torch.Tensor, dtype) -> torch.Tensor:
+    """(Cout,Cin,R,S) fp32 -> [Cout][R][S][Cin8] of ``dtype``, Cin8 = Cin rounded up to 8 with zeros."""
+    code = _h16_code(dtype)
+    cout, cin, r, s = w.shape
+    out = _new_like((cout, r, s, (cin + 7) // 8 * 8), w, dtype)
+    _check(lib().vatl_pack_conv_weight_h16(_ptr(w.contiguous()), _ptr(out, dtype), cout, cin, r, s, code, _stream()), "vatl_pack_conv_weight_h16")
+    return out
+
+
+def pack_deconv_weight_h16(w: torch.Tensor, dtype) -> torch.Tensor:
+    """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) fp32 -> four 2x2 phase filters [4][Cout][2][2][Cin8] of ``dtype``."""
+    code = _h16_code(dtype)
+    cin, cout, kh, kw = w.shape
+    if (kh, kw) != (4, 4):
+        raise VatlError(f"pack_deconv_weight_h16: a 4x4 filter is needed, got {kh}x{kw}")
+    out = _new_like((4, cout, 2, 2, (cin + 7) // 8 * 8), w, dtype)
+    _check(lib().vatl_pack_deconv4x4s2_weight_h16(_ptr(w.contiguous()), _ptr(out, dtype), cin, cout, code, _stream()), "vatl_pack_deconv4x4s2_weight_h16")
+    return out
+
+
+def conv2d_fwd_h16(x, w_packed, scale, bias, stride: int, pad: int, relu: bool, residual=None, out_f32_nchw: bool = False, out=None):
+    """x (N,H,W,Cin) fp16 / bf16, w_packed from pack_conv_weight_h16 -> (N,Ho,Wo,Cout) of x's dtype, or fp32 (N,Cout,Ho,Wo).
+    scale / bias fp32 or None; residual (N,Ho,Wo,Cout) of x's dtype."""
+    t = x.dtype
+    code = _h16_code(t)
+    n, h, w, cin = x.shape
+    cout, r, s, cin_w = w_packed.shape
+    if cin_w != cin:
+        raise VatlError(f"conv2d_fwd_h16: input has {cin} channels, the filter {cin_w}")
+    ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+    shape = (n, cout, ho, wo) if out_f32_nchw else (n, ho, wo, cout)
+    odt = torch.float32 if out_f32_nchw else t
+    if out is None:
+        out = _new_like(shape, x, odt)
+    elif tuple(out.shape) != shape:
+        raise VatlError(f"conv2d_fwd_h16: out has shape {tuple(out.shape)}, expected {shape}")
+    if residual is not None and tuple(residual.shape) != (n, ho, wo, cout):
+        raise VatlError(f"conv2d_fwd_h16: residual has shape {tuple(residual.shape)}, expected {(n, ho, wo, cout)}")
+    _check(lib().vatl_conv2d_fwd_h16(_ptr(x, t), _ptr(w_packed, t), _ptr(scale), _ptr(bias), _ptr(residual, t), _ptr(out, odt), n, h, w, cin, cout, r, s,
+                                     stride, pad, int(relu), int(out_f32_nchw), code, _stream()), "vatl_conv2d_fwd_h16")
+    return out
+
+
+def deconv4x4s2_fwd_h16(x, w_packed, scale, bias, relu: bool):
+    t = x.dtype
+    code = _h16_code(t)
+    n, h, w, cin = x.shape
+    cout = w_packed.shape[1]
+    if w_packed.shape[-1] != cin:
+        raise VatlError(f"deconv4x4s2_fwd_h16: input has {cin} channels, the filter {w_packed.shape[-1]}")
+    y = _new_like((n, 2 * h, 2 * w, cout), x)
+    _check(lib().vatl_deconv4x4s2_fwd_h16(_ptr(x, t), _ptr(w_packed, t), _ptr(scale), _ptr(bias), _ptr(y, t), n, h, w, cin, cout, int(relu), code, _stream()),
+           "vatl_deconv4x4s2_fwd_h16")
+    return y
+
+
+def nchw_to_nhwc_h16(x: torch.Tensor, dtype) -> torch.Tensor:
+    """(N,C,H,W) fp32 -> (N,H,W,C8) of ``dtype``: rounded to nearest even, channels C .. C8-1 exact zeros."""
+    code = _h16_code(dtype)
+    n, c, h, w = x.shape
+    y = _new_like((n, h, w, (c + 7) // 8 * 8), x, dtype)
+    _check(lib().vatl_nchw_to_nhwc_h16(_ptr(x), _ptr(y, dtype), n, c, h, w, code, _stream()), "vatl_nchw_to_nhwc_h16")
+    return y
+
+
+def nhwc_to_nchw_h16(x: torch.Tensor) -> torch.Tensor:
+    """(N,H,W,C) fp16 / bf16 -> (N,C,H,W) fp32 (exact)."""
+    code = _h16_code(x.dtype)
+    n, h, w, c = x.shape
+    y = _new_like((n, c, h, w), x, torch.float32)
+    _check(lib().vatl_nhwc_to_nchw_h16(_ptr(x, x.dtype), _ptr(y), n, c, h, w, code, _stream()), "vatl_nhwc_to_nchw_h16")
+    return y
+
+
+def maxpool3x3s2_fwd_h16(x):
+    code = _h16_code(x.dtype)
+    n, h, w, c = x.shape
+    y = _new_like((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), x)
+    _check(lib().vatl_maxpool3x3s2_fwd_h16(_ptr(x, x.dtype), _ptr(y, x.dtype), n, h, w, c, code, _stream()), "vatl_maxpool3x3s2_fwd_h16")
+    return y
+
+
+def gap_fwd_h16(x, out=None):
+    """(N,H,W,C) fp16 / bf16 -> (N,C) fp32: pixels summed in fp32 in order."""
+    code = _h16_code(x.dtype)
+    n, h, w, c = x.shape
+    if out is None:
+        out = _new_like((n, c), x, torch.float32)
+    elif tuple(out.shape) != (n, c):
+        raise VatlError(f"gap_fwd_h16: out has shape {tuple(out.shape)}, expected {(n, c)}")
+    _check(lib().vatl_gap_fwd_h16(_ptr(x, x.dtype), _ptr(out), n, h * w, c, code, _stream()), "vatl_gap_fwd_h16")
+    return out
+
+
+def pixelshuffle2_fwd_h16(x):
+    code = _h16_code(x.dtype)
+    n, h, w, c = x.shape
+    y = _new_like((n, 2 * h, 2 * w, c // 4), x)
+    _check(lib().vatl_pixelshuffle2_fwd_h16(_ptr(x, x.dtype), _ptr(y, x.dtype), n, h, w, c, code, _stream()), "vatl_pixelshuffle2_fwd_h16")
+    return y
+
+
+def se_scale_add_relu_h16(x, gate, residual):
+    """y = relu(x * sigmoid(gate) + residual): x, residual (N,H,W,C) fp16 / bf16, gate (N,C) fp32."""
+    code = _h16_code(x.dtype)
+    n, h, w, c = x.shape
+    if tuple(gate.shape) != (n, c) or residual.shape != x.shape:
+        raise VatlError("se_scale_add_relu_h16: gate must be (N,C) and the residual shaped like x")
+    y = torch.empty_like(x)
+    _check(lib().vatl_se_scale_add_relu_h16(_ptr(x, x.dtype), _ptr(gate), _ptr(residual, x.dtype), _ptr(y, x.dtype), n, h * w, c, code, _stream()),
+           "vatl_se_scale_add_relu_h16")
+    return y
+
+
+def fuse_upsample_add_h16(base, ups, relu: bool):
+    """base (N,H,W,C); ups = [(z, shift)] with z (N,H>>shift,W>>shift,C), at most 3, added in fp32 in list order."""
+    t = base.dtype
+    code = _h16_code(t)
+    n, h, w, c = base.shape
+    if len(ups) > 3:
+        raise VatlError("fuse_upsample_add_h16: at most three up-sampled sources")
+    for z, sh in ups:
+        if tuple(z.shape) != (n, h >> sh, w >> sh, c):
+            raise VatlError(f"fuse_upsample_add_h16: source {tuple(z.shape)} does not match {tuple(base.shape)} >> {sh}")
+    y = torch.empty_like(base)
+    a = list(ups) + [(None, 0)] * (3 - len(ups))
+    _check(lib().vatl_fuse_upsample_add_h16(_ptr(base, t), _ptr(a[0][0], t), a[0][1], _ptr(a[1][0], t), a[1][1], _ptr(a[2][0], t), a[2][1], _ptr(y, t),
+                                            n, h, w, c, int(relu), code, _stream()), "vatl_fuse_upsample_add_h16")
     return y
