@@ -52,7 +52,7 @@ int vatl_flop_meter_end(double* direct_flops, double* winograd_flops, int64_t* d
 #define VATL_ROUTE_NAMES "igemm,igemm_bnbwd,igemm_dma,persistent_1x1,streamk,rows_1x1,bottleneck_chain,stem_pool,halo_3x3," \
                          "winograd,winograd_2h,winograd_bnbwd,winograd_persist,winograd_c32,wgrad,winograd_wgrad,winograd_wgrad_2h," \
                          "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43,winograd_s2_43,stem_pool_w1d," \
-                         "chain_proj,chain_step"
+                         "chain_proj,chain_step,gemm1x1_bf16x6"
 int vatl_flop_meter_routes(int64_t* counts, int n);
 
 /* ------------------------------------------------------------------------ *
@@ -886,6 +886,27 @@ int vatl_pack_winograd_s2_43_weight(const float* w, float* u, int Cout, int Cin,
 int vatl_conv3x3s2_winograd43_supported(int N, int H, int W, int Cin, int Cout);
 int vatl_conv3x3s2_winograd43_fwd(const float* x, const float* u, const float* scale, const float* bias, float* y, int N, int H, int W,
                                   int Cin, int Cout, int relu, void* stream);
+/* Long-K 1x1 / stride-1 layers of the inference plans with fp32 operands on the 16-bit matrix pipe (csrc/gemm1x1_bf16x6.hip, inference only): every
+ * float is cut exactly into three bf16 pieces (csrc/split16.h) and a product a * w becomes the six piece products a_i w_j with i + j <= 2, each exact
+ * in the fp32 accumulator; a0 w0 is summed in one accumulator set and the five small products in a second one, added once in front of the epilogue.
+ * Results agree with the fp32 kernels to fp32 rounding (not the same bits); a crop's bits do not depend on its batch position.  An infinity in x or w
+ * makes the outputs that read it NaN (inf - inf in the split).
+ * _fwd: x (N,H,W,Cin) NHWC -> y (N,H,W,Cout) NHWC, y = relu?(scale * (x W^T) + bias + residual) (scale / bias / residual may be null); stride is the
+ * layer's stride and must be 1.  _dual_fwd: the conv3 + projection form of vatl_conv1x1_dual_fwd over K = C1 + C2 (a, then x sampled with stride2),
+ * bias may be null, residual must be null.  u: vatl_gemm1x1_bf16x6_weight_floats(N, K) = 3 N K / 2 floats (6 bytes per weight: three bf16 planes in
+ * the order the kernel's B fragments are read) from vatl_pack_gemm1x1_bf16x6_weight, w = the [N][K] fp32 filter (for the dual form the [Cout][C1 + C2]
+ * rows of vatl_pack_conv1x1_dual_weight), N % 128 == 0, K % 64 == 0.
+ * _supported(M, K, K1, N): 1 for M = N * H * W rows, N (= Cout) % 128 == 0, K % 64 == 0, K >= 512 (K1 = 0: plain form) or K1 = C1 >= 64, K1 % 64 == 0,
+ * K - K1 >= 64, K >= 384 (dual form), and tensors within 32-bit byte offsets ((M + 128) * N < 2^30, M * K < 2^30); else 0, and the _fwd calls fail on
+ * those without a launch.  The flop meter books the launch in its DIRECT class with 6/16 of 2 * Mpad * Npad * K (the fp32-pipe time that six bf16
+ * instructions occupy) and under the route gemm1x1_bf16x6: the call is made in place of vatl_conv2d_fwd / vatl_conv1x1_dual_fwd. */
+int64_t vatl_gemm1x1_bf16x6_weight_floats(int N, int K);
+int vatl_pack_gemm1x1_bf16x6_weight(const float* w, float* u, int N, int K, void* stream);
+int vatl_gemm1x1_bf16x6_supported(int64_t M, int K, int K1, int N);
+int vatl_gemm1x1_bf16x6_fwd(const float* x, const float* u, const float* scale, const float* bias, const float* residual, float* y,
+                            int N, int H, int W, int Cin, int Cout, int stride, int relu, void* stream);
+int vatl_gemm1x1_bf16x6_dual_fwd(const float* a, const float* x, const float* u, const float* bias, const float* residual, float* y,
+                                 int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int stride2, int Cout, int relu, void* stream);
 int64_t vatl_winograd_deconv_stats_row_blocks(int64_t N, int H, int W);
 int vatl_deconv4x4s2_winograd_fwd_stats(const float* x, const float* u, float* y, double* stats, int64_t* row_blocks_used, int N, int H, int W,
                                         int Cin, int Cout, void* stream);

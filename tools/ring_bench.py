@@ -7,7 +7,9 @@ VATL_HIP_LIB=.../libvatl_hip_ablation.so).
     python tools/ring_bench.py [--batch 1024] [--iters 10] [--reps 3]
 
 Prints one line per layer: us per launch (median of --reps timed loops of --iters back-to-back launches), TFLOP/s and the fraction of
-the 157.3 TFLOP/s fp32 MFMA peak.
+the 157.3 TFLOP/s fp32 MFMA peak; then, where the library has it, the same launch on the bf16x6 route (u_x6=, csrc/gemm1x1_bf16x6.hip) timed in the
+same run, the timed loops of the two alternating: us, speed-up over the fp32 kernel, and the fraction of the route's own MFMA floor, 6/16 of the
+fp32 one.  --hrnet adds the trunk shapes at the 384x288 input of the FastPose configs.
 """
 import argparse
 import os
@@ -24,21 +26,35 @@ PEAK = 157.3e12
 # name: (H, W, K, N, residual)
 PLAIN = {"l2.n.c1": (32, 24, 512, 128, False), "l3.0.c1": (32, 24, 512, 256, False), "l3.n.c1": (16, 12, 1024, 256, False),
          "l4.0.c1": (16, 12, 1024, 512, False), "l4.n.c1": (8, 6, 2048, 512, False), "l4.n.c3": (8, 6, 512, 2048, True)}
+# further plain shapes the bf16x6 shape rule admits (--hrnet): the same (K, N) pairs of a ResNet trunk at the 384x288 input of the FastPose configs (grids 48x36 / 24x18 / 12x9)
+OTHER = {"fp.l2.n.c1": (48, 36, 512, 128, False), "fp.l3.0.c1": (48, 36, 512, 256, False), "fp.l3.n.c1": (24, 18, 1024, 256, False),
+         "fp.l4.0.c1": (24, 18, 1024, 512, False), "fp.l4.n.c1": (12, 9, 2048, 512, False), "fp.l4.n.c3": (12, 9, 512, 2048, True)}
 # name: (Ho, Wo, C1, H2, W2, C2, N)  (projection stride 2)
 DUAL = {"l2.0.c3+p": (32, 24, 128, 64, 48, 256, 512), "l3.0.c3+p": (16, 12, 256, 32, 24, 512, 1024), "l4.0.c3+p": (8, 6, 512, 16, 12, 1024, 2048)}
 
 
-def timed(fn, iters, reps):
-    fn(); torch.cuda.synchronize()
-    ts = []
+def timed(fns, iters, reps):
+    """Median us per launch of each of `fns`, their timed loops alternating."""
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
     for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record(); b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3 / iters)
-    return sorted(ts)[len(ts) // 2]
+        for t, fn in zip(ts, fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record(); b.synchronize()
+            t.append(a.elapsed_time(b) * 1e3 / iters)
+    return [sorted(t)[len(t) // 2] for t in ts]
+
+
+def report(name, shape, fl, us):
+    line = f"{name:10s} {shape}  {us[0]:9.1f} us  {fl / us[0] / 1e6:6.1f} TFLOP/s  {fl / us[0] / 1e-6 / PEAK:5.3f} of peak"
+    if len(us) > 1:
+        line += f"   bf16x6 {us[1]:9.1f} us  {us[0] / us[1]:5.2f}x  {fl / us[1] / 1e-6 / PEAK:5.3f} of the fp32 floor, {fl * 6 / 16 / us[1] / 1e-6 / PEAK:5.3f} of the 6/16 floor"
+    print(line, flush=True)
 
 
 def main():
@@ -46,6 +62,7 @@ def main():
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--hrnet", action="store_true", help="also the trunk shapes at the 384x288 input of the FastPose configs (pass a smaller --batch: 1024 crops of 48x36x512 exceed the 2^30-element guard)")
     ap.add_argument("--ring", type=int, default=-1, help="vatl_tune_set(27, v) before timing (profiling library only; -1: leave the library default)")
     a = ap.parse_args()
     vh.lib()
@@ -53,17 +70,22 @@ def main():
         vh.tune_set(27, a.ring)
     n = a.batch
     g = torch.Generator(device="cuda"); g.manual_seed(0)
-    total = 0.0
-    for name, (h, w, k, cout, res) in PLAIN.items():
+    total = total6 = 0.0
+    x6 = hasattr(vh, "gemm1x1_bf16x6_supported")        # (an older library through VATL_HIP_LIB: the fp32 column alone)
+    plain = dict(PLAIN, **(OTHER if a.hrnet else {}))
+    for name, (h, w, k, cout, res) in plain.items():
         x = torch.randn((n, h, w, k), device="cuda", generator=g)
         wp = vh.pack_conv_weight(torch.randn((cout, k, 1, 1), device="cuda", generator=g) / k ** 0.5)
         sc, bi = torch.rand(cout, device="cuda", generator=g) + 0.5, torch.randn(cout, device="cuda", generator=g)
         rs = torch.randn((n, h, w, cout), device="cuda", generator=g) if res else None
         y = torch.empty((n, h, w, cout), device="cuda")
-        us = timed(lambda: vh.conv2d_fwd(x, wp, sc, bi, cout, 1, 1, 1, 0, True, residual=rs, out=y), a.iters, a.reps)
-        fl = 2.0 * n * h * w * k * cout
-        total += us
-        print(f"{name:10s} {n}x{h}x{w} {k:5d}->{cout:5d}  {us:9.1f} us  {fl / us / 1e6:6.1f} TFLOP/s  {fl / us / 1e-6 / PEAK:5.3f} of peak", flush=True)
+        fns = [lambda: vh.conv2d_fwd(x, wp, sc, bi, cout, 1, 1, 1, 0, True, residual=rs, out=y)]
+        if x6 and vh.gemm1x1_bf16x6_supported(n * h * w, k, 0, cout):
+            ux6 = vh.pack_gemm1x1_bf16x6_weight(wp)
+            fns.append(lambda: vh.conv2d_fwd(x, wp, sc, bi, cout, 1, 1, 1, 0, True, residual=rs, out=y, u_x6=ux6))
+        us = timed(fns, a.iters, a.reps)
+        total += us[0]; total6 += us[-1]
+        report(name, f"{n}x{h}x{w} {k:5d}->{cout:5d}", 2.0 * n * h * w * k * cout, us)
         del x, rs, y
     for name, (ho, wo, c1, h2, w2, c2, cout) in DUAL.items():
         x1 = torch.randn((n, ho, wo, c1), device="cuda", generator=g)
@@ -72,12 +94,15 @@ def main():
         wp, bias = vh.pack_conv1x1_dual_weight(torch.randn((cout, c1, 1, 1), device="cuda", generator=g) / c1 ** 0.5, ones, zeros,
                                                torch.randn((cout, c2, 1, 1), device="cuda", generator=g) / c2 ** 0.5, ones, zeros)
         y = torch.empty((n, ho, wo, cout), device="cuda")
-        us = timed(lambda: vh.conv1x1_dual_fwd(x1, x2, wp, bias, cout, 2, True, out=y), a.iters, a.reps)
-        fl = 2.0 * n * ho * wo * (c1 + c2) * cout
-        total += us
-        print(f"{name:10s} {n}x{ho}x{wo} {c1}+{c2}->{cout}  {us:9.1f} us  {fl / us / 1e6:6.1f} TFLOP/s  {fl / us / 1e-6 / PEAK:5.3f} of peak", flush=True)
+        fns = [lambda: vh.conv1x1_dual_fwd(x1, x2, wp, bias, cout, 2, True, out=y)]
+        if x6 and vh.gemm1x1_bf16x6_supported(n * ho * wo, c1 + c2, c1, cout):
+            ux6 = vh.pack_gemm1x1_bf16x6_weight(wp)
+            fns.append(lambda: vh.conv1x1_dual_fwd(x1, x2, wp, bias, cout, 2, True, out=y, u_x6=ux6))
+        us = timed(fns, a.iters, a.reps)
+        total += us[0]; total6 += us[-1]
+        report(name, f"{n}x{ho}x{wo} {c1}+{c2}->{cout}", 2.0 * n * ho * wo * (c1 + c2) * cout, us)
         del x1, x2, y
-    print(f"sum of one launch per shape: {total:.1f} us", flush=True)
+    print(f"sum of one launch per shape: {total:.1f} us" + (f"   with bf16x6 where admitted: {total6:.1f} us" if x6 else ""), flush=True)
 
 
 if __name__ == "__main__":

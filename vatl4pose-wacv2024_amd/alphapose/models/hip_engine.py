@@ -67,10 +67,18 @@ DECONV_43 = True
 # outputs against 108 of the direct sum).  Geometry-only choice like WINOGRAD; not taken with a residual, for NCHW output or in the small-batch module call.
 # False = the implicit GEMM (same values to fp32 rounding, not the same bits).
 S2_43 = True
+# 1x1 / stride 1 layers with K >= 512 (K a multiple of 64, N of 128: Bottleneck.conv1 of ResNet stages 2 - 4, conv3 of stage 4) and the conv3 + projection launches with
+# K >= 384 — the shapes of the LDS-DMA ring kernel — as SIX bf16 MFMAs per fp32 product (csrc/gemm1x1_bf16x6.hip): both operands are cut exactly into three bf16
+# pieces (csrc/split16.h), the products a_i w_j with i + j <= 2 are exact in the fp32 accumulator, a0 w0 and the five small products are summed in separate accumulator
+# sets.  6/16 of the fp32 matrix-pipe cycles.  Accuracy: 0.99x the normwise error of the fp32 route against float64 on SimplePose-R50 (tests/probes/bf16x6_accuracy.py),
+# each layer inside the 2e-5 bar; an infinity in the input turns into NaN.  The filter planes (6 bytes per weight) are packed on the first call that takes the route.
+# Geometry-only choice like WINOGRAD; not taken for NCHW output, in the small-batch module call or by the trainers.  False = the ring / tiled fp32 kernels (same values
+# to fp32 rounding, not the same bits).
+BF16X6 = True
 
 
 class _Conv:
-    __slots__ = ("w", "u", "u32", "u4", "us2", "wsrc", "wino", "c32", "f4", "s2", "scale", "bias", "cout", "r", "s", "stride", "pad")
+    __slots__ = ("w", "u", "u32", "u4", "us2", "ux6", "wsrc", "wino", "c32", "f4", "s2", "x6", "scale", "bias", "cout", "r", "s", "stride", "pad")
 
     def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d | None):
         assert conv.groups == 1 and conv.dilation == (1, 1)
@@ -88,8 +96,11 @@ class _Conv:
         self.f4 = self.wino and WINO_F4 and conv.in_channels >= 64 and conv.in_channels % 16 == 0 and self.cout % 64 == 0
         self.us2 = None
         self.s2 = WINOGRAD and S2_43 and (self.r, self.s, self.stride, self.pad) == (3, 3, 2, 1) and conv.in_channels % 16 == 0 and self.cout % 64 == 0
+        self.ux6 = None                                   # (packed from self.w, which for a 1x1 layer is the [N][K] filter itself)
+        self.x6 = (BF16X6 and (self.r, self.s, self.stride, self.pad) == (1, 1, 1, 0) and conv.in_channels >= 512 and conv.in_channels % 64 == 0
+                   and self.cout % 128 == 0)
         self.wsrc = conv.weight.detach() if self.wino or self.s2 else None
-        cb = conv.bias.detach() if conv.bias is not None else None
+        cb =conv.bias.detach() if conv.bias is not None else None
         if bn is not None:
             self.scale, self.bias = vh.bn_fold(_d(bn.weight), _d(bn.bias), bn.running_mean, bn.running_var, bn.eps, cb)
         elif cb is not None:
@@ -118,8 +129,13 @@ class _Conv:
             if self.us2 is None and vh.conv3x3s2_winograd43_supported(x.shape[0], x.shape[1], x.shape[2], x.shape[3], self.cout):
                 self.us2 = vh.pack_winograd_s2_43_weight(self.wsrc)
             us2 = self.us2
+        ux6 = None
+        if self.x6 and not out_nchw and not vh.latency_mode():                            # long-K 1x1: six bf16 MFMAs per product, inside conv2d_fwd
+            if self.ux6 is None and vh.gemm1x1_bf16x6_supported(x.shape[0] * x.shape[1] * x.shape[2], x.shape[3], 0, self.cout):
+                self.ux6 = vh.pack_gemm1x1_bf16x6_weight(self.w)
+            ux6 = self.ux6
         return vh.conv2d_fwd(x, self.w, self.scale, self.bias, self.cout, self.r, self.s, self.stride, self.pad, relu,
-                             residual=residual, out_nchw=out_nchw, out=out, u_s2=us2)
+                             residual=residual, out_nchw=out_nchw, out=out, u_s2=us2, u_x6=ux6)
 
 
 # Deformable conv2 of a DCN bottleneck (csrc/deform_conv.hip).  False = the column route: deform_columns + the 1x1 GEMM with bn2 + ReLU in its epilogue.
@@ -198,6 +214,7 @@ class _BottleneckPlan:
             w, b = vh.pack_conv1x1_dual_weight(blk.conv3.weight.detach(), self.c3.scale, self.c3.bias, blk.downsample[0].weight.detach(),
                                                self.proj.scale, self.proj.bias)
             self.dual = (w, b, self.proj.stride)
+        self.dual_x6 = None                                # bf16 planes of the dual filter (BF16X6), packed on the first call that takes the route
 
     def __call__(self, x, out=None, y1=None, nxt=None):
         y = y1 if y1 is not None else self.c1(x, relu=True)         # y1: conv1 + bn1 + relu already computed by the block before (chained launch)
@@ -213,7 +230,12 @@ class _BottleneckPlan:
                     return vh.conv1x1_rows_fwd(y, self.dual[0], None, self.dual[1], self.c3.cout, True, x2=x, out=out, next_conv1=nxt)
                 t = vh.conv1x1_rows_fwd(y, self.dual[0], None, self.dual[1], self.c3.cout, True, x2=x, out=out)
             else:
-                t = vh.conv1x1_dual_fwd(y, x, self.dual[0], self.dual[1], self.c3.cout, self.dual[2], True, out=out)
+                ux6 = None
+                if BF16X6 and not vh.latency_mode():
+                    if self.dual_x6 is None and vh.gemm1x1_bf16x6_supported(y.shape[0] * y.shape[1] * y.shape[2], y.shape[-1] + x.shape[-1], y.shape[-1], self.c3.cout):
+                        self.dual_x6 = vh.pack_gemm1x1_bf16x6_weight(self.dual[0])
+                    ux6 = self.dual_x6
+                t = vh.conv1x1_dual_fwd(y, x, self.dual[0], self.dual[1], self.c3.cout, self.dual[2], True, out=out, u_x6=ux6)
         else:
             skip = x if self.proj is None else self.proj(x, relu=False)
             t = self.c3(y, relu=True, residual=skip, out=out)       # relu(bn3(conv3) + skip)

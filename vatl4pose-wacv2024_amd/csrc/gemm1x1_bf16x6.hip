@@ -1,0 +1,360 @@
+// The bf16x6 GEMM for the long-K 1x1 layers of the inference plans: fp32 operands, each product as six bf16 MFMAs.  Kernel, filter pack,
+// launcher, the shape rule (vatl_gemm1x1_bf16x6_supported) and the C entry points.
+#include "conv_igemm.h"
+#include "split16.h"
+#include "tile_order.h"
+
+namespace vatl {
+
+// ---------------------------------------------------------------------------------------------------------
+// Y[M][N] = A[M][K] W[N][K]^T for the shapes of gemm1x1_ring_kernel (stride-1 1x1 layers with K >= 512 and the dual-source conv3 +
+// projection form, whole 128-wide N tiles, NHWC output) on the 16-bit matrix pipe with fp32 results.  split16.h cuts a float exactly
+// into three bf16 pieces, a = a0 + a1 + a2, w = w0 + w1 + w2, and the product becomes the six piece products a_i w_j with i + j <= 2
+// (the three dropped ones are below 2^-24 of the product).  Each piece product is exact in the fp32 accumulator.  Six
+// v_mfma_f32_32x32x16_bf16 take 6/16 of the matrix-pipe cycles of the sixteen v_mfma_f32_32x32x2_f32 they replace.
+//  * TWO accumulator sets: a0 w0 goes into one, the five small products (a0 w1, a1 w0, a1 w1, a0 w2, a2 w0, in this order, every
+//    16-k stage) into the other, and the two are added once, in front of the epilogue.  With one set the small products are rounded
+//    at the magnitude of the large sum and the network error rises to 1.06x fp32's; with two it is 0.99x (tests/probes/bf16x6_accuracy.py).
+//  * the A operand stays fp32 in HBM and in LDS: the ring kernel's LDS-DMA requests and swizzle (rows of 64 bytes, chunk c of tile row r
+//    at position c ^ ((r >> 2) & 3), applied on the source side).  A lane reads the eight k of its row that the MFMA wants from it
+//    (chunks 2h and 2h + 1: k = 8h .. 8h + 7 of the stage, h = lane >> 5) with two ds_read_b128 — conflict-free like the ring's
+//    reads, every service group shares h — and splits them in registers: per element two ANDs and two exact subtractions, per pair
+//    three packs.
+//  * the filter is split once, by vatl_pack_gemm1x1_bf16x6_weight, into three bf16 planes in the order the B fragments are read: per
+//    (n-tile, stage) 12 KB = [plane 3][column block 4][lane 64] x 16 bytes, lane l of column block jb holding piece `plane` of
+//    W[128 n_tile + 32 jb + (l & 31)][16 stage + 8 (l >> 5) + 0 .. 7].  The DMA copies it linearly, a fragment is one ds_read_b128 at
+//    lane * 16: conflict-free, no swizzle.
+//  * a stage is 16 k = 8 KB of A + 12 KB of B, a ring of four is 80 KB per block, two blocks per CU: the vector work of one block's
+//    wave (the split) runs under the MFMAs of the other block's wave on the same SIMD.  Per stage and wave 24 MFMAs, five DMA
+//    requests, one counted s_waitcnt, one barrier.
+//  * the residual is read in the write-out, after the two accumulator sets are added (the registers the ring kernel keeps it in hold
+//    the second set here).
+// Arithmetic per output row depends on that row's inputs and the filter only: the same bits alone and in any batch position.
+// Tail rows read row M-1; their stores lie past the descriptor and are dropped.  No atomics, no split-K.
+// Dual source: stages 0 .. 2 k1 - 1 read x, the rest x2 at the row's strided pixel (the ring kernel's rules).
+// ---------------------------------------------------------------------------------------------------------
+constexpr int X6_BK = 16;                             // k per stage
+constexpr int X6_NS = 4;                              // stages in the ring
+constexpr int X6_A_FLOATS = 128 * X6_BK;              // 8 KB: 128 A rows of 64 bytes
+constexpr int X6_B_BYTES = 3 * 128 * X6_BK * 2;       // 12 KB: three bf16 planes of 128 filter rows
+constexpr int X6_STAGE = X6_A_FLOATS + X6_B_BYTES / 4;   // floats per stage
+constexpr int X6_BYTES = X6_NS * X6_STAGE * (int)sizeof(float);
+
+typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
+
+template <int N>
+__device__ __forceinline__ void x6_wait_vm() {       // s_waitcnt vmcnt(N), N a compile-time count of this wave's younger DMA requests
+    static_assert(N == 0 || N == 5 || N == 10, "add the count here");
+    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+}
+
+__device__ __forceinline__ f32x16 x6_mfma(u32x4 a, u32x4 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x6_bf16x8, a), __builtin_bit_cast(x6_bf16x8, b), c, 0, 0, 0);
+}
+
+template <bool DUAL, bool RES>
+__device__ __forceinline__ void gemm1x1_bf16x6_body(const ConvParams& p, float* smem) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;          // 2 x 2 waves of 64 x 64
+
+    const int t = xcd_contiguous_index(blockIdx.x, gridDim.x);   // tile order of the ring kernel: n-tile fastest inside an XCD's run
+    const int m_tile = t / p.n_tiles, n_tile = t - m_tile * p.n_tiles;
+    const int m0 = m_tile * 128, n0 = n_tile * 128;
+
+    const __amdgpu_buffer_rsrc_t xr = buf_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t wr = buf_rsrc(p.w, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t xr2 = buf_rsrc(DUAL ? p.x2 : p.x, DUAL ? p.x2_bytes : p.x_bytes);
+
+    const int S = p.ktiles * 2;                       // stages (a multiple of 4: x6_shape_ok)
+    const int S1 = DUAL ? p.k1 * 2 : S;               // stages that read x
+
+    // ---- loader.  A: DMA instruction u (0, 1) of wave w fills tile rows (4u + w) * 16 .. + 15; lane -> (row lane >> 2, position lane & 3),
+    // which receives the row's chunk (lane & 3) ^ ((row >> 2) & 3).  B: instruction u (0 .. 2) of wave w copies 1 KB piece 4u + w of the
+    // stage's 12 KB, lane-linear.
+    const int lchk = (lane & 3) ^ ((lane >> 4) & 3);
+    unsigned aoff[2], aoff2[2], boff[3];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int row = (4 * u + wave) * 16 + (lane >> 2);
+        const int m = min(m0 + row, p.M - 1);
+        aoff[u] = (unsigned)m * (unsigned)(p.Cin * 4) + (unsigned)lchk * 16u;
+        aoff2[u] = 0;
+        if (DUAL) {
+            const int b = fdiv(m, p.d_HoWo);
+            const int rem = m - b * p.Ho * p.Wo;
+            const int oy = fdiv(rem, p.d_Wo);
+            const int ox = rem - oy * p.Wo;
+            aoff2[u] = (unsigned)((b * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2) * (unsigned)(p.C2 * 4) + (unsigned)lchk * 16u;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 3; ++u) boff[u] = (unsigned)(n_tile * S) * (unsigned)X6_B_BYTES + (unsigned)(4 * u + wave) * 1024u + (unsigned)lane * 16u;
+    auto issue = [&](auto src, int buf, int s) {
+        float* st = smem + buf * X6_STAGE;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            lds_void* da = (lds_void*)(st + (4 * u + wave) * 256);
+            if constexpr (DUAL && decltype(src)::value == 1) __builtin_amdgcn_raw_ptr_buffer_load_lds(xr2, da, 16, aoff2[u], (unsigned)(s - S1) * 64u, 0, 0);
+            else                                             __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, da, 16, aoff[u], (unsigned)s * 64u, 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void*)(st + X6_A_FLOATS + (4 * u + wave) * 256), 16, boff[u], (unsigned)s * (unsigned)X6_B_BYTES, 0, 0);
+    };
+
+    // ---- fragments.  A: row frow (+ 32 i) of the wave's 64, logical chunks 2h and 2h + 1 at positions (2h + c) ^ ((frow >> 2) & 3).
+    // B: plane pl, column block 2 wn + j: 16 bytes at ((4 pl + 2 wn + j) * 64 + lane) * 16.
+    const int frow = lane & 31, h = lane >> 5;
+    const int fsw = (frow >> 2) & 3;
+    const float* Ard[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) Ard[c] = smem + (wm * 64 + frow) * X6_BK + (((2 * h + c) ^ fsw) << 2);
+    const float* Brd = smem + X6_A_FLOATS + (2 * wn * 64 + lane) * 4;
+
+    f32x16 acc[2][2], sml[2][2];                      // a0 w0 | the five small products
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; sml[i][j][e] = 0.f; }
+
+    // One stage.  KIND 0: steady state (stages s+1, s+2 in flight behind s: vmcnt(10)), then the request of stage s+3 into the slot every
+    // wave finished reading before this barrier (stage s-1's); 1: s = S-3, nothing left to request; 2: s = S-2 (stage S-1 younger);
+    // 3: s = S-1.  VMEM operations retire in order, so each count waits for this wave's pieces of stage s exactly.
+    auto stage = [&](auto slot, auto kind, auto src, int s) {
+        constexpr int B = decltype(slot)::value, KIND = decltype(kind)::value;
+        if constexpr (KIND <= 1) x6_wait_vm<10>();
+        else if constexpr (KIND == 2) x6_wait_vm<5>();
+        else x6_wait_vm<0>();
+        __builtin_amdgcn_s_barrier();                 // every wave's pieces of stage s have landed; every wave is done reading slot (s - 1) % 4
+        asm volatile("" ::: "memory");
+        f32x4 af[2][2];
+        u32x4 bw[3][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) af[i][c] = *reinterpret_cast<const f32x4*>(Ard[c] + B * X6_STAGE + i * 32 * X6_BK);
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bw[pl][j] = *reinterpret_cast<const u32x4*>(Brd + B * X6_STAGE + (4 * pl + j) * 256);
+        if constexpr (KIND == 0) issue(src, (B + 3) & 3, s + 3);
+        // the split (split16.h): fragment dword d = k pair (2d, 2d + 1) of the lane's eight
+        u32x4 a0[2], a1[2], a2[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                const split16::Pieces e = split16::split3(af[i][d >> 1][(2 * d) & 3]), o = split16::split3(af[i][d >> 1][(2 * d + 1) & 3]);
+                a0[i][d] = split16::pack_pair(e.hi, o.hi);
+                a1[i][d] = split16::pack_pair(e.mid, o.mid);
+                a2[i][d] = split16::pack_pair(e.lo, o.lo);
+            }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = x6_mfma(a0[i], bw[0][j], acc[i][j]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a0[i], bw[1][j], sml[i][j]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a1[i], bw[0][j], sml[i][j]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a1[i], bw[1][j], sml[i][j]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a0[i], bw[2][j], sml[i][j]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a2[i], bw[0][j], sml[i][j]);
+        __builtin_amdgcn_sched_barrier(0);            // a stage's reads and requests stay between its barrier and the next
+    };
+    using C0 = std::integral_constant<int, 0>;
+    using C1 = std::integral_constant<int, 1>;
+    using C2 = std::integral_constant<int, 2>;
+    using C3 = std::integral_constant<int, 3>;
+
+    using X2 = std::integral_constant<int, DUAL ? 1 : 0>;   // source of the stages past S1 (x itself for the plain form)
+    auto group = [&](auto src, int s) {               // four steady-state stages whose requests all read one source
+        stage(C0{}, C0{}, src, s);
+        stage(C1{}, C0{}, src, s + 1);
+        stage(C2{}, C0{}, src, s + 2);
+        stage(C3{}, C0{}, src, s + 3);
+    };
+
+    issue(C0{}, 0, 0);                                // (S1 >= 4: the first three stages read x)
+    issue(C0{}, 1, 1);
+    issue(C0{}, 2, 2);
+    int s = 0;
+    if constexpr (DUAL) {
+        for (; s < S1 - 4; s += 4) group(C0{}, s);
+        stage(C0{}, C0{}, C0{}, s);                   // the group whose requests cross from x to x2 (S1 - 1 | S1 .. S1 + 2)
+        stage(C1{}, C0{}, X2{}, s + 1);
+        stage(C2{}, C0{}, X2{}, s + 2);
+        stage(C3{}, C0{}, X2{}, s + 3);
+        s += 4;
+    }
+    for (; s < S - 4; s += 4) group(X2{}, s);
+    stage(C0{}, C0{}, X2{}, s);                       // the last group: requests the last stage
+    stage(C1{}, C1{}, X2{}, s + 1);
+    stage(C2{}, C2{}, X2{}, s + 2);
+    stage(C3{}, C3{}, X2{}, s + 3);
+
+    // ---- write-out from the accumulator layout (the ring kernel's): element e of tile (i, j) is row 32 i + (e & 3) + 8 (e >> 2) + 4 h,
+    // channel 64 wn + 32 j + frow; rows >= M lie past the descriptor (loads read 0, stores are dropped).  Same expression as conv_epilogue.
+    const unsigned rowb = (unsigned)p.Cout * 4u;
+    const unsigned ylane = (unsigned)(m0 + wm * 64 + 4 * h) * rowb + (unsigned)(n0 + wn * 64 + frow) * 4u;
+    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(RES ? p.res : p.y, RES ? p.y_bytes : 0u);
+    float sc[2], bi[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int n = n0 + wn * 64 + j * 32 + frow;
+        sc[j] = p.scale ? p.scale[n] : 1.f;
+        bi[j] = p.bias ? p.bias[n] : 0.f;
+    }
+    const float lo = p.relu ? 0.f : -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float rs[2][16];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                rs[j][e] = RES ? buf_load1(rr, ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u) : 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float a = acc[i][j][e] + sml[i][j][e];
+                const float v = fmaxf(a * sc[j] + bi[j] + rs[j][e], lo);
+                buf_store1(yr, ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u, v);
+            }
+    }
+}
+
+template <bool DUAL, bool RES>
+__global__ __launch_bounds__(256, 2) void gemm1x1_bf16x6_kernel(ConvParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    gemm1x1_bf16x6_body<DUAL, RES>(p, smem);
+}
+
+// ---- filter pack: one thread per 16-byte fragment piece (see the layout above)
+__global__ __launch_bounds__(256) void gemm1x1_bf16x6_pack_kernel(const float* __restrict__ w, u32x4* __restrict__ u, int K, long long units) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= units) return;
+    const int S = K / X6_BK;
+    const int l = (int)(idx & 63), jb = (int)((idx >> 6) & 3);
+    const long long rest = idx >> 8;
+    const int pl = (int)(rest % 3);
+    const long long ts = rest / 3;                    // n_tile * S + stage
+    const int st = (int)(ts % S), n_tile = (int)(ts / S);
+    const float* src = w + (long long)(n_tile * 128 + jb * 32 + (l & 31)) * K + st * X6_BK + 8 * (l >> 5);
+    float pc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const split16::Pieces q = split16::split3(src[j]);
+        pc[j] = pl == 0 ? q.hi : (pl == 1 ? q.mid : q.lo);
+    }
+    u32x4 o;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[d] = split16::pack_pair(pc[2 * d], pc[2 * d + 1]);
+    u[idx] = o;
+}
+
+// The shapes the kernel serves — the ring kernel's, by geometry alone: whole 128-wide N tiles, K a multiple of 64 and at least 512 (plain
+// form; the stage count a multiple of 4), or the dual form with the x / x2 boundary K1 on a multiple of 64, at least 64 channels on
+// either side and K >= 384; (M + 128) * N < 2^30 so that the byte offsets of the tail tile's dropped rows do not wrap; the operands
+// within 32-bit byte offsets.
+static bool x6_shape_ok(long long M, int K, int K1, int N) {
+    if (M < 1 || N < 128 || (N % 128) || K < 1 || (K % 64)) return false;
+    if (K1 == 0 ? K < 512 : (K1 < 64 || (K1 % 64) || K - K1 < 64 || K < 384)) return false;
+    if ((M + 128) * N >= (1LL << 30) || M * (K1 ? K1 : K) >= (1LL << 30) || 6LL * N * K >= (1LL << 31)) return false;
+    return true;
+}
+
+template <bool DUAL, bool RES>
+static int launch_x6_impl(const ConvParams& p, hipStream_t st) {
+    auto kern = gemm1x1_bf16x6_kernel<DUAL, RES>;
+    static std::atomic<unsigned> configured{0};
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), X6_BYTES, configured, "gemm1x1_bf16x6")) return rc;
+    ConvParams q = p;
+    q.n_tiles = p.Cout / 128;
+    q.m_tiles = cdiv(p.M, 128);
+    q.splits = 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(q.m_tiles * q.n_tiles)), dim3(256), X6_BYTES, st, q);
+    // six bf16 MFMAs in place of sixteen fp32-MFMA equivalents: the fp32-pipe time the launch occupies
+    meter_add(0, (6.0 / 16.0) * 2.0 * ((double)q.m_tiles * 128) * ((double)q.n_tiles * 128) * ((double)q.ktiles * BK));
+    meter_route(kRouteGemm1x1Bf16x6);
+    return check_launch("gemm1x1_bf16x6");
+}
+
+}  // namespace vatl
+
+using namespace vatl;
+
+extern "C" int64_t vatl_gemm1x1_bf16x6_weight_floats(int N, int K) { return 3LL * N * K / 2; }
+
+extern "C" int vatl_pack_gemm1x1_bf16x6_weight(const float* w, float* u, int N, int K, void* stream) {
+    if (!w || !u) return fail(VATL_EINVAL, "pack_gemm1x1_bf16x6_weight: null pointer");
+    if (N < 128 || (N % 128) || K < 64 || (K % 64) || 6LL * N * K >= (1LL << 31))
+        return fail(VATL_EINVAL, "pack_gemm1x1_bf16x6_weight: N %d must be a multiple of 128, K %d of 64, 6 N K below 2^31 bytes", N, K);
+    const long long units = 6LL * N * K / 16;
+    hipLaunchKernelGGL(gemm1x1_bf16x6_pack_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, reinterpret_cast<u32x4*>(u), K, units);
+    return check_launch("gemm1x1_bf16x6_pack");
+}
+
+extern "C" int vatl_gemm1x1_bf16x6_supported(int64_t M, int K, int K1, int N) { return x6_shape_ok(M, K, K1, N) ? 1 : 0; }
+
+extern "C" int vatl_gemm1x1_bf16x6_fwd(const float* x, const float* u, const float* scale, const float* bias, const float* residual, float* y,
+                                       int N, int H, int W, int Cin, int Cout, int stride, int relu, void* stream) {
+    if (!x || !u || !y || N <= 0 || H <= 0 || W <= 0) return fail(VATL_EINVAL, "gemm1x1_bf16x6_fwd: null pointer or empty batch");
+    const long long M = (long long)N * H * W;
+    if (stride != 1 || !x6_shape_ok(M, Cin, 0, Cout))
+        return fail(VATL_EINVAL, "gemm1x1_bf16x6_fwd: %lld x %d -> %d, stride %d is outside stride 1, K %% 64 == 0, K >= 512, N %% 128 == 0 and 32-bit offsets", M, Cin, Cout, stride);
+    ConvParams p{};
+    p.x = x; p.w = u; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.CoutPad = Cout;
+    p.R = 1; p.S = 1; p.stride = 1;
+    p.Ho = H; p.Wo = W; p.M = (int)M;
+    p.OH = H; p.OW = W; p.osy = 1; p.osx = 1;
+    p.relu = relu;
+    p.kpr = Cin / BK; p.ktiles = p.kpr; p.K = Cin;
+    p.x_bytes = (unsigned)(M * Cin * 4); p.y_bytes = (unsigned)(M * Cout * 4); p.w_bytes = (unsigned)(6LL * Cout * Cin);
+    p.d_HoWo = make_fastdiv((unsigned)(H * W)); p.d_Wo = make_fastdiv((unsigned)W);
+    return residual ? launch_x6_impl<false, true>(p, (hipStream_t)stream) : launch_x6_impl<false, false>(p, (hipStream_t)stream);
+}
+
+extern "C" int vatl_gemm1x1_bf16x6_dual_fwd(const float* a, const float* x, const float* u, const float* bias, const float* residual, float* y,
+                                            int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int stride2, int Cout, int relu, void* stream) {
+    if (!a || !x || !u || !y || N <= 0 || Ho <= 0 || Wo <= 0) return fail(VATL_EINVAL, "gemm1x1_bf16x6_dual_fwd: null pointer or empty batch");
+    if (residual) return fail(VATL_EINVAL, "gemm1x1_bf16x6_dual_fwd: the dual form takes no residual");
+    if (stride2 < 1 || (long long)(Ho - 1) * stride2 >= H2 || (long long)(Wo - 1) * stride2 >= W2)
+        return fail(VATL_EINVAL, "gemm1x1_bf16x6_dual_fwd: stride %d does not map %dx%d onto %dx%d", stride2, Ho, Wo, H2, W2);
+    const long long M = (long long)N * Ho * Wo, x2e = (long long)N * H2 * W2 * C2;
+    if (C1 <= 0 || C2 <= 0 || !x6_shape_ok(M, C1 + C2, C1, Cout) || x2e >= (1LL << 30))
+        return fail(VATL_EINVAL, "gemm1x1_bf16x6_dual_fwd: %lld x (%d + %d) -> %d is outside C1 %% 64 == 0, C2 %% 64 == 0, K >= 384, N %% 128 == 0 and 32-bit offsets", M, C1, C2, Cout);
+    ConvParams p{};
+    p.x = a; p.x2 = x; p.w = u; p.bias = bias; p.y = y;
+    p.N = N; p.H = Ho; p.W = Wo; p.Cin = C1; p.Cout = Cout; p.CoutPad = Cout;
+    p.R = 1; p.S = 1; p.stride = 1;
+    p.Ho = Ho; p.Wo = Wo; p.M = (int)M;
+    p.OH = Ho; p.OW = Wo; p.osy = 1; p.osx = 1;
+    p.relu = relu;
+    p.k1 = C1 / BK; p.C2 = C2; p.H2 = H2; p.W2 = W2; p.stride2 = stride2;
+    p.kpr = (C1 + C2) / BK; p.ktiles = p.kpr; p.K = C1 + C2;
+    p.x_bytes = (unsigned)(M * C1 * 4); p.x2_bytes = (unsigned)(x2e * 4); p.y_bytes = (unsigned)(M * Cout * 4); p.w_bytes = (unsigned)(6LL * Cout * p.K);
+    p.d_HoWo = make_fastdiv((unsigned)(Ho * Wo)); p.d_Wo = make_fastdiv((unsigned)Wo);
+    return launch_x6_impl<true, false>(p, (hipStream_t)stream);
+}

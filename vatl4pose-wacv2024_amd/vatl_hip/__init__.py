@@ -136,6 +136,11 @@ SIGNATURES = {
     "vatl_pack_winograd_s2_43_weight": (_i, [_p, _p, _i, _i, _p]),
     "vatl_conv3x3s2_winograd43_supported": (_i, [_i, _i, _i, _i, _i]),
     "vatl_conv3x3s2_winograd43_fwd": (_i, [_p] * 5 + [_i] * 6 + [_p]),
+    "vatl_gemm1x1_bf16x6_weight_floats": (_i64, [_i, _i]),
+    "vatl_pack_gemm1x1_bf16x6_weight": (_i, [_p, _p, _i, _i, _p]),
+    "vatl_gemm1x1_bf16x6_supported": (_i, [_i64, _i, _i, _i]),
+    "vatl_gemm1x1_bf16x6_fwd": (_i, [_p] * 6 + [_i] * 7 + [_p]),
+    "vatl_gemm1x1_bf16x6_dual_fwd": (_i, [_p] * 6 + [_i] * 10 + [_p]),
     "vatl_winograd_deconv_stats_row_blocks": (_i64, [_i64, _i, _i]),
     "vatl_deconv4x4s2_winograd_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_conv2d_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
@@ -313,7 +318,7 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
 
 ROUTE_NAMES = ("igemm", "igemm_bnbwd", "igemm_dma", "persistent_1x1", "streamk", "rows_1x1", "bottleneck_chain", "stem_pool", "halo_3x3", "winograd",
                "winograd_2h", "winograd_bnbwd", "winograd_persist", "winograd_c32", "wgrad", "winograd_wgrad", "winograd_wgrad_2h", "winograd_wgrad_table", "winograd_f4", "winograd_f4_bnbwd",
-               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43", "stem_pool_w1d", "chain_proj", "chain_step")
+               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43", "stem_pool_w1d", "chain_proj", "chain_step", "gemm1x1_bf16x6")
 
 
 class flop_meter:
@@ -677,6 +682,16 @@ def pack_winograd_s2_43_weight(w: torch.Tensor) -> torch.Tensor:
         int(lib().vatl_winograd_s2_43_weight_floats(cout, cin)), "vatl_pack_winograd_s2_43_weight", (cout, cin), None), planned=False)
 
 
+def pack_gemm1x1_bf16x6_weight(w: torch.Tensor) -> torch.Tensor:
+    """The [N][K] fp32 filter of a 1x1 layer (pack_conv_weight's (N,1,1,K), or the rows of pack_conv1x1_dual_weight) -> its three bf16 planes (csrc/split16.h) in
+    the order the B fragments of csrc/gemm1x1_bf16x6.hip are read: 6 bytes per weight.  Inference only: packed on the spot, never part of a PackPlan's
+    one-launch re-pack table."""
+    n = w.shape[0]
+    k = w.numel() // n
+    return _pack(("gemm1x1_bf16x6", w.data_ptr(), tuple(w.shape)), w, lambda: (
+        int(lib().vatl_gemm1x1_bf16x6_weight_floats(n, k)), "vatl_pack_gemm1x1_bf16x6_weight", (n, k), None), planned=False)
+
+
 def pack_winograd_deconv_dgrad_weight(w: torch.Tensor) -> torch.Tensor:
     """ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> the filters of its DATA gradient (a 4x4 / stride 2 conv over dz = four pixel
     phases x 2x2 convolutions) in the F(3x3,2x2) transform domain."""
@@ -757,11 +772,18 @@ def conv3x3s2_winograd43_supported(n: int, h: int, w: int, cin: int, cout: int) 
     return bool(lib().vatl_conv3x3s2_winograd43_supported(n, h, w, cin, cout))
 
 
+def gemm1x1_bf16x6_supported(m: int, k: int, k1: int, n: int) -> bool:
+    """m rows of a 1x1 / stride-1 layer k -> n (k1 = 0), or of the dual form (k1 + (k - k1)) -> n, on the bf16x6 GEMM (csrc/gemm1x1_bf16x6.hip)."""
+    return bool(lib().vatl_gemm1x1_bf16x6_supported(m, k, k1, n))
+
+
 def conv2d_fwd(x, w_packed, scale, bias, cout: int, r: int, s: int, stride: int, pad: int, relu: bool,
-               residual=None, out_nchw: bool = False, out=None, u_s2=None):
+               residual=None, out_nchw: bool = False, out=None, u_s2=None, u_x6=None):
     """Conv2d + folded BN (+ residual) (+ ReLU) of an NHWC tensor on the implicit GEMM — or, when ``u_s2`` (pack_winograd_s2_43_weight) is given and the
     call is a 3x3 / stride 2 / pad 1 layer without residual, NHWC output, of a shape the kernel serves (conv3x3s2_winograd43_supported), as Winograd
-    F(4x3,2x2) summed over the four input phases (csrc/winograd_s2_43.hip; other bits).  Every other call ignores ``u_s2``."""
+    F(4x3,2x2) summed over the four input phases (csrc/winograd_s2_43.hip; other bits).  Every other call ignores ``u_s2``.
+    With ``u_x6`` (pack_gemm1x1_bf16x6_weight) a 1x1 / stride 1 layer with NHWC output of a shape gemm1x1_bf16x6_supported admits runs as six bf16 MFMAs per
+    product (csrc/gemm1x1_bf16x6.hip; same values to fp32 rounding, other bits); every other call ignores ``u_x6``."""
     n, h, w, cin = x.shape
     ho = (h + 2 * pad - r) // stride + 1
     wo = (w + 2 * pad - s) // stride + 1
@@ -772,16 +794,25 @@ def conv2d_fwd(x, w_packed, scale, bias, cout: int, r: int, s: int, stride: int,
         _check(lib().vatl_conv3x3s2_winograd43_fwd(_ptr(x), _ptr(u_s2), _ptr(scale), _ptr(bias), _ptr(y), n, h, w, cin, cout, int(relu), _stream()),
                "vatl_conv3x3s2_winograd43_fwd")
         return y
+    if u_x6 is not None and (r, s, stride, pad) == (1, 1, 1, 0) and not out_nchw and gemm1x1_bf16x6_supported(n * h * w, cin, 0, cout):
+        _check(lib().vatl_gemm1x1_bf16x6_fwd(_ptr(x), _ptr(u_x6), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout, stride, int(relu),
+                                             _stream()), "vatl_gemm1x1_bf16x6_fwd")
+        return y
     _check(lib().vatl_conv2d_fwd(_ptr(x), _ptr(w_packed), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w, cin, cout,
                                  w_packed.shape[0], r, s, stride, pad, int(relu), int(out_nchw), _stream()), "vatl_conv2d_fwd")
     return y
 
 
-def conv1x1_dual_fwd(a, x, w_packed, bias, cout: int, stride2: int, relu: bool, out=None):
-    """relu?(W1' a + W2' x[::s, ::s] + bias): a (N,Ho,Wo,C1) and x (N,H2,W2,C2) NHWC -> (N,Ho,Wo,Cout)."""
+def conv1x1_dual_fwd(a, x, w_packed, bias, cout: int, stride2: int, relu: bool, out=None, u_x6=None):
+    """relu?(W1' a + W2' x[::s, ::s] + bias): a (N,Ho,Wo,C1) and x (N,H2,W2,C2) NHWC -> (N,Ho,Wo,Cout).  With ``u_x6`` (pack_gemm1x1_bf16x6_weight of
+    w_packed) and a shape gemm1x1_bf16x6_supported admits, as six bf16 MFMAs per product (csrc/gemm1x1_bf16x6.hip; other bits); else ``u_x6`` is ignored."""
     n, ho, wo, c1 = a.shape
     _, h2, w2, c2 = x.shape
     y = out if out is not None else torch.empty((n, ho, wo, cout), device=a.device, dtype=torch.float32)
+    if u_x6 is not None and gemm1x1_bf16x6_supported(n * ho * wo, c1 + c2, c1, cout):
+        _check(lib().vatl_gemm1x1_bf16x6_dual_fwd(_ptr(a), _ptr(x), _ptr(u_x6), _ptr(bias), None, _ptr(y), n, ho, wo, c1, h2, w2, c2, stride2, cout, int(relu),
+                                                  _stream()), "vatl_gemm1x1_bf16x6_dual_fwd")
+        return y
     _check(lib().vatl_conv1x1_dual_fwd(_ptr(a), _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(y), n, ho, wo, c1, h2, w2, c2, stride2, cout,
                                        w_packed.shape[0], int(relu), _stream()), "vatl_conv1x1_dual_fwd")
     return y
