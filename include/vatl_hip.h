@@ -1015,6 +1015,60 @@ int vatl_se_scale_add_relu_h16(const void* x, const float* gate, const void* res
 int vatl_fuse_upsample_add_h16(const void* base, const void* z0, int shift0, const void* z1, int shift1, const void* z2, int shift2,
                                void* y, int N, int H, int W, int C, int relu, int dtype, void* stream);
 
+/* BF16 FINE-TUNE STEP (csrc/wgrad_h16.hip, csrc/train_glue_h16.hip, the data-gradient launcher of csrc/conv_h16.hip;
+ * alphapose/models/hip_train_h16.py).  Opt-in (cfg.RETRAIN.PRECISION): the fp32 trainer takes none of these entry points, they feed no
+ * FLOP meter and have no tuning knob.  Same conventions as the inference route above: T named by `dtype`, NHWC, 16-byte aligned, channel
+ * counts of T tensors multiples of 8 ("C8": the count rounded up to 8, the padding channels exact zeros).  The input, every conv output z,
+ * every BatchNorm (+ residual) (+ ReLU) output y and every gradient with respect to them are T; products are accumulated in fp32 by the
+ * MFMA; statistics, backward sums, weight / bias / BatchNorm gradients are fp32.  Every reduction has one fixed order (no atomics; split
+ * boundaries depend on the geometry only; partials added in ascending order): results are bit-reproducible run to run.
+ *
+ * VATL_WGRAD_H16_CHUNK: pixels per split of the weight gradient's reduction; vatl_wgrad_h16_splits(M) = ceil(M / chunk) for M pixels.
+ * vatl_conv2d_wgrad_h16: dW[co][r][s][ci] = sum over the M = N*Ho*Wo output pixels of dz[p][co] * x[p*stride - pad + (r,s)][ci] on
+ *   v_mfma_f32_16x16x32_{f16,bf16}; x (N,H,W,Cin8), dz (N,Ho,Wo,Cout8); one fp32 partial [Cout8][R][S][Cin8] per split into `workspace`
+ *   (vatl_conv2d_wgrad_h16_workspace_floats floats; NULL or too small is refused).  R, S <= 7, stride 1 or 2.  transposed != 0:
+ *   nn.ConvTranspose2d(4,2,1) with x (N,H,W,Cin8) its forward input and dz (N,2H,2W,Cout8) its output gradient — the operands exchange
+ *   roles (M = N*H*W, partials [Cin8][4][4][Cout8]); the workspace size is then ..._workspace_floats(Cin8, Cout8, 4, 4, N*H*W).
+ * vatl_wgrad_h16_reduce: adds the partials in ascending split order and writes the parameter's layout in fp32, padded channels dropped:
+ *   (Cout,Cin,R,S), or (Cin,Cout,4,4) for the transposed form.  M as above.
+ * vatl_pack_conv_weight_dgrad_h16: nn.Conv2d weight (Cout,Cin,R,S) fp32 -> the data gradient's filters, Cin8*R*S*Cout8 T in all: for
+ *   stride 1 one filter [Cin8][R][S][Cout8] with the taps flipped; for stride 2 the four input-pixel phases (py*2+px) one after the
+ *   other, phase filter [Cin8][ty][tx][Cout8] holding the taps of the parity of (py+pad, px+pad) in descending order.
+ * vatl_conv2d_dgrad_h16: dx (N,H,W,Cin8) T = data gradient of that conv from dz (N,Ho,Wo,Cout8), launch logic on the inference kernel:
+ *   one launch for stride 1, one per phase for stride 2 (a phase no tap reaches — the odd pixels of a 1x1 / stride 2 conv — is filled
+ *   with the residual, or +0.0); `residual` (N,H,W,Cin8) T or NULL is added in fp32 in the write-out (the skip connection's gradient).
+ *   The data gradient of ConvTranspose2d(4,2,1) is vatl_conv2d_fwd_h16 (4x4, stride 2, pad 1) with vatl_pack_conv_weight_h16 applied to
+ *   the (Cin,Cout,4,4) weight as if it were (Cout',Cin',4,4).
+ * Glue, M = N*H*W rows of C channels, workspace vatl_bn_h16_workspace_doubles(M, C) doubles:
+ *   vatl_bn_train_fwd_stats_h16: batch mean / biased variance of z (values converted from T) -> save_mean, save_invstd, (scale, bias) with
+ *     y = z*scale + bias, and the running-statistics update of nn.BatchNorm2d (momentum, unbiased variance; NULL = none);
+ *   vatl_bn_apply_h16: y = act(z*scale[c] + bias[c] (+ residual)) -> T;
+ *   vatl_bn_train_bwd_h16: g = dy*[y > 0] (y NULL: g = dy), dbeta = sum g, dgamma = sum g*xhat, dz = gamma*invstd*(g - dbeta/M -
+ *     xhat*dgamma/M) -> T; g_out_or_null receives g (the skip connection's gradient); coef3C: 3*C floats of scratch;
+ *   vatl_maxpool3x3s2_bwd_h16: dx (N,H,W,C) from dpool (N,Ho,Wo,C) and the pool's input x: the gradient goes to the first maximum of a
+ *     window in scan order (torch's tie rule), summed per input pixel in window order.
+ * There is NO stand-alone gradient-add entry point: every sum of two gradients of SimplePose is a skip connection's, and it is taken in
+ * fp32 in vatl_conv2d_dgrad_h16's write-out (`residual`) and rounded once. */
+#define VATL_WGRAD_H16_CHUNK 2048
+int64_t vatl_wgrad_h16_splits(int64_t M);
+int64_t vatl_conv2d_wgrad_h16_workspace_floats(int Cout8, int Cin8, int R, int S, int64_t M);
+int vatl_conv2d_wgrad_h16(const void* x, const void* dz, float* workspace, int64_t workspace_floats, int N, int H, int W, int Cin8, int Cout8,
+                          int R, int S, int stride, int pad, int transposed, int dtype, void* stream);
+int vatl_wgrad_h16_reduce(const float* workspace, float* dw, int64_t M, int Cout, int Cin, int R, int S, int transposed, void* stream);
+int vatl_pack_conv_weight_dgrad_h16(const float* w_oihw, void* w_packed, int Cout, int Cin, int R, int S, int stride, int pad, int dtype, void* stream);
+int vatl_conv2d_dgrad_h16(const void* dz, const void* w_dgrad, const void* residual, void* dx, int N, int H, int W, int Cin8, int Cout8,
+                          int R, int S, int stride, int pad, int dtype, void* stream);
+int64_t vatl_bn_h16_workspace_doubles(int64_t M, int C);
+int vatl_bn_train_fwd_stats_h16(const void* z, int64_t M, int C, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                float momentum, float eps, float* save_mean, float* save_invstd, float* scale, float* bias, double* workspace,
+                                int dtype, void* stream);
+int vatl_bn_apply_h16(const void* z, const float* scale, const float* bias, const void* residual, void* y, int64_t M, int C, int relu, int dtype,
+                      void* stream);
+int vatl_bn_train_bwd_h16(const void* dy, const void* y_or_null, const void* z, const float* gamma, const float* save_mean, const float* save_invstd,
+                          void* dz, void* g_out_or_null, float* dgamma, float* dbeta, int64_t M, int C, float* coef3C, double* workspace, int dtype,
+                          void* stream);
+int vatl_maxpool3x3s2_bwd_h16(const void* dpool, const void* x, void* dx, int N, int H, int W, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,20 @@ def precision_dtype(name):
     return table[name]
 
 
+def retrain_precision(cfg):
+    """``cfg.RETRAIN.PRECISION`` -> "fp32" (the default, and what an absent key means: ``hip_train.trainer_for``, the bits of every
+    shipped yaml) or "bf16" (the opt-in bf16 fine-tune step of ``hip_train_h16``, SimplePose only).  "fp16" would need loss scaling for
+    the heat-map MSE gradients and is, like anything else, a ValueError; "bf16" with another network a NotImplementedError."""
+    name = cfg.RETRAIN.get("PRECISION", "fp32") if "RETRAIN" in cfg else "fp32"
+    if not isinstance(name, str) or name not in ("fp32", "bf16"):
+        raise ValueError(f"RETRAIN.PRECISION must be one of ['bf16', 'fp32'], got {name!r}")
+    if name == "bf16":
+        model = cfg.MODEL.get("TYPE")
+        if model != "SimplePose":
+            raise NotImplementedError(f"RETRAIN.PRECISION bf16 serves SimplePose only, not MODEL.TYPE {model!r} (FastPose, DCN and HRNet train in fp32)")
+    return name
+
+
 def _collective(fn):
     """Public entry points run on every rank in lock-step.  On the driver process that owns worker processes, the outermost
     call is announced to them first (active_learning/worker.py); under torchrun every rank calls the method itself."""
@@ -113,6 +127,7 @@ class ActiveLearning:
         self.unc_lambda = float(cfg.VAL.get("UNC_LAMBDA", 1.0))
         self.precision = cfg.VAL.get("PRECISION", "fp32")             # of the evaluation pass's forwards only (_heatmaps)
         self.precision_dtype = precision_dtype(self.precision)
+        self.retrain_precision = retrain_precision(cfg)               # of retrain_model's trainer only
         self.finish_margin = 0.05
         # one process per GPU: join the torchrun group, or (plain single process, opt.num_gpu > 1) start the worker ranks
         self._depth = 0
@@ -826,7 +841,11 @@ class ActiveLearning:
         loader = DataLoader(subset, batch_size=self.cfg.RETRAIN.BATCH_SIZE * self.replicas, shuffle=True, num_workers=0, drop_last=False,
                             collate_fn=self.collate_fn, generator=gen)
         self.model.train()
-        trainer = hip_train.trainer_for(self.model)
+        if self.retrain_precision == "bf16":                   # opt-in (cfg.RETRAIN.PRECISION): same interface, bf16 storage, fp32 gradients
+            from alphapose.models import hip_train_h16
+            trainer = hip_train_h16.trainer_for_h16(self.model)
+        else:
+            trainer = hip_train.trainer_for(self.model)
         arena = hip_train.arena_for(self.model)
         # the per-step loss / accuracy read-backs wait until the EPOCH's steps are enqueued: read inside the loop they drain the stream every step, and the host's
         # preparation of the next mini-batch (crops, targets) then runs behind the step instead of beside it.  Flushed once per epoch (one synchronisation, before

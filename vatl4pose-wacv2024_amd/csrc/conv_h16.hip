@@ -252,6 +252,61 @@ __global__ void pack_deconv_weight_h16_kernel(const float* __restrict__ src, uns
 
 static inline int pack_grid_h16(long long n) { long long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
+// DATA GRADIENT of the bf16 fine-tune step: dx = conv(dz, filter with the two channel counts exchanged), on conv_h16_kernel as it is.
+// Along one axis, input pixel i = stride*j + ph (phase ph) receives dz[j + d] * w[r] for the taps r = i + pad - stride*(j + d): those of
+// the parity of ph + pad under stride 2, all of them under stride 1.  Taken in DESCENDING order r_0 > r_1 > ... they read
+// dz[j - pad' + t], t = 0 .. taps-1: a plain stride-1 conv of dz with `taps` taps and padding pad' (which may be negative).
+struct DgradAxis { int taps, r0, pad; };        // number of taps, the largest one (tap t is r0 - stride*t), the phase conv's padding
+__host__ __device__ inline DgradAxis dgrad_axis(int R, int stride, int pad, int ph) {
+    const int par = (ph + pad) % stride;
+    DgradAxis a{0, 0, 0};
+    if (par > R - 1) return a;                  // no tap reaches this phase (1x1 / stride 2, odd pixels)
+    a.r0 = par + (R - 1 - par) / stride * stride;
+    a.taps = (a.r0 - par) / stride + 1;
+    a.pad = (a.r0 - ph - pad) / stride;         // exact: r0 = ph + pad (mod stride)
+    return a;
+}
+// Packed data-gradient filters: the stride*stride phases one after the other (phase = py*stride + px), each [Cin8][ty][tx][Cout8] T with
+// w[co][ci][ry.r0 - stride*ty][rx.r0 - stride*tx]; every tap belongs to exactly one phase, so the whole buffer has Cin8*R*S*Cout8 elements.
+__host__ __device__ inline long long dgrad_phase_offset(int R, int S, int stride, int pad, int phase, long long cc) {
+    long long off = 0;
+    for (int q = 0; q < phase; ++q) off += cc * dgrad_axis(R, stride, pad, q / stride).taps * dgrad_axis(S, stride, pad, q % stride).taps;
+    return off;
+}
+template <typename T>
+__global__ void pack_dgrad_weight_h16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int Cout, int Cin, int Cout8, int Cin8, int R, int S,
+                                             int stride, int pad) {
+    const long long cc = (long long)Cin8 * Cout8;
+    for (int phase = 0; phase < stride * stride; ++phase) {
+        const DgradAxis ay = dgrad_axis(R, stride, pad, phase / stride), ax = dgrad_axis(S, stride, pad, phase % stride);
+        unsigned short* out = dst + dgrad_phase_offset(R, S, stride, pad, phase, cc);
+        const long long total = cc * ay.taps * ax.taps;
+        for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+            const int co = (int)(i % Cout8);
+            long long t = i / Cout8;
+            const int tx = (int)(t % ax.taps); t /= ax.taps;
+            const int ty = (int)(t % ay.taps);
+            const int ci = (int)(t / ay.taps);
+            const int r = ay.r0 - stride * ty, s = ax.r0 - stride * tx;
+            out[i] = (co < Cout && ci < Cin) ? T::from_f32(src[(((long long)co * Cin + ci) * R + r) * S + s]) : (unsigned short)0;
+        }
+    }
+}
+
+// the pixels of a phase no tap reaches: dx = residual, or +0.0 (eight channels per thread)
+__global__ void dgrad_fill_phase_h16_kernel(const uint4* __restrict__ residual, uint4* __restrict__ dx, long long N, int H, int W, int G, int stride, int py,
+                                            int px, int Hp, int Wp) {
+    const long long total = N * Hp * Wp * G;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int gq = (int)(i % G);
+        long long t = i / G;
+        const int jx = (int)(t % Wp); t /= Wp;
+        const int jy = (int)(t % Hp);
+        const long long o = (((t / Hp) * H + (long long)jy * stride + py) * W + (long long)jx * stride + px) * G + gq;
+        dx[o] = residual ? residual[o] : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
 }  // namespace vatl
 
 using namespace vatl;
@@ -300,6 +355,49 @@ extern "C" int vatl_deconv4x4s2_fwd_h16(const void* x, const void* w, const floa
         const int rc = launch_conv_h16("deconv4x4s2_fwd_h16", x, (const unsigned short*)w + (long long)ph * Cout * 4 * Cin, scale, bias, nullptr, y, g, N, dtype,
                                        (hipStream_t)stream);
         if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int vatl_pack_conv_weight_dgrad_h16(const float* w_oihw, void* w_packed, int Cout, int Cin, int R, int S, int stride, int pad, int dtype, void* stream) {
+    if (!w_oihw || !w_packed || Cout < 1 || Cin < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0 || !h16_dtype_ok(dtype))
+        return fail(VATL_EINVAL, "pack_conv_weight_dgrad_h16: bad arguments");
+    const int Cin8 = (Cin + 7) & ~7, Cout8 = (Cout + 7) & ~7;
+    const dim3 grid(pack_grid_h16((long long)Cin8 * Cout8 * R * S));
+    if (dtype == kH16F16)
+        hipLaunchKernelGGL(pack_dgrad_weight_h16_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cout8, Cin8, R, S,
+                           stride, pad);
+    else
+        hipLaunchKernelGGL(pack_dgrad_weight_h16_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cout8, Cin8, R, S,
+                           stride, pad);
+    return check_launch("pack_conv_weight_dgrad_h16");
+}
+
+extern "C" int vatl_conv2d_dgrad_h16(const void* dz, const void* w_dgrad, const void* residual, void* dx, int N, int H, int W, int Cin8, int Cout8, int R, int S,
+                                     int stride, int pad, int dtype, void* stream) {
+    const char* what = "conv2d_dgrad_h16";
+    // roles on the kernel: dz is the input (Cout8 channels), dx the output (Cin8 channels)
+    if (const int rc = conv_h16_contract(what, dz, w_dgrad, residual, dx, Cout8, Cin8, 0, dtype)) return rc;
+    if (N < 0 || H < 1 || W < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0 || H + 2 * pad < R || W + 2 * pad < S)
+        return fail(VATL_EINVAL, "%s: N %d, %dx%d, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", what, N, H, W, R, S, stride, pad);
+    if (N == 0) return 0;
+    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+    const long long cc = (long long)Cin8 * Cout8;
+    for (int phase = 0; phase < stride * stride; ++phase) {
+        const int py = phase / stride, px = phase % stride;
+        const int Hp = H > py ? (H - py + stride - 1) / stride : 0, Wp = W > px ? (W - px + stride - 1) / stride : 0;
+        if (Hp == 0 || Wp == 0) continue;
+        const DgradAxis ay = dgrad_axis(R, stride, pad, py), ax = dgrad_axis(S, stride, pad, px);
+        if (ay.taps == 0 || ax.taps == 0) {
+            const long long total = (long long)N * Hp * Wp * (Cin8 >> 3);
+            hipLaunchKernelGGL(dgrad_fill_phase_h16_kernel, dim3(pack_grid_h16(total)), dim3(256), 0, (hipStream_t)stream, (const uint4*)residual, (uint4*)dx,
+                               (long long)N, H, W, Cin8 >> 3, stride, py, px, Hp, Wp);
+            if (const int rc = check_launch(what)) return rc;
+            continue;
+        }
+        ConvH16Geom g{(long long)N * Hp * Wp, Ho, Wo, Cout8, Cin8, ay.taps, ax.taps, 1, ay.pad, ax.pad, Hp, Wp, H, W, stride, stride, py, px, 0, 0};
+        const unsigned short* wp = (const unsigned short*)w_dgrad + dgrad_phase_offset(R, S, stride, pad, phase, cc);
+        if (const int rc = launch_conv_h16(what, dz, wp, nullptr, nullptr, residual, dx, g, N, dtype, (hipStream_t)stream)) return rc;
     }
     return 0;
 }

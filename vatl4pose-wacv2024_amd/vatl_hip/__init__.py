@@ -221,6 +221,17 @@ SIGNATURES = {
     "vatl_pixelshuffle2_fwd_h16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_se_scale_add_relu_h16": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "vatl_fuse_upsample_add_h16": (_i, [_p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "vatl_wgrad_h16_splits": (_i64, [_i64]),
+    "vatl_conv2d_wgrad_h16_workspace_floats": (_i64, [_i, _i, _i, _i, _i64]),
+    "vatl_conv2d_wgrad_h16": (_i, [_p, _p, _p, _i64] + [_i] * 11 + [_p]),
+    "vatl_wgrad_h16_reduce": (_i, [_p, _p, _i64, _i, _i, _i, _i, _i, _p]),
+    "vatl_pack_conv_weight_dgrad_h16": (_i, [_p, _p] + [_i] * 7 + [_p]),
+    "vatl_conv2d_dgrad_h16": (_i, [_p] * 4 + [_i] * 10 + [_p]),
+    "vatl_bn_h16_workspace_doubles": (_i64, [_i64, _i]),
+    "vatl_bn_train_fwd_stats_h16": (_i, [_p, _i64, _i, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i, _p]),
+    "vatl_bn_apply_h16": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
+    "vatl_bn_train_bwd_h16": (_i, [_p] * 10 + [_i64, _i, _p, _p, _i, _p]),
+    "vatl_maxpool3x3s2_bwd_h16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib = None
@@ -2590,3 +2601,120 @@ def fuse_upsample_add_h16(base, ups, relu: bool):
     _check(lib().vatl_fuse_upsample_add_h16(_ptr(base, t), _ptr(a[0][0], t), a[0][1], _ptr(a[1][0], t), a[1][1], _ptr(a[2][0], t), a[2][1], _ptr(y, t),
                                             n, h, w, c, int(relu), code, _stream()), "vatl_fuse_upsample_add_h16")
     return y
+
+
+# ----------------------------------------------------------------------------
+# bf16 fine-tune step (csrc/wgrad_h16.hip, csrc/train_glue_h16.hip, the data-gradient launcher of csrc/conv_h16.hip)
+# ----------------------------------------------------------------------------
+
+def _pad8(c: int) -> int:
+    return (c + 7) // 8 * 8
+
+
+def wgrad_h16_splits(m: int) -> int:
+    return int(lib().vatl_wgrad_h16_splits(m))
+
+
+def conv2d_wgrad_h16(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: int, transposed: bool = False, out=None):
+    """Weight gradient in fp32: (cout,cin,r,s) from x (N,H,W,Cin8) and dz (N,Ho,Wo,Cout8) of one 16-bit dtype; ``transposed``:
+    ConvTranspose2d(4,2,1) with x its forward input and dz (N,2H,2W,Cout8) its output gradient -> (cin,cout,4,4)."""
+    t = x.dtype
+    code = _h16_code(t)
+    n, h, w, cin8 = x.shape
+    cout8 = dz.shape[-1]
+    if cin8 != _pad8(cin) or cout8 != _pad8(cout):
+        raise VatlError(f"conv2d_wgrad_h16: tensors carry {cin8} / {cout8} channels, the filter has {cin} / {cout}")
+    if transposed:
+        want, m, rows8, cols8, shape = (n, 2 * h, 2 * w, cout8), n * h * w, cin8, cout8, (cin, cout, 4, 4)
+    else:
+        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+        want, m, rows8, cols8, shape = (n, ho, wo, cout8), n * ho * wo, cout8, cin8, (cout, cin, r, s)
+    if tuple(dz.shape) != want:
+        raise VatlError(f"conv2d_wgrad_h16: dz has shape {tuple(dz.shape)}, expected {want}")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != shape:
+        raise VatlError(f"conv2d_wgrad_h16: out has shape {tuple(out.shape)}, expected {shape}")
+    floats = int(lib().vatl_conv2d_wgrad_h16_workspace_floats(rows8, cols8, r, s, m))
+    ws = torch.empty(floats, device=x.device, dtype=torch.float32)
+    _check(lib().vatl_conv2d_wgrad_h16(_ptr(x, t), _ptr(dz, t), _ptr(ws), floats, n, h, w, cin8, cout8, r, s, stride, pad, int(transposed), code, _stream()),
+           "vatl_conv2d_wgrad_h16")
+    _check(lib().vatl_wgrad_h16_reduce(_ptr(ws), _ptr(out), m, cout, cin, r, s, int(transposed), _stream()), "vatl_wgrad_h16_reduce")
+    return out
+
+
+def pack_conv_weight_dgrad_h16(w: torch.Tensor, stride: int, pad: int, dtype) -> torch.Tensor:
+    """(Cout,Cin,R,S) fp32 -> the flat data-gradient filters of conv2d_dgrad_h16 (Cin8*R*S*Cout8 elements of ``dtype``)."""
+    code = _h16_code(dtype)
+    cout, cin, r, s = w.shape
+    out = _new_like((_pad8(cin) * r * s * _pad8(cout),), w, dtype)
+    _check(lib().vatl_pack_conv_weight_dgrad_h16(_ptr(w.contiguous()), _ptr(out, dtype), cout, cin, r, s, stride, pad, code, _stream()),
+           "vatl_pack_conv_weight_dgrad_h16")
+    return out
+
+
+def conv2d_dgrad_h16(dz, w_dgrad, xshape, r: int, s: int, stride: int, pad: int, residual=None):
+    """dx (N,H,W,Cin8) = data gradient of a (r x s, stride, pad) conv from dz (N,Ho,Wo,Cout8); ``residual`` shaped like dx is added."""
+    t = dz.dtype
+    code = _h16_code(t)
+    n, h, w, cin8 = xshape
+    cout8 = dz.shape[-1]
+    ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+    if tuple(dz.shape) != (n, ho, wo, cout8) or w_dgrad.numel() != cin8 * r * s * cout8:
+        raise VatlError(f"conv2d_dgrad_h16: dz {tuple(dz.shape)} / filter of {w_dgrad.numel()} elements do not match input {tuple(xshape)}")
+    if residual is not None and tuple(residual.shape) != (n, h, w, cin8):
+        raise VatlError(f"conv2d_dgrad_h16: residual has shape {tuple(residual.shape)}, expected {(n, h, w, cin8)}")
+    dx = _new_like((n, h, w, cin8), dz)
+    _check(lib().vatl_conv2d_dgrad_h16(_ptr(dz, t), _ptr(w_dgrad, t), _ptr(residual, t), _ptr(dx, t), n, h, w, cin8, cout8, r, s, stride, pad, code, _stream()),
+           "vatl_conv2d_dgrad_h16")
+    return dx
+
+
+def _bn_ws_h16(m: int, c: int, device):
+    return torch.empty(int(lib().vatl_bn_h16_workspace_doubles(m, c)), device=device, dtype=torch.float64)
+
+
+def bn_train_fwd_stats_h16(z, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+    """z NHWC fp16 / bf16 -> save_mean, save_invstd, scale, bias (C,) fp32; running statistics updated in place (None: not)."""
+    code = _h16_code(z.dtype)
+    c = z.shape[-1]
+    m = z.numel() // c
+    outs = [torch.empty(c, device=z.device, dtype=torch.float32) for _ in range(4)]
+    _check(lib().vatl_bn_train_fwd_stats_h16(_ptr(z, z.dtype), m, c, _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), momentum, eps,
+                                             _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(_bn_ws_h16(m, c, z.device), torch.float64), code,
+                                             _stream()), "vatl_bn_train_fwd_stats_h16")
+    return outs
+
+
+def bn_apply_h16(z, scale, bias, residual, relu: bool):
+    code = _h16_code(z.dtype)
+    c = z.shape[-1]
+    y = torch.empty_like(z)
+    _check(lib().vatl_bn_apply_h16(_ptr(z, z.dtype), _ptr(scale), _ptr(bias), _ptr(residual, z.dtype), _ptr(y, z.dtype), z.numel() // c, c, int(relu), code,
+                                   _stream()), "vatl_bn_apply_h16")
+    return y
+
+
+def bn_train_bwd_h16(dy, y, z, gamma, save_mean, save_invstd, want_g: bool = False, dgamma=None, dbeta=None):
+    """-> dz, g (or None), dgamma, dbeta; dy, y (or None: no ReLU mask), z of one 16-bit dtype, the rest fp32."""
+    t = z.dtype
+    code = _h16_code(t)
+    c = z.shape[-1]
+    m = z.numel() // c
+    dz, dgamma, dbeta, coef = _bn_bwd_outs(z, dgamma, dbeta)
+    g = torch.empty_like(z) if want_g else None
+    _check(lib().vatl_bn_train_bwd_h16(_ptr(dy, t), _ptr(y, t), _ptr(z, t), _ptr(gamma), _ptr(save_mean), _ptr(save_invstd), _ptr(dz, t), _ptr(g, t),
+                                       _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _ptr(_bn_ws_h16(m, c, z.device), torch.float64), code, _stream()),
+           "vatl_bn_train_bwd_h16")
+    return dz, g, dgamma, dbeta
+
+
+def maxpool3x3s2_bwd_h16(dpool, x):
+    """Gradient of MaxPool2d(3,2,1)'s input x (N,H,W,C) from dpool: first maximum in scan order takes it (torch's tie rule)."""
+    code = _h16_code(x.dtype)
+    n, h, w, c = x.shape
+    if tuple(dpool.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
+        raise VatlError(f"maxpool3x3s2_bwd_h16: dpool has shape {tuple(dpool.shape)}")
+    dx = torch.empty_like(x)
+    _check(lib().vatl_maxpool3x3s2_bwd_h16(_ptr(dpool, x.dtype), _ptr(x, x.dtype), _ptr(dx, x.dtype), n, h, w, c, code, _stream()), "vatl_maxpool3x3s2_bwd_h16")
+    return dx
