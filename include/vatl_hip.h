@@ -1069,6 +1069,58 @@ int vatl_bn_train_bwd_h16(const void* dy, const void* y_or_null, const void* z, 
                           void* stream);
 int vatl_maxpool3x3s2_bwd_h16(const void* dpool, const void* x, void* dx, int N, int H, int W, int C, int dtype, void* stream);
 
+/* FLOAT64 REFERENCE GRADIENTS (csrc/wgrad_f64.hip, csrc/train_glue_f64.hip, the data-gradient launcher of csrc/conv_f64.hip;
+ * alphapose/models/hip_train_f64.py).  The yardstick of the fine-tune step, beside the float64 forward above: no trainer, plan or
+ * benchmark takes these entry points, they feed no FLOP meter and have no tuning knob.  Every tensor is float64 NHWC with any channel
+ * count >= 1; every reduction has one fixed order (no atomics; split boundaries depend on the row count only; partials added in
+ * ascending order): bits do not depend on grid size, occupancy or stream.
+ *
+ * VATL_WGRAD_F64_CHUNK: pixels per split of the weight gradient's reduction; vatl_wgrad_f64_splits(M) = ceil(M / chunk) for M pixels.
+ * vatl_conv2d_wgrad_f64: dW[co][r][s][ci] = sum over the M = N*Ho*Wo output pixels of dz[p][co] * x[p*stride - pad + (r,s)][ci] on
+ *   v_mfma_f64_16x16x4_f64; x (N,H,W,Cin), dz (N,Ho,Wo,Cout); one float64 partial slab [Cout][R][S][Cin] per split into `workspace`
+ *   (vatl_conv2d_wgrad_f64_workspace_doubles doubles; NULL or too small is refused).  R, S <= 7, stride 1 or 2, any pad >= 0.
+ *   transposed != 0: nn.ConvTranspose2d(4,2,1) with x (N,H,W,Cin) its forward input and dz (N,2H,2W,Cout) its output gradient — the
+ *   operands exchange roles (M = N*H*W, slabs [Cin][4][4][Cout]); the workspace size is then ..._workspace_doubles(Cin, Cout, 4, 4, N*H*W).
+ * vatl_wgrad_f64_reduce: adds the slabs in ascending split order and writes the parameter's layout: (Cout,Cin,R,S), or (Cin,Cout,4,4)
+ *   for the transposed form.  M as above.
+ * vatl_pack_conv_weight_dgrad_f64: nn.Conv2d weight (Cout,Cin,R,S) fp32 -> the data gradient's filters, Cin*R*S*Cout doubles in all
+ *   (exact): for stride 1 one filter [Cin][R][S][Cout] with the taps flipped; for stride 2 the four input-pixel phases (py*2+px) one
+ *   after the other, phase filter [Cin][ty][tx][Cout] holding the taps of the parity of (py+pad, px+pad) in descending order.
+ * vatl_conv2d_dgrad_f64: dx (N,H,W,Cin) = data gradient of that conv from dz (N,Ho,Wo,Cout), launch logic on the forward kernel: one
+ *   launch for stride 1, one per phase for stride 2 (a phase no tap reaches — the odd pixels of a 1x1 / stride 2 conv — is filled with
+ *   the residual, or +0.0); `residual` (N,H,W,Cin) or NULL is added in the write-out (the skip connection's gradient).  The data
+ *   gradient of ConvTranspose2d(4,2,1) is vatl_conv2d_fwd_f64 (4x4, stride 2, pad 1) with vatl_pack_conv_weight_f64 applied to the
+ *   (Cin,Cout,4,4) weight as if it were (Cout',Cin',4,4).
+ * Glue, M rows of C channels, workspace vatl_bn_f64_workspace_doubles(M, C) doubles:
+ *   vatl_bn_train_fwd_stats_f64: stats7C receives seven rows of C doubles — batch mean, biased variance (max(q/M - mean^2, 0)), invstd =
+ *     1/sqrt(var + eps), scale = gamma*invstd, bias = beta - mean*scale, and the running mean / unbiased running variance a training
+ *     step WOULD write for `momentum` from running_mean / running_var (both NULL: the batch values themselves).  Nothing is updated;
+ *   vatl_bn_apply_f64: y = act(fma(z, scale[c], bias[c]) (+ residual));
+ *   vatl_bn_train_bwd_f64: g = dy*[y > 0] (y NULL: g = dy), dbeta = sum g, dgamma = sum g*xhat, dz = gamma*invstd*(g - dbeta/M -
+ *     xhat*dgamma/M); g_out_or_null receives g (the skip connection's gradient);
+ *   vatl_maxpool3x3s2_bwd_f64: dx (N,H,W,C) from dpool (N,Ho,Wo,C) and the pool's input x: the gradient goes to the first maximum of a
+ *     window in scan order (torch's tie rule), summed per input pixel in window order;
+ *   vatl_col_sum_f64: out[c] = sum over the M rows of x[m][c] (the head's bias gradient). */
+#define VATL_WGRAD_F64_CHUNK 2048
+int64_t vatl_wgrad_f64_splits(int64_t M);
+int64_t vatl_conv2d_wgrad_f64_workspace_doubles(int Cout, int Cin, int R, int S, int64_t M);
+int vatl_conv2d_wgrad_f64(const double* x, const double* dz, double* workspace, int64_t workspace_doubles, int N, int H, int W, int Cin, int Cout,
+                          int R, int S, int stride, int pad, int transposed, void* stream);
+int vatl_wgrad_f64_reduce(const double* workspace, double* dw, int64_t M, int Cout, int Cin, int R, int S, int transposed, void* stream);
+int vatl_pack_conv_weight_dgrad_f64(const float* w_oihw, double* w_packed, int Cout, int Cin, int R, int S, int stride, int pad, void* stream);
+int vatl_conv2d_dgrad_f64(const double* dz, const double* w_dgrad, const double* residual, double* dx, int N, int H, int W, int Cin, int Cout,
+                          int R, int S, int stride, int pad, void* stream);
+int64_t vatl_bn_f64_workspace_doubles(int64_t M, int C);
+int vatl_bn_train_fwd_stats_f64(const double* z, int64_t M, int C, const double* gamma, const double* beta, const double* running_mean,
+                                const double* running_var, double momentum, double eps, double* stats7C, double* workspace, void* stream);
+int vatl_bn_apply_f64(const double* z, const double* scale, const double* bias, const double* residual, double* y, int64_t M, int C, int relu,
+                      void* stream);
+int vatl_bn_train_bwd_f64(const double* dy, const double* y_or_null, const double* z, const double* gamma, const double* save_mean,
+                          const double* save_invstd, double* dz, double* g_out_or_null, double* dgamma, double* dbeta, int64_t M, int C,
+                          double* workspace, void* stream);
+int vatl_maxpool3x3s2_bwd_f64(const double* dpool, const double* x, double* dx, int N, int H, int W, int C, void* stream);
+int vatl_col_sum_f64(const double* x, int64_t M, int C, double* out, double* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,3 +218,87 @@ extern "C" int vatl_deconv4x4s2_fwd_f64(const double* x, const double* w, const 
     }
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// DATA GRADIENT of the float64 reference step (alphapose/models/hip_train_f64.py): dx = conv(dz, filter with the two channel counts
+// exchanged), launch logic on conv_f64_kernel as it is — stride 1 is one launch with the flipped, transposed filter, stride 2 one
+// launch per input-pixel phase that writes every other pixel (phase geometry: dgrad_phase.h).  The skip gradient of a bottleneck
+// rides in the write-out's residual.  The data gradient of ConvTranspose2d(4,2,1) needs nothing new: it is vatl_conv2d_fwd_f64
+// (4x4, stride 2, pad 1) of dz with vatl_pack_conv_weight_f64 applied to the (Cin,Cout,4,4) parameter as if it were OIHW.
+#include "dgrad_phase.h"
+
+namespace vatl {
+
+// OIHW fp32 -> the phases one after the other, each [Cin][ty][tx][Cout] float64 (exact): the kernel's [rows][K] filter with rows = Cin
+__global__ void pack_dgrad_weight_f64_kernel(const float* __restrict__ src, double* __restrict__ dst, int Cout, int Cin, int R, int S, int stride, int pad) {
+    const long long cc = (long long)Cin * Cout;
+    for (int phase = 0; phase < stride * stride; ++phase) {
+        const DgradAxis ay = dgrad_axis(R, stride, pad, phase / stride), ax = dgrad_axis(S, stride, pad, phase % stride);
+        double* out = dst + dgrad_phase_offset(R, S, stride, pad, phase, cc);
+        const long long total = cc * ay.taps * ax.taps;
+        for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+            const int co = (int)(i % Cout);
+            long long t = i / Cout;
+            const int tx = (int)(t % ax.taps); t /= ax.taps;
+            const int ty = (int)(t % ay.taps);
+            const int ci = (int)(t / ay.taps);
+            const int r = ay.r0 - stride * ty, s = ax.r0 - stride * tx;
+            out[i] = (double)src[(((long long)co * Cin + ci) * R + r) * S + s];
+        }
+    }
+}
+
+// the pixels of a phase no tap reaches: dx = residual, or +0.0
+__global__ void dgrad_fill_phase_f64_kernel(const double* __restrict__ residual, double* __restrict__ dx, long long N, int H, int W, int C, int stride, int py,
+                                            int px, int Hp, int Wp) {
+    const long long total = N * Hp * Wp * C;
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        long long t = i / C;
+        const int jx = (int)(t % Wp); t /= Wp;
+        const int jy = (int)(t % Hp);
+        const long long o = (((t / Hp) * H + (long long)jy * stride + py) * W + (long long)jx * stride + px) * C + c;
+        dx[o] = residual ? residual[o] : 0.0;
+    }
+}
+
+}  // namespace vatl
+
+extern "C" int vatl_pack_conv_weight_dgrad_f64(const float* w_oihw, double* w_packed, int Cout, int Cin, int R, int S, int stride, int pad, void* stream) {
+    if (!w_oihw || !w_packed || Cout < 1 || Cin < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0)
+        return fail(VATL_EINVAL, "pack_conv_weight_dgrad_f64: bad arguments");
+    hipLaunchKernelGGL(pack_dgrad_weight_f64_kernel, dim3(pack_grid((long long)Cin * Cout * R * S)), dim3(256), 0, (hipStream_t)stream, w_oihw, w_packed, Cout, Cin,
+                       R, S, stride, pad);
+    return check_launch("pack_conv_weight_dgrad_f64");
+}
+
+extern "C" int vatl_conv2d_dgrad_f64(const double* dz, const double* w_dgrad, const double* residual, double* dx, int N, int H, int W, int Cin, int Cout, int R,
+                                     int S, int stride, int pad, void* stream) {
+    const char* what = "conv2d_dgrad_f64";
+    if (!dz || !w_dgrad || !dx) return fail(VATL_EINVAL, "%s: null pointer", what);
+    if (N < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0 || H + 2 * pad < R ||
+        W + 2 * pad < S)
+        return fail(VATL_EINVAL, "%s: N %d, %dx%d, %d <- %d channels, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", what, N, H, W, Cin, Cout, R, S,
+                    stride, pad);
+    if (N == 0) return 0;
+    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
+    const long long cc = (long long)Cin * Cout;
+    for (int phase = 0; phase < stride * stride; ++phase) {
+        const int py = phase / stride, px = phase % stride;
+        const int Hp = H > py ? (H - py + stride - 1) / stride : 0, Wp = W > px ? (W - px + stride - 1) / stride : 0;
+        if (Hp == 0 || Wp == 0) continue;
+        const DgradAxis ay = dgrad_axis(R, stride, pad, py), ax = dgrad_axis(S, stride, pad, px);
+        if (ay.taps == 0 || ax.taps == 0) {
+            hipLaunchKernelGGL(dgrad_fill_phase_f64_kernel, dim3(pack_grid((long long)N * Hp * Wp * Cin)), dim3(256), 0, (hipStream_t)stream, residual, dx,
+                               (long long)N, H, W, Cin, stride, py, px, Hp, Wp);
+            if (const int rc = check_launch(what)) return rc;
+            continue;
+        }
+        // roles on the kernel: dz is the input (Cout channels on an Ho x Wo plane), dx the output (Cin channels), written at (stride*j + py, stride*i + px)
+        ConvF64Geom g{(long long)N * Hp * Wp, Ho, Wo, Cout, Cin, ay.taps, ax.taps, 1, ay.pad, ax.pad, Hp, Wp, H, W, stride, stride, py, px, 0, 0};
+        if (const int rc = launch_conv_f64(what, dz, w_dgrad + dgrad_phase_offset(R, S, stride, pad, phase, cc), nullptr, nullptr, residual, dx, g, N,
+                                           (hipStream_t)stream))
+            return rc;
+    }
+    return 0;
+}

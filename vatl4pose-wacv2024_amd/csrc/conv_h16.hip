@@ -20,6 +20,7 @@
 // current one is multiplied.  LDS rows are padded from 128 to 144 bytes: the sixteen rows a fragment read touches at one k-group fall
 // on sixteen different 16-byte bank groups.
 // Operand lane maps: A[row lane&15][k 8(lane>>4)+j], B[k 8(lane>>4)+j][col lane&15]; result col lane&15, row 4(lane>>4)+reg.
+#include "dgrad_phase.h"
 #include "h16.h"
 
 namespace vatl {
@@ -253,26 +254,7 @@ __global__ void pack_deconv_weight_h16_kernel(const float* __restrict__ src, uns
 static inline int pack_grid_h16(long long n) { long long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 // DATA GRADIENT of the bf16 fine-tune step: dx = conv(dz, filter with the two channel counts exchanged), on conv_h16_kernel as it is.
-// Along one axis, input pixel i = stride*j + ph (phase ph) receives dz[j + d] * w[r] for the taps r = i + pad - stride*(j + d): those of
-// the parity of ph + pad under stride 2, all of them under stride 1.  Taken in DESCENDING order r_0 > r_1 > ... they read
-// dz[j - pad' + t], t = 0 .. taps-1: a plain stride-1 conv of dz with `taps` taps and padding pad' (which may be negative).
-struct DgradAxis { int taps, r0, pad; };        // number of taps, the largest one (tap t is r0 - stride*t), the phase conv's padding
-__host__ __device__ inline DgradAxis dgrad_axis(int R, int stride, int pad, int ph) {
-    const int par = (ph + pad) % stride;
-    DgradAxis a{0, 0, 0};
-    if (par > R - 1) return a;                  // no tap reaches this phase (1x1 / stride 2, odd pixels)
-    a.r0 = par + (R - 1 - par) / stride * stride;
-    a.taps = (a.r0 - par) / stride + 1;
-    a.pad = (a.r0 - ph - pad) / stride;         // exact: r0 = ph + pad (mod stride)
-    return a;
-}
-// Packed data-gradient filters: the stride*stride phases one after the other (phase = py*stride + px), each [Cin8][ty][tx][Cout8] T with
-// w[co][ci][ry.r0 - stride*ty][rx.r0 - stride*tx]; every tap belongs to exactly one phase, so the whole buffer has Cin8*R*S*Cout8 elements.
-__host__ __device__ inline long long dgrad_phase_offset(int R, int S, int stride, int pad, int phase, long long cc) {
-    long long off = 0;
-    for (int q = 0; q < phase; ++q) off += cc * dgrad_axis(R, stride, pad, q / stride).taps * dgrad_axis(S, stride, pad, q % stride).taps;
-    return off;
-}
+// The phase geometry (DgradAxis, dgrad_axis, dgrad_phase_offset) is dgrad_phase.h, shared with the float64 reference.
 template <typename T>
 __global__ void pack_dgrad_weight_h16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int Cout, int Cin, int Cout8, int Cin8, int R, int S,
                                              int stride, int pad) {

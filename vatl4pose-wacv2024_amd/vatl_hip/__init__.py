@@ -232,6 +232,18 @@ SIGNATURES = {
     "vatl_bn_apply_h16": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "vatl_bn_train_bwd_h16": (_i, [_p] * 10 + [_i64, _i, _p, _p, _i, _p]),
     "vatl_maxpool3x3s2_bwd_h16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_wgrad_f64_splits": (_i64, [_i64]),
+    "vatl_conv2d_wgrad_f64_workspace_doubles": (_i64, [_i, _i, _i, _i, _i64]),
+    "vatl_conv2d_wgrad_f64": (_i, [_p, _p, _p, _i64] + [_i] * 10 + [_p]),
+    "vatl_wgrad_f64_reduce": (_i, [_p, _p, _i64, _i, _i, _i, _i, _i, _p]),
+    "vatl_pack_conv_weight_dgrad_f64": (_i, [_p, _p] + [_i] * 6 + [_p]),
+    "vatl_conv2d_dgrad_f64": (_i, [_p] * 4 + [_i] * 9 + [_p]),
+    "vatl_bn_f64_workspace_doubles": (_i64, [_i64, _i]),
+    "vatl_bn_train_fwd_stats_f64": (_i, [_p, _i64, _i, _p, _p, _p, _p, _d, _d, _p, _p, _p]),
+    "vatl_bn_apply_f64": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _p]),
+    "vatl_bn_train_bwd_f64": (_i, [_p] * 10 + [_i64, _i, _p, _p]),
+    "vatl_maxpool3x3s2_bwd_f64": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "vatl_col_sum_f64": (_i, [_p, _i64, _i, _p, _p, _p]),
 }
 
 _lib = None
@@ -2453,6 +2465,121 @@ def fuse_upsample_add_f64(base, ups, relu: bool):
     _check(lib().vatl_fuse_upsample_add_f64(_f64(base), _f64(a[0][0]), a[0][1], _f64(a[1][0]), a[1][1], _f64(a[2][0]), a[2][1], _f64(y),
                                             n, h, w, c, int(relu), _stream()), "vatl_fuse_upsample_add_f64")
     return y
+
+
+# float64 reference gradients (csrc/wgrad_f64.hip, csrc/train_glue_f64.hip, the data-gradient launcher of csrc/conv_f64.hip)
+
+def wgrad_f64_splits(m: int) -> int:
+    return int(lib().vatl_wgrad_f64_splits(m))
+
+
+def conv2d_wgrad_f64(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: int, transposed: bool = False, out=None):
+    """Weight gradient in float64: (cout,cin,r,s) from x (N,H,W,cin) and dz (N,Ho,Wo,cout); ``transposed``: ConvTranspose2d(4,2,1)
+    with x its forward input and dz (N,2H,2W,cout) its output gradient -> (cin,cout,4,4)."""
+    n, h, w, cx = x.shape
+    cz = dz.shape[-1]
+    if cx != cin or cz != cout:
+        raise VatlError(f"conv2d_wgrad_f64: tensors carry {cx} / {cz} channels, the filter has {cin} / {cout}")
+    if transposed:
+        want, m, rows, cols, shape = (n, 2 * h, 2 * w, cout), n * h * w, cin, cout, (cin, cout, 4, 4)
+    else:
+        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+        want, m, rows, cols, shape = (n, ho, wo, cout), n * ho * wo, cout, cin, (cout, cin, r, s)
+    if tuple(dz.shape) != want:
+        raise VatlError(f"conv2d_wgrad_f64: dz has shape {tuple(dz.shape)}, expected {want}")
+    if out is None:
+        out = _new_f64(shape, x)
+    elif tuple(out.shape) != shape:
+        raise VatlError(f"conv2d_wgrad_f64: out has shape {tuple(out.shape)}, expected {shape}")
+    doubles = int(lib().vatl_conv2d_wgrad_f64_workspace_doubles(rows, cols, r, s, m))
+    ws = _new_f64((doubles,), x)
+    _check(lib().vatl_conv2d_wgrad_f64(_f64(x), _f64(dz), _f64(ws), doubles, n, h, w, cin, cout, r, s, stride, pad, int(transposed), _stream()),
+           "vatl_conv2d_wgrad_f64")
+    _check(lib().vatl_wgrad_f64_reduce(_f64(ws), _f64(out), m, cout, cin, r, s, int(transposed), _stream()), "vatl_wgrad_f64_reduce")
+    return out
+
+
+def pack_conv_weight_dgrad_f64(w: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    """(Cout,Cin,R,S) fp32 -> the flat data-gradient filters of conv2d_dgrad_f64 (Cin*R*S*Cout doubles, exact)."""
+    cout, cin, r, s = w.shape
+    out = _new_f64((cin * r * s * cout,), w)
+    _check(lib().vatl_pack_conv_weight_dgrad_f64(_ptr(w.contiguous()), _f64(out), cout, cin, r, s, stride, pad, _stream()), "vatl_pack_conv_weight_dgrad_f64")
+    return out
+
+
+def conv2d_dgrad_f64(dz, w_dgrad, xshape, r: int, s: int, stride: int, pad: int, residual=None):
+    """dx (N,H,W,Cin) = data gradient of a (r x s, stride, pad) conv from dz (N,Ho,Wo,Cout); ``residual`` shaped like dx is added."""
+    n, h, w, cin = xshape
+    cout = dz.shape[-1]
+    ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+    if tuple(dz.shape) != (n, ho, wo, cout) or w_dgrad.numel() != cin * r * s * cout:
+        raise VatlError(f"conv2d_dgrad_f64: dz {tuple(dz.shape)} / filter of {w_dgrad.numel()} elements do not match input {tuple(xshape)}")
+    if residual is not None and tuple(residual.shape) != (n, h, w, cin):
+        raise VatlError(f"conv2d_dgrad_f64: residual has shape {tuple(residual.shape)}, expected {(n, h, w, cin)}")
+    dx = _new_f64((n, h, w, cin), dz)
+    _check(lib().vatl_conv2d_dgrad_f64(_f64(dz), _f64(w_dgrad), _f64(residual), _f64(dx), n, h, w, cin, cout, r, s, stride, pad, _stream()),
+           "vatl_conv2d_dgrad_f64")
+    return dx
+
+
+def _bn_ws_f64(m: int, c: int, like):
+    return _new_f64((int(lib().vatl_bn_f64_workspace_doubles(m, c)),), like)
+
+
+def bn_train_fwd_stats_f64(z, gamma, beta, running_mean, running_var, momentum: float, eps: float):
+    """z NHWC float64 -> (7,C) float64: batch mean, biased variance, invstd, scale, bias, and the running mean / unbiased running
+    variance a training step WOULD write from ``running_mean`` / ``running_var`` (float64 copies; nothing is updated)."""
+    c = z.shape[-1]
+    m = z.numel() // c
+    for name, t in (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None and t.numel() != c:
+            raise VatlError(f"bn_train_fwd_stats_f64: {name} has {t.numel()} elements, z {c} channels")
+    out = _new_f64((7, c), z)
+    _check(lib().vatl_bn_train_fwd_stats_f64(_f64(z), m, c, _f64(gamma), _f64(beta), _f64(running_mean), _f64(running_var), float(momentum), float(eps),
+                                             _f64(out), _f64(_bn_ws_f64(m, c, z)), _stream()), "vatl_bn_train_fwd_stats_f64")
+    return out
+
+
+def bn_apply_f64(z, scale, bias, residual, relu: bool):
+    c = z.shape[-1]
+    if scale.numel() != c or bias.numel() != c or (residual is not None and residual.shape != z.shape):
+        raise VatlError(f"bn_apply_f64: scale / bias / residual do not match z {tuple(z.shape)}")
+    y = torch.empty_like(z)
+    _check(lib().vatl_bn_apply_f64(_f64(z), _f64(scale), _f64(bias), _f64(residual), _f64(y), z.numel() // c, c, int(relu), _stream()), "vatl_bn_apply_f64")
+    return y
+
+
+def bn_train_bwd_f64(dy, y, z, gamma, save_mean, save_invstd, want_g: bool = False):
+    """-> dz, g (or None), dgamma, dbeta, all float64; y None: no ReLU mask."""
+    c = z.shape[-1]
+    m = z.numel() // c
+    if dy.shape != z.shape or (y is not None and y.shape != z.shape) or save_mean.numel() != c or save_invstd.numel() != c:
+        raise VatlError(f"bn_train_bwd_f64: dy / y / statistics do not match z {tuple(z.shape)}")
+    dz = torch.empty_like(z)
+    g = torch.empty_like(z) if want_g else None
+    dgamma, dbeta = _new_f64((c,), z), _new_f64((c,), z)
+    _check(lib().vatl_bn_train_bwd_f64(_f64(dy), _f64(y), _f64(z), _f64(gamma), _f64(save_mean), _f64(save_invstd), _f64(dz), _f64(g), _f64(dgamma),
+                                       _f64(dbeta), m, c, _f64(_bn_ws_f64(m, c, z)), _stream()), "vatl_bn_train_bwd_f64")
+    return dz, g, dgamma, dbeta
+
+
+def maxpool3x3s2_bwd_f64(dpool, x):
+    """Gradient of MaxPool2d(3,2,1)'s input x (N,H,W,C) from dpool: first maximum in scan order takes it (torch's tie rule)."""
+    n, h, w, c = x.shape
+    if tuple(dpool.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
+        raise VatlError(f"maxpool3x3s2_bwd_f64: dpool has shape {tuple(dpool.shape)}")
+    dx = torch.empty_like(x)
+    _check(lib().vatl_maxpool3x3s2_bwd_f64(_f64(dpool), _f64(x), _f64(dx), n, h, w, c, _stream()), "vatl_maxpool3x3s2_bwd_f64")
+    return dx
+
+
+def col_sum_f64(x2d):
+    """(..., C) float64 -> (C,) column sums in one fixed order."""
+    c = x2d.shape[-1]
+    m = x2d.numel() // c
+    out = _new_f64((c,), x2d)
+    _check(lib().vatl_col_sum_f64(_f64(x2d), m, c, _f64(out), _f64(_bn_ws_f64(m, c, x2d)), _stream()), "vatl_col_sum_f64")
+    return out
 
 
 # ----------------------------------------------------------------------------
