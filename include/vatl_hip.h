@@ -52,7 +52,7 @@ int vatl_flop_meter_end(double* direct_flops, double* winograd_flops, int64_t* d
 #define VATL_ROUTE_NAMES "igemm,igemm_bnbwd,igemm_dma,persistent_1x1,streamk,rows_1x1,bottleneck_chain,stem_pool,halo_3x3," \
                          "winograd,winograd_2h,winograd_bnbwd,winograd_persist,winograd_c32,wgrad,winograd_wgrad,winograd_wgrad_2h," \
                          "winograd_wgrad_table,winograd_f4,winograd_f4_bnbwd,gemm1x1_ring,winograd_deconv43,winograd_s2_43,stem_pool_w1d," \
-                         "chain_proj,chain_step,gemm1x1_bf16x6"
+                         "chain_proj,chain_step,gemm1x1_bf16x6,gemm1x1_bf16x6_short"
 int vatl_flop_meter_routes(int64_t* counts, int n);
 
 /* ------------------------------------------------------------------------ *
@@ -907,6 +907,14 @@ int vatl_gemm1x1_bf16x6_fwd(const float* x, const float* u, const float* scale, 
                             int N, int H, int W, int Cin, int Cout, int stride, int relu, void* stream);
 int vatl_gemm1x1_bf16x6_dual_fwd(const float* a, const float* x, const float* u, const float* bias, const float* residual, float* y,
                                  int N, int Ho, int Wo, int C1, int H2, int W2, int C2, int stride2, int Cout, int relu, void* stream);
+/* The same GEMM for the short-K, wide-N 1x1 / stride-1 layers (conv3 of ResNet stages 2 and 3: 128 -> 512, 256 -> 1024, with or without the skip): the
+ * arithmetic, the filter planes (vatl_pack_gemm1x1_bf16x6_weight) and the operands of vatl_gemm1x1_bf16x6_fwd; the kernel instantiation loads scale /
+ * bias in front of the k-loop and brings the residual tile in by LDS-DMA under the last three stages.
+ * _short_supported(M, K, N): 1 for K % 64 == 0, 128 <= K < 512, N % 256 == 0, N >= 512 and the 32-bit offset guards above; else 0, and _short_fwd
+ * fails on those (and on stride != 1) without a launch.  Metered like the long-K launch (DIRECT class, 6/16), under the route gemm1x1_bf16x6_short. */
+int vatl_gemm1x1_bf16x6_short_supported(int64_t M, int K, int N);
+int vatl_gemm1x1_bf16x6_short_fwd(const float* x, const float* u, const float* scale, const float* bias, const float* residual, float* y,
+                                  int N, int H, int W, int Cin, int Cout, int stride, int relu, void* stream);
 int64_t vatl_winograd_deconv_stats_row_blocks(int64_t N, int H, int W);
 int vatl_deconv4x4s2_winograd_fwd_stats(const float* x, const float* u, float* y, double* stats, int64_t* row_blocks_used, int N, int H, int W,
                                         int Cin, int Cout, void* stream);

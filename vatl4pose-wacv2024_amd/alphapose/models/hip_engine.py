@@ -75,10 +75,19 @@ S2_43 = True
 # Geometry-only choice like WINOGRAD; not taken for NCHW output, in the small-batch module call or by the trainers.  False = the ring / tiled fp32 kernels (same values
 # to fp32 rounding, not the same bits).
 BF16X6 = True
+# ... and the short-K, wide-N 1x1 / stride 1 layers (128 <= K < 512, N >= 512: conv3 of ResNet stages 2 and 3, with or without the skip) on the short-K form of the
+# same kernel, in place of the row-streaming GEMM: the same arithmetic and filter planes; scale / bias are loaded in front of the k-loop and the residual tile comes
+# in by LDS-DMA under the last three stages (vatl_gemm1x1_bf16x6_short_fwd, inside vh.conv1x1_rows_fwd(..., u_x6=); profiles/bf16x6_short_notes.md).  In effect
+# only while BF16X6 is True; the same conditions.  False = the row-streaming fp32 kernel for these layers.
+# BF16X6_SHORT_MIN_K: the plans take the route from this K on (geometry only).  The kernel and its shape rule start at K = 128, and per layer both families win
+# (128 -> 512 + skip 1.27x, 256 -> 1024 + skip 1.5x at 1024 crops), but the headline step moved by 3x the spread of its base only with the K = 256 family alone
+# (profiles/bf16x6_short_notes.md, section 5; with both families it moved by 2.2x).  128 = both families.
+BF16X6_SHORT = True
+BF16X6_SHORT_MIN_K = 256
 
 
 class _Conv:
-    __slots__ = ("w", "u", "u32", "u4", "us2", "ux6", "wsrc", "wino", "c32", "f4", "s2", "x6", "scale", "bias", "cout", "r", "s", "stride", "pad")
+    __slots__ = ("w", "u", "u32", "u4", "us2", "ux6", "wsrc", "wino", "c32", "f4", "s2", "x6", "x6s", "scale", "bias", "cout", "r", "s", "stride", "pad")
 
     def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d | None):
         assert conv.groups == 1 and conv.dilation == (1, 1)
@@ -99,6 +108,8 @@ class _Conv:
         self.ux6 = None                                   # (packed from self.w, which for a 1x1 layer is the [N][K] filter itself)
         self.x6 = (BF16X6 and (self.r, self.s, self.stride, self.pad) == (1, 1, 1, 0) and conv.in_channels >= 512 and conv.in_channels % 64 == 0
                    and self.cout % 128 == 0)
+        self.x6s = (BF16X6 and BF16X6_SHORT and (self.r, self.s, self.stride, self.pad) == (1, 1, 1, 0) and max(128, BF16X6_SHORT_MIN_K) <= conv.in_channels < 512
+                    and conv.in_channels % 64 == 0 and self.cout >= 512 and self.cout % 256 == 0)
         self.wsrc = conv.weight.detach() if self.wino or self.s2 else None
         cb =conv.bias.detach() if conv.bias is not None else None
         if bn is not None:
@@ -121,6 +132,10 @@ class _Conv:
             if self.u is None:
                 self.u = vh.pack_winograd_weight(self.wsrc)
             return vh.conv3x3_winograd_fwd(x, self.u, self.scale, self.bias, self.cout, relu, residual=residual, out=out)
+        if self.x6s and not out_nchw and not vh.latency_mode() and vh.gemm1x1_bf16x6_short_supported(x.shape[0] * x.shape[1] * x.shape[2], x.shape[3], self.cout):
+            if self.ux6 is None:                                                          # short-K, wide N: six bf16 MFMAs per product, inside conv1x1_rows_fwd
+                self.ux6 = vh.pack_gemm1x1_bf16x6_weight(self.w)
+            return vh.conv1x1_rows_fwd(x, self.w, self.scale, self.bias, self.cout, relu, residual=residual, out=out, u_x6=self.ux6)
         if (ROWS_GEMM and self.r == 1 and self.stride == 1 and not out_nchw and not vh.latency_mode() and x.shape[-1] in ROWS_GEMM_K
                 and vh.conv1x1_rows_supported(x.shape[-1], 0, self.cout, x.shape[0] * x.shape[1] * x.shape[2])):
             return vh.conv1x1_rows_fwd(x, self.w, self.scale, self.bias, self.cout, relu, residual=residual, out=out)     # K = 128 / 256, wide N: row-streaming GEMM

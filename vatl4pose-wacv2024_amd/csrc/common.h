@@ -25,7 +25,7 @@ enum MeterRoute {
     kRouteIgemm = 0, kRouteIgemmBnBwd, kRouteIgemmDma, kRoutePersistent1x1, kRouteStreamK, kRouteRows, kRouteChain, kRouteStemPool, kRouteHalo,
     kRouteWino, kRouteWino2H, kRouteWinoBnBwd, kRouteWinoPersist, kRouteWinoC32, kRouteWgrad, kRouteWinoWgrad, kRouteWinoWgrad2H,
     kRouteWinoWgradTable, kRouteWinoF4, kRouteWinoF4BnBwd, kRouteGemm1x1Ring, kRouteWinoDeconv43, kRouteWinoS2_43, kRouteStemPoolW1d, kRouteChainProj,
-    kRouteChainStep, kRouteGemm1x1Bf16x6, kRouteCount
+    kRouteChainStep, kRouteGemm1x1Bf16x6, kRouteGemm1x1Bf16x6Short, kRouteCount
 };
 void meter_route(int route);
 

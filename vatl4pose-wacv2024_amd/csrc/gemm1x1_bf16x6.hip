@@ -1,5 +1,5 @@
 // The bf16x6 GEMM for the long-K 1x1 layers of the inference plans: fp32 operands, each product as six bf16 MFMAs.  Kernel, filter pack,
-// launcher, the shape rule (vatl_gemm1x1_bf16x6_supported) and the C entry points.
+// launcher, the shape rules (vatl_gemm1x1_bf16x6_supported, and vatl_gemm1x1_bf16x6_short_supported of the short-K form) and the C entry points.
 #include "conv_igemm.h"
 #include "split16.h"
 #include "tile_order.h"
@@ -32,6 +32,20 @@ namespace vatl {
 // Arithmetic per output row depends on that row's inputs and the filter only: the same bits alone and in any batch position.
 // Tail rows read row M-1; their stores lie past the descriptor and are dropped.  No atomics, no split-K.
 // Dual source: stages 0 .. 2 k1 - 1 read x, the rest x2 at the row's strided pixel (the ring kernel's rules).
+//
+// SHORT (128 <= K < 512, N >= 512: conv3 of ResNet stages 2 and 3; gemm1x1_bf16x6_short_kernel): the same loop, products and order — 8 to 28
+// stages — with the per-tile cost that a long loop hides taken out of the tail:
+//  * scale, bias and the write-out addresses are loaded / computed in front of the k-loop;
+//  * the residual tile is requested by LDS-DMA into the ring slots that fall free at the tail: stages S-3, S-2 and S-1 issue no operand
+//    requests, so slot (s - 1) % 4 is free from the barrier of each of them on — 60 KB.  The 64 KB tile less the last eight rows of
+//    either wave row (56 KB: compact row cr = 56 wm + lr, lr < 56, 512 bytes each, linear from the ring's base) goes there in 5 + 5 + 4
+//    requests per wave, the 2 x 4 elements a lane owns of the other eight rows are loaded into registers in front of the loop.  The
+//    write-out reads the tile with ds_read_b32 (16-byte chunk c of row cr sits at position c ^ 8 ((cr >> 2) & 1): the two half-waves
+//    of a read, four rows apart, take opposite halves of the 64 banks).  The residual's HBM round trip thus runs under the last three
+//    stages' MFMAs.  Counted waits of the tail (per wave, oldest first): S-3: [S-3, S-2, S-1] -> vmcnt(10), then R0 (5); S-2: [S-2, S-1, R0]
+//    -> vmcnt(10), then R1 (5); S-1: [S-1, R0, R1] -> vmcnt(10), then R2 (4); after the loop vmcnt(0) and one barrier.  The register
+//    loads and the scale / bias loads in front of the loop share the counter: wherever the compiler puts them among the first requests, an
+//    operation younger than stage s's pieces can only make a counted wait stricter (vmcnt(N) leaves at most the N youngest outstanding).
 // ---------------------------------------------------------------------------------------------------------
 constexpr int X6_BK = 16;                             // k per stage
 constexpr int X6_NS = 4;                              // stages in the ring
@@ -54,8 +68,16 @@ __device__ __forceinline__ f32x16 x6_mfma(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x6_bf16x8, a), __builtin_bit_cast(x6_bf16x8, b), c, 0, 0, 0);
 }
 
-template <bool DUAL, bool RES>
+struct X6Epilogue {                                   // what the write-out needs beside the accumulators
+    unsigned rowb, ylane;
+    __amdgpu_buffer_rsrc_t yr, rr;
+    float sc[2], bi[2], lo;
+};
+
+template <bool DUAL, bool RES, bool SHORT = false>
 __device__ __forceinline__ void gemm1x1_bf16x6_body(const ConvParams& p, float* smem) {
+    static_assert(!(SHORT && DUAL), "the short-K form is plain");
+    constexpr bool LDSRES = SHORT && RES;             // residual through the ring slots that fall free at the tail
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;          // 2 x 2 waves of 64 x 64
@@ -114,6 +136,47 @@ __device__ __forceinline__ void gemm1x1_bf16x6_body(const ConvParams& p, float* 
     for (int c = 0; c < 2; ++c) Ard[c] = smem + (wm * 64 + frow) * X6_BK + (((2 * h + c) ^ fsw) << 2);
     const float* Brd = smem + X6_A_FLOATS + (2 * wn * 64 + lane) * 4;
 
+    // ---- write-out operands (SHORT: in front of the k-loop).  Element e of tile (i, j) is row 32 i + (e & 3) + 8 (e >> 2) + 4 h, channel 64 wn + 32 j + frow.
+    auto epilogue_operands = [&]() {
+        X6Epilogue ep;
+        ep.rowb = (unsigned)p.Cout * 4u;
+        ep.ylane = (unsigned)(m0 + wm * 64 + 4 * h) * ep.rowb + (unsigned)(n0 + wn * 64 + frow) * 4u;
+        ep.yr = buf_rsrc(p.y, p.y_bytes);
+        ep.rr = buf_rsrc(RES ? p.res : p.y, RES ? p.y_bytes : 0u);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + wn * 64 + j * 32 + frow;
+            ep.sc[j] = p.scale ? p.scale[n] : 1.f;
+            ep.bi[j] = p.bias ? p.bias[n] : 0.f;
+        }
+        ep.lo = p.relu ? 0.f : -INFINITY;
+        return ep;
+    };
+    X6Epilogue ep;
+    if constexpr (SHORT) ep = epilogue_operands();
+    float dres[2][4];                                 // LDSRES: residual of rows 56 .. 59 (+ 4 h) of the wave's 64, the eight rows the ring has no room for
+    unsigned roff = 0;
+    if constexpr (LDSRES) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dres[j][r] = buf_load1(ep.rr, ep.ylane + (unsigned)(56 + r) * ep.rowb + (unsigned)j * 128u);
+        // request u of piece Q by wave w fills compact rows 40 Q + 8 u + 2 w + (lane >> 5): 1 KB, lane-linear; the lane fetches chunk (lane & 31) ^ 8 (w >> 1)
+        // (rows past M are clamped to row M - 1 like the A rows: every request stays inside the tensor, and those rows' stores are dropped)
+        roff = (unsigned)n0 * 4u + (unsigned)((lane & 31) ^ ((wave >> 1) << 3)) * 16u;
+    }
+    const int rrow = m0 + 2 * wave + (lane >> 5);
+    auto issue_res = [&](auto piece) {
+        constexpr int Q = decltype(piece)::value;
+#pragma unroll
+        for (int u = 0; u < (Q < 2 ? 5 : 4); ++u) {
+            const int cr0 = 40 * Q + 8 * u;                           // (a block of eight compact rows never straddles row 56)
+            const int row0 = cr0 + (cr0 >= 56 ? 8 : 0);               // tile row of compact row cr0
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(ep.rr, (lds_void*)(smem + (20 * Q + 4 * u + wave) * 256), 16,
+                                                     (unsigned)min(rrow + row0, p.M - 1) * ep.rowb + roff, 0, 0, 0);
+        }
+    };
+
     f32x16 acc[2][2], sml[2][2];                      // a0 w0 | the five small products
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -127,7 +190,7 @@ __device__ __forceinline__ void gemm1x1_bf16x6_body(const ConvParams& p, float* 
     // 3: s = S-1.  VMEM operations retire in order, so each count waits for this wave's pieces of stage s exactly.
     auto stage = [&](auto slot, auto kind, auto src, int s) {
         constexpr int B = decltype(slot)::value, KIND = decltype(kind)::value;
-        if constexpr (KIND <= 1) x6_wait_vm<10>();
+        if constexpr (KIND <= 1 || LDSRES) x6_wait_vm<10>();      // (LDSRES: the tail's residual requests keep two pieces behind stage s, see above)
         else if constexpr (KIND == 2) x6_wait_vm<5>();
         else x6_wait_vm<0>();
         __builtin_amdgcn_s_barrier();                 // every wave's pieces of stage s have landed; every wave is done reading slot (s - 1) % 4
@@ -143,6 +206,7 @@ __device__ __forceinline__ void gemm1x1_bf16x6_body(const ConvParams& p, float* 
 #pragma unroll
             for (int j = 0; j < 2; ++j) bw[pl][j] = *reinterpret_cast<const u32x4*>(Brd + B * X6_STAGE + (4 * pl + j) * 256);
         if constexpr (KIND == 0) issue(src, (B + 3) & 3, s + 3);
+        else if constexpr (LDSRES) issue_res(std::integral_constant<int, KIND - 1>{});      // into slot B - 1 = KIND - 1 (S % 4 == 0)
         // the split (split16.h): fragment dword d = k pair (2d, 2d + 1) of the lane's eight
         u32x4 a0[2], a1[2], a2[2];
 #pragma unroll
@@ -213,34 +277,62 @@ __device__ __forceinline__ void gemm1x1_bf16x6_body(const ConvParams& p, float* 
 
     // ---- write-out from the accumulator layout (the ring kernel's): element e of tile (i, j) is row 32 i + (e & 3) + 8 (e >> 2) + 4 h,
     // channel 64 wn + 32 j + frow; rows >= M lie past the descriptor (loads read 0, stores are dropped).  Same expression as conv_epilogue.
-    const unsigned rowb = (unsigned)p.Cout * 4u;
-    const unsigned ylane = (unsigned)(m0 + wm * 64 + 4 * h) * rowb + (unsigned)(n0 + wn * 64 + frow) * 4u;
-    const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
-    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(RES ? p.res : p.y, RES ? p.y_bytes : 0u);
-    float sc[2], bi[2];
+    if constexpr (!SHORT) {
+        const unsigned rowb = (unsigned)p.Cout * 4u;
+        const unsigned ylane = (unsigned)(m0 + wm * 64 + 4 * h) * rowb + (unsigned)(n0 + wn * 64 + frow) * 4u;
+        const __amdgpu_buffer_rsrc_t yr = buf_rsrc(p.y, p.y_bytes);
+        const __amdgpu_buffer_rsrc_t rr = buf_rsrc(RES ? p.res : p.y, RES ? p.y_bytes : 0u);
+        float sc[2], bi[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn * 64 + j * 32 + frow;
-        sc[j] = p.scale ? p.scale[n] : 1.f;
-        bi[j] = p.bias ? p.bias[n] : 0.f;
-    }
-    const float lo = p.relu ? 0.f : -INFINITY;
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + wn * 64 + j * 32 + frow;
+            sc[j] = p.scale ? p.scale[n] : 1.f;
+            bi[j] = p.bias ? p.bias[n] : 0.f;
+        }
+        const float lo = p.relu ? 0.f : -INFINITY;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float rs[2][16];
+        for (int i = 0; i < 2; ++i) {
+            float rs[2][16];
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e)
-                rs[j][e] = RES ? buf_load1(rr, ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u) : 0.f;
+                for (int e = 0; e < 16; ++e)
+                    rs[j][e] = RES ? buf_load1(rr, ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u) : 0.f;
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float a = acc[i][j][e] + sml[i][j][e];
-                const float v = fmaxf(a * sc[j] + bi[j] + rs[j][e], lo);
-                buf_store1(yr, ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u, v);
-            }
+                for (int e = 0; e < 16; ++e) {
+                    const float a = acc[i][j][e] + sml[i][j][e];
+                    const float v = fmaxf(a * sc[j] + bi[j] + rs[j][e], lo);
+                    buf_store1(yr, ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * rowb + (unsigned)j * 128u, v);
+                }
+        }
+    } else {                                          // the same expression; operands from in front of the loop, the residual from the ring's LDS
+        if constexpr (RES) {
+            x6_wait_vm<0>();
+            __builtin_amdgcn_s_barrier();             // every wave's pieces of the residual tile have landed
+            asm volatile("" ::: "memory");
+        }
+        const float* resL = smem + (wm * 56 + 4 * h) * 128 + wn * 64 + frow;      // the lane's first element of the residual tile
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float rs[2][16];
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    if constexpr (!RES) rs[j][e] = 0.f;
+                    else rs[j][e] = (i == 1 && e >= 12) ? dres[j][e - 12] : resL[(32 * i + (e & 3) + 8 * (e >> 2)) * 128 + ((j ^ h) << 5)];
+                }
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float a = acc[i][j][e] + sml[i][j][e];
+                    const float v = fmaxf(a * ep.sc[j] + ep.bi[j] + rs[j][e], ep.lo);
+                    buf_store1(ep.yr, ep.ylane + (unsigned)(32 * i + (e & 3) + 8 * (e >> 2)) * ep.rowb + (unsigned)j * 128u, v);
+                }
+        }
     }
 }
 
@@ -248,6 +340,12 @@ template <bool DUAL, bool RES>
 __global__ __launch_bounds__(256, 2) void gemm1x1_bf16x6_kernel(ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     gemm1x1_bf16x6_body<DUAL, RES>(p, smem);
+}
+
+template <bool RES>
+__global__ __launch_bounds__(256, 2) void gemm1x1_bf16x6_short_kernel(ConvParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    gemm1x1_bf16x6_body<false, RES, true>(p, smem);
 }
 
 // ---- filter pack: one thread per 16-byte fragment piece (see the layout above)
@@ -284,11 +382,23 @@ static bool x6_shape_ok(long long M, int K, int K1, int N) {
     return true;
 }
 
-template <bool DUAL, bool RES>
+// The short-K rule, geometry only: stride-1 1x1 layers with 128 <= K < 512, K a multiple of 64 (8 .. 28 stages, a multiple of 4), N >= 512 (narrower layers stay
+// on the row-streaming kernel) and N a multiple of 256 — the widths of the conv3 layers the form was measured on (512, 1024); the kernel itself serves any whole
+// number of 128-wide N tiles, but N = 640 and the like are left to the fp32 kernels until one is measured — and the 32-bit offset guards of x6_shape_ok.
+static bool x6_short_shape_ok(long long M, int K, int N) {
+    if (M < 1 || N < 512 || (N % 256) || K < 128 || K >= 512 || (K % 64)) return false;
+    if ((M + 128) * N >= (1LL << 30) || M * K >= (1LL << 30) || 6LL * N * K >= (1LL << 31)) return false;
+    return true;
+}
+
+template <bool DUAL, bool RES, bool SHORT = false>
 static int launch_x6_impl(const ConvParams& p, hipStream_t st) {
-    auto kern = gemm1x1_bf16x6_kernel<DUAL, RES>;
+    auto kern = [] {
+        if constexpr (SHORT) return gemm1x1_bf16x6_short_kernel<RES>;
+        else return gemm1x1_bf16x6_kernel<DUAL, RES>;
+    }();
     static std::atomic<unsigned> configured{0};
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), X6_BYTES, configured, "gemm1x1_bf16x6")) return rc;
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), X6_BYTES, configured, SHORT ? "gemm1x1_bf16x6_short" : "gemm1x1_bf16x6")) return rc;
     ConvParams q = p;
     q.n_tiles = p.Cout / 128;
     q.m_tiles = cdiv(p.M, 128);
@@ -296,8 +406,8 @@ static int launch_x6_impl(const ConvParams& p, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3((unsigned)(q.m_tiles * q.n_tiles)), dim3(256), X6_BYTES, st, q);
     // six bf16 MFMAs in place of sixteen fp32-MFMA equivalents: the fp32-pipe time the launch occupies
     meter_add(0, (6.0 / 16.0) * 2.0 * ((double)q.m_tiles * 128) * ((double)q.n_tiles * 128) * ((double)q.ktiles * BK));
-    meter_route(kRouteGemm1x1Bf16x6);
-    return check_launch("gemm1x1_bf16x6");
+    meter_route(SHORT ? kRouteGemm1x1Bf16x6Short : kRouteGemm1x1Bf16x6);
+    return check_launch(SHORT ? "gemm1x1_bf16x6_short" : "gemm1x1_bf16x6");
 }
 
 }  // namespace vatl
@@ -315,14 +425,9 @@ extern "C" int vatl_pack_gemm1x1_bf16x6_weight(const float* w, float* u, int N, 
     return check_launch("gemm1x1_bf16x6_pack");
 }
 
-extern "C" int vatl_gemm1x1_bf16x6_supported(int64_t M, int K, int K1, int N) { return x6_shape_ok(M, K, K1, N) ? 1 : 0; }
-
-extern "C" int vatl_gemm1x1_bf16x6_fwd(const float* x, const float* u, const float* scale, const float* bias, const float* residual, float* y,
-                                       int N, int H, int W, int Cin, int Cout, int stride, int relu, void* stream) {
-    if (!x || !u || !y || N <= 0 || H <= 0 || W <= 0) return fail(VATL_EINVAL, "gemm1x1_bf16x6_fwd: null pointer or empty batch");
+static ConvParams x6_plain_params(const float* x, const float* u, const float* scale, const float* bias, const float* residual, float* y,
+                                  int N, int H, int W, int Cin, int Cout, int relu) {
     const long long M = (long long)N * H * W;
-    if (stride != 1 || !x6_shape_ok(M, Cin, 0, Cout))
-        return fail(VATL_EINVAL, "gemm1x1_bf16x6_fwd: %lld x %d -> %d, stride %d is outside stride 1, K %% 64 == 0, K >= 512, N %% 128 == 0 and 32-bit offsets", M, Cin, Cout, stride);
     ConvParams p{};
     p.x = x; p.w = u; p.scale = scale; p.bias = bias; p.res = residual; p.y = y;
     p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.CoutPad = Cout;
@@ -333,7 +438,31 @@ extern "C" int vatl_gemm1x1_bf16x6_fwd(const float* x, const float* u, const flo
     p.kpr = Cin / BK; p.ktiles = p.kpr; p.K = Cin;
     p.x_bytes = (unsigned)(M * Cin * 4); p.y_bytes = (unsigned)(M * Cout * 4); p.w_bytes = (unsigned)(6LL * Cout * Cin);
     p.d_HoWo = make_fastdiv((unsigned)(H * W)); p.d_Wo = make_fastdiv((unsigned)W);
+    return p;
+}
+
+extern "C" int vatl_gemm1x1_bf16x6_supported(int64_t M, int K, int K1, int N) { return x6_shape_ok(M, K, K1, N) ? 1 : 0; }
+
+extern "C" int vatl_gemm1x1_bf16x6_fwd(const float* x, const float* u, const float* scale, const float* bias, const float* residual, float* y,
+                                       int N, int H, int W, int Cin, int Cout, int stride, int relu, void* stream) {
+    if (!x || !u || !y || N <= 0 || H <= 0 || W <= 0) return fail(VATL_EINVAL, "gemm1x1_bf16x6_fwd: null pointer or empty batch");
+    const long long M = (long long)N * H * W;
+    if (stride != 1 || !x6_shape_ok(M, Cin, 0, Cout))
+        return fail(VATL_EINVAL, "gemm1x1_bf16x6_fwd: %lld x %d -> %d, stride %d is outside stride 1, K %% 64 == 0, K >= 512, N %% 128 == 0 and 32-bit offsets", M, Cin, Cout, stride);
+    const ConvParams p = x6_plain_params(x, u, scale, bias, residual, y, N, H, W, Cin, Cout, relu);
     return residual ? launch_x6_impl<false, true>(p, (hipStream_t)stream) : launch_x6_impl<false, false>(p, (hipStream_t)stream);
+}
+
+extern "C" int vatl_gemm1x1_bf16x6_short_supported(int64_t M, int K, int N) { return x6_short_shape_ok(M, K, N) ? 1 : 0; }
+
+extern "C" int vatl_gemm1x1_bf16x6_short_fwd(const float* x, const float* u, const float* scale, const float* bias, const float* residual, float* y,
+                                             int N, int H, int W, int Cin, int Cout, int stride, int relu, void* stream) {
+    if (!x || !u || !y || N <= 0 || H <= 0 || W <= 0) return fail(VATL_EINVAL, "gemm1x1_bf16x6_short_fwd: null pointer or empty batch");
+    const long long M = (long long)N * H * W;
+    if (stride != 1 || !x6_short_shape_ok(M, Cin, Cout))
+        return fail(VATL_EINVAL, "gemm1x1_bf16x6_short_fwd: %lld x %d -> %d, stride %d is outside stride 1, K %% 64 == 0, 128 <= K < 512, N %% 256 == 0, N >= 512 and 32-bit offsets", M, Cin, Cout, stride);
+    const ConvParams p = x6_plain_params(x, u, scale, bias, residual, y, N, H, W, Cin, Cout, relu);
+    return residual ? launch_x6_impl<false, true, true>(p, (hipStream_t)stream) : launch_x6_impl<false, false, true>(p, (hipStream_t)stream);
 }
 
 extern "C" int vatl_gemm1x1_bf16x6_dual_fwd(const float* a, const float* x, const float* u, const float* bias, const float* residual, float* y,

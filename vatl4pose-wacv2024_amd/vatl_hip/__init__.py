@@ -141,6 +141,8 @@ SIGNATURES = {
     "vatl_gemm1x1_bf16x6_supported": (_i, [_i64, _i, _i, _i]),
     "vatl_gemm1x1_bf16x6_fwd": (_i, [_p] * 6 + [_i] * 7 + [_p]),
     "vatl_gemm1x1_bf16x6_dual_fwd": (_i, [_p] * 6 + [_i] * 10 + [_p]),
+    "vatl_gemm1x1_bf16x6_short_supported": (_i, [_i64, _i, _i]),
+    "vatl_gemm1x1_bf16x6_short_fwd": (_i, [_p] * 6 + [_i] * 7 + [_p]),
     "vatl_winograd_deconv_stats_row_blocks": (_i64, [_i64, _i, _i]),
     "vatl_deconv4x4s2_winograd_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_conv2d_fwd_stats": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
@@ -341,7 +343,8 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
 
 ROUTE_NAMES = ("igemm", "igemm_bnbwd", "igemm_dma", "persistent_1x1", "streamk", "rows_1x1", "bottleneck_chain", "stem_pool", "halo_3x3", "winograd",
                "winograd_2h", "winograd_bnbwd", "winograd_persist", "winograd_c32", "wgrad", "winograd_wgrad", "winograd_wgrad_2h", "winograd_wgrad_table", "winograd_f4", "winograd_f4_bnbwd",
-               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43", "stem_pool_w1d", "chain_proj", "chain_step", "gemm1x1_bf16x6")
+               "gemm1x1_ring", "winograd_deconv43", "winograd_s2_43", "stem_pool_w1d", "chain_proj", "chain_step", "gemm1x1_bf16x6",
+               "gemm1x1_bf16x6_short")
 
 
 class flop_meter:
@@ -800,6 +803,11 @@ def gemm1x1_bf16x6_supported(m: int, k: int, k1: int, n: int) -> bool:
     return bool(lib().vatl_gemm1x1_bf16x6_supported(m, k, k1, n))
 
 
+def gemm1x1_bf16x6_short_supported(m: int, k: int, n: int) -> bool:
+    """m rows of a 1x1 / stride-1 layer k -> n on the short-K form of the bf16x6 GEMM (128 <= k < 512, k % 64 == 0, n >= 512, n % 256 == 0; conv1x1_rows_fwd(..., u_x6=))."""
+    return bool(lib().vatl_gemm1x1_bf16x6_short_supported(m, k, n))
+
+
 def conv2d_fwd(x, w_packed, scale, bias, cout: int, r: int, s: int, stride: int, pad: int, relu: bool,
                residual=None, out_nchw: bool = False, out=None, u_s2=None, u_x6=None):
     """Conv2d + folded BN (+ residual) (+ ReLU) of an NHWC tensor on the implicit GEMM — or, when ``u_s2`` (pack_winograd_s2_43_weight) is given and the
@@ -845,10 +853,12 @@ def conv1x1_rows_supported(k1: int, k2: int, n: int, m: int) -> bool:
     return bool(lib().vatl_conv1x1_rows_supported(k1, k2, n, m))
 
 
-def conv1x1_rows_fwd(a, w, scale, bias, cout: int, relu: bool, residual=None, x2=None, out=None, next_conv1=None, y1_out=None):
+def conv1x1_rows_fwd(a, w, scale, bias, cout: int, relu: bool, residual=None, x2=None, out=None, next_conv1=None, y1_out=None, u_x6=None):
     """relu?(scale * (A W^T) + bias + residual) for K = 128 input channels (a (N,H,W,128), or a (N,H,W,64) + x2 (N,H,W,64)); w [cout][128] packed.
     next_conv1 = (w1, scale1, bias1) of the next block's 256 -> 64 conv1 (two-source form only): the same launch also computes
-    y1 = relu(scale1 * (y W1^T) + bias1) from the tile in LDS (vatl_chain_proj_fwd) and the call returns (y, y1)."""
+    y1 = relu(scale1 * (y W1^T) + bias1) from the tile in LDS (vatl_chain_proj_fwd) and the call returns (y, y1).
+    With ``u_x6`` (pack_gemm1x1_bf16x6_weight of w) a single-source call of a shape gemm1x1_bf16x6_short_supported admits runs as six bf16 MFMAs per
+    product (csrc/gemm1x1_bf16x6.hip, the short-K form; same values to fp32 rounding, other bits); every other call ignores ``u_x6``."""
     n, h, w_, k1 = a.shape
     k2 = 0 if x2 is None else x2.shape[-1]
     assert w.numel() >= cout * (k1 + k2) and (x2 is None or tuple(x2.shape[:3]) == (n, h, w_)) and (residual is None or tuple(residual.shape) == (n, h, w_, cout))
@@ -865,6 +875,10 @@ def conv1x1_rows_fwd(a, w, scale, bias, cout: int, relu: bool, residual=None, x2
         _check(lib().vatl_chain_proj_fwd(_ptr(a), _ptr(x2), _ptr(w), _ptr(scale), _ptr(bias), _ptr(y), _ptr(w1), _ptr(scale1), _ptr(bias1), _ptr(y1),
                                          n * h * w_, k1, cout, cnext, int(relu), _stream()), "vatl_chain_proj_fwd")
         return y, y1
+    if u_x6 is not None and x2 is None and gemm1x1_bf16x6_short_supported(n * h * w_, k1, cout):
+        _check(lib().vatl_gemm1x1_bf16x6_short_fwd(_ptr(a), _ptr(u_x6), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n, h, w_, k1, cout, 1, int(relu),
+                                                   _stream()), "vatl_gemm1x1_bf16x6_short_fwd")
+        return y
     _check(lib().vatl_conv1x1_rows_fwd(_ptr(a), _ptr(x2), _ptr(w), _ptr(scale), _ptr(bias), _ptr(residual), _ptr(y), n * h * w_, k1, k2, cout, int(relu),
                                        _stream()), "vatl_conv1x1_rows_fwd")
     return y
