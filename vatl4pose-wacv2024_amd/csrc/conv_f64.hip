@@ -10,7 +10,7 @@
 // Block = 256 threads = 2 x 2 waves, tile 64 pixels x 64 channels, a wave owns 32 x 32 (2 x 2 MFMA tiles).  Both operands are staged
 // through LDS one 16-deep k-tile at a time, the next tile's loads in flight while the current one is multiplied.  MFMA operands (one
 // f64 per lane): A[row lane&15][k lane>>4], B[k lane>>4][col lane&15]; result col lane&15, row (lane>>4) + 4*reg (csrc/kmeans.hip).
-#include "common.h"
+#include "dgrad_phase.h"
 
 namespace vatl {
 
@@ -19,16 +19,9 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 constexpr int kF64BM = 64, kF64BN = 64, kF64BK = 16;
 constexpr int kF64Ld = kF64BM + 2;          // LDS row stride in doubles: the sixteen k-rows a staging store touches fall on different banks
 
-// Geometry of one launch.  Output pixel (n, oy, ox) of the Ho x Wo grid reads input (oy*stride - pad_y + r, ox*stride - pad_x + s) and is
-// stored at (oy*osy + ooy, ox*osx + oox) of an OH x OW plane (a transposed conv's phase writes every other pixel).
-struct ConvF64Geom {
-    long long M;
-    int H, W, Cin, Cout, R, S, stride, pad_y, pad_x, Ho, Wo, OH, OW, osy, osx, ooy, oox, relu, out_nchw;
-};
-
 __global__ __launch_bounds__(256) void conv_f64_kernel(const double* __restrict__ x, const double* __restrict__ w, const double* __restrict__ scale,
                                                        const double* __restrict__ bias, const double* __restrict__ residual, double* __restrict__ y,
-                                                       ConvF64Geom g) {
+                                                       ConvGeom g) {
     __shared__ double As[kF64BK][kF64Ld];
     __shared__ double Bs[kF64BK][kF64Ld];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(256) void conv_f64_kernel(const double* __restrict_
 }
 
 static int launch_conv_f64(const char* what, const double* x, const double* w, const double* scale, const double* bias, const double* residual, double* y,
-                           const ConvF64Geom& g, int N, hipStream_t st) {
+                           const ConvGeom& g, int N, hipStream_t st) {
     if (g.M <= 0) return 0;
     const long long gx = (g.M + kF64BM - 1) / kF64BM;
     if (gx > 0x7FFFFFFFLL || (long long)N * g.OH * g.OW * g.Cout >= (1LL << 40) || (long long)N * g.H * g.W * g.Cin >= (1LL << 40))
@@ -153,12 +146,7 @@ static int launch_conv_f64(const char* what, const double* x, const double* w, c
 __global__ void pack_conv_weight_f64_kernel(const float* __restrict__ src, double* __restrict__ dst, int Cout, int Cin, int R, int S) {
     const long long total = (long long)Cout * R * S * Cin;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % Cin);
-        long long t = i / Cin;
-        const int s = (int)(t % S); t /= S;
-        const int r = (int)(t % R);
-        const long long co = t / R;
-        dst[i] = (double)src[((co * Cin + c) * R + r) * S + s];
+        dst[i] = (double)src[conv_weight_src<false>(i, Cin, Cin, R, S)];
     }
 }
 
@@ -166,17 +154,9 @@ __global__ void pack_conv_weight_f64_kernel(const float* __restrict__ src, doubl
 __global__ void pack_deconv_weight_f64_kernel(const float* __restrict__ src, double* __restrict__ dst, int Cin, int Cout) {
     const long long total = 16LL * Cout * Cin;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % Cin);
-        long long t = i / Cin;
-        const int tx = (int)(t & 1), ty = (int)((t >> 1) & 1); t >>= 2;
-        const int co = (int)(t % Cout);
-        const int ph = (int)(t / Cout);
-        const int ky = 3 - (ph >> 1) - 2 * ty, kx = 3 - (ph & 1) - 2 * tx;
-        dst[i] = (double)src[(((long long)c * Cout + co) * 4 + ky) * 4 + kx];
+        dst[i] = (double)src[deconv_weight_src<false>(i, Cin, Cin, Cout)];
     }
 }
-
-static inline int pack_grid(long long n) { long long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 }  // namespace vatl
 
@@ -197,23 +177,18 @@ extern "C" int vatl_pack_deconv4x4s2_weight_f64(const float* w_iohw, double* w_p
 extern "C" int vatl_conv2d_fwd_f64(const double* x, const double* w, const double* scale, const double* bias, const double* residual, double* y, int N, int H,
                                    int W, int Cin, int Cout, int R, int S, int stride, int pad, int relu, int out_nchw, void* stream) {
     if (!x || !w || !y) return fail(VATL_EINVAL, "conv2d_fwd_f64: null pointer");
-    if (N < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0)
-        return fail(VATL_EINVAL, "conv2d_fwd_f64: N %d, %dx%d, %d -> %d channels, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", N, H, W, Cin,
-                    Cout, R, S, stride, pad);
-    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-    if (H + 2 * pad < R || W + 2 * pad < S) return fail(VATL_EINVAL, "conv2d_fwd_f64: a %dx%d filter does not fit a %dx%d plane with pad %d", R, S, H, W, pad);
-    ConvF64Geom g{(long long)N * Ho * Wo, H, W, Cin, Cout, R, S, stride, pad, pad, Ho, Wo, Ho, Wo, 1, 1, 0, 0, relu != 0, out_nchw != 0};
-    return launch_conv_f64("conv2d_fwd_f64", x, w, scale, bias, residual, y, g, N, (hipStream_t)stream);
+    if (const int rc = conv_shape_contract("conv2d_fwd_f64", "->", false, N, H, W, Cin, Cout, R, S, stride, pad)) return rc;
+    return launch_conv_f64("conv2d_fwd_f64", x, w, scale, bias, residual, y, conv_fwd_geom(N, H, W, Cin, Cout, R, S, stride, pad, relu, out_nchw), N,
+                           (hipStream_t)stream);
 }
 
 extern "C" int vatl_deconv4x4s2_fwd_f64(const double* x, const double* w, const double* scale, const double* bias, double* y, int N, int H, int W, int Cin,
                                         int Cout, int relu, void* stream) {
     if (!x || !w || !y) return fail(VATL_EINVAL, "deconv4x4s2_fwd_f64: null pointer");
     if (N < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return fail(VATL_EINVAL, "deconv4x4s2_fwd_f64: bad shape");
-    for (int ph = 0; ph < 4; ++ph) {                // output (2y+py, 2x+px) = 2x2 taps over inputs (y + py - 1 + ty, x + px - 1 + tx)
-        const int py = ph >> 1, px = ph & 1;
-        ConvF64Geom g{(long long)N * H * W, H, W, Cin, Cout, 2, 2, 1, 1 - py, 1 - px, H, W, 2 * H, 2 * W, 2, 2, py, px, relu != 0, 0};
-        const int rc = launch_conv_f64("deconv4x4s2_fwd_f64", x, w + (long long)ph * Cout * 4 * Cin, scale, bias, nullptr, y, g, N, (hipStream_t)stream);
+    for (int ph = 0; ph < 4; ++ph) {
+        const int rc = launch_conv_f64("deconv4x4s2_fwd_f64", x, w + (long long)ph * Cout * 4 * Cin, scale, bias, nullptr, y,
+                                       deconv_phase_geom(N, H, W, Cin, Cout, ph, relu), N, (hipStream_t)stream);
         if (rc) return rc;
     }
     return 0;
@@ -225,8 +200,6 @@ extern "C" int vatl_deconv4x4s2_fwd_f64(const double* x, const double* w, const 
 // launch per input-pixel phase that writes every other pixel (phase geometry: dgrad_phase.h).  The skip gradient of a bottleneck
 // rides in the write-out's residual.  The data gradient of ConvTranspose2d(4,2,1) needs nothing new: it is vatl_conv2d_fwd_f64
 // (4x4, stride 2, pad 1) of dz with vatl_pack_conv_weight_f64 applied to the (Cin,Cout,4,4) parameter as if it were OIHW.
-#include "dgrad_phase.h"
-
 namespace vatl {
 
 // OIHW fp32 -> the phases one after the other, each [Cin][ty][tx][Cout] float64 (exact): the kernel's [rows][K] filter with rows = Cin
@@ -237,13 +210,7 @@ __global__ void pack_dgrad_weight_f64_kernel(const float* __restrict__ src, doub
         double* out = dst + dgrad_phase_offset(R, S, stride, pad, phase, cc);
         const long long total = cc * ay.taps * ax.taps;
         for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-            const int co = (int)(i % Cout);
-            long long t = i / Cout;
-            const int tx = (int)(t % ax.taps); t /= ax.taps;
-            const int ty = (int)(t % ay.taps);
-            const int ci = (int)(t / ay.taps);
-            const int r = ay.r0 - stride * ty, s = ax.r0 - stride * tx;
-            out[i] = (double)src[(((long long)co * Cin + ci) * R + r) * S + s];
+            out[i] = (double)src[dgrad_weight_src<false>(i, ay, ax, Cout, Cin, Cout, R, S, stride)];
         }
     }
 }
@@ -276,29 +243,18 @@ extern "C" int vatl_conv2d_dgrad_f64(const double* dz, const double* w_dgrad, co
                                      int S, int stride, int pad, void* stream) {
     const char* what = "conv2d_dgrad_f64";
     if (!dz || !w_dgrad || !dx) return fail(VATL_EINVAL, "%s: null pointer", what);
-    if (N < 0 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0 || H + 2 * pad < R ||
-        W + 2 * pad < S)
-        return fail(VATL_EINVAL, "%s: N %d, %dx%d, %d <- %d channels, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", what, N, H, W, Cin, Cout, R, S,
-                    stride, pad);
+    if (const int rc = conv_shape_contract(what, "<-", true, N, H, W, Cin, Cout, R, S, stride, pad)) return rc;
     if (N == 0) return 0;
-    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-    const long long cc = (long long)Cin * Cout;
     for (int phase = 0; phase < stride * stride; ++phase) {
-        const int py = phase / stride, px = phase % stride;
-        const int Hp = H > py ? (H - py + stride - 1) / stride : 0, Wp = W > px ? (W - px + stride - 1) / stride : 0;
-        if (Hp == 0 || Wp == 0) continue;
-        const DgradAxis ay = dgrad_axis(R, stride, pad, py), ax = dgrad_axis(S, stride, pad, px);
-        if (ay.taps == 0 || ax.taps == 0) {
-            hipLaunchKernelGGL(dgrad_fill_phase_f64_kernel, dim3(pack_grid((long long)N * Hp * Wp * Cin)), dim3(256), 0, (hipStream_t)stream, residual, dx,
-                               (long long)N, H, W, Cin, stride, py, px, Hp, Wp);
+        const DgradPhase p = dgrad_phase_geom(N, H, W, Cin, Cout, R, S, stride, pad, phase);
+        if (p.Hp == 0 || p.Wp == 0) continue;
+        if (p.ay.taps == 0 || p.ax.taps == 0) {
+            hipLaunchKernelGGL(dgrad_fill_phase_f64_kernel, dim3(pack_grid((long long)N * p.Hp * p.Wp * Cin)), dim3(256), 0, (hipStream_t)stream, residual, dx,
+                               (long long)N, H, W, Cin, stride, p.py, p.px, p.Hp, p.Wp);
             if (const int rc = check_launch(what)) return rc;
             continue;
         }
-        // roles on the kernel: dz is the input (Cout channels on an Ho x Wo plane), dx the output (Cin channels), written at (stride*j + py, stride*i + px)
-        ConvF64Geom g{(long long)N * Hp * Wp, Ho, Wo, Cout, Cin, ay.taps, ax.taps, 1, ay.pad, ax.pad, Hp, Wp, H, W, stride, stride, py, px, 0, 0};
-        if (const int rc = launch_conv_f64(what, dz, w_dgrad + dgrad_phase_offset(R, S, stride, pad, phase, cc), nullptr, nullptr, residual, dx, g, N,
-                                           (hipStream_t)stream))
-            return rc;
+        if (const int rc = launch_conv_f64(what, dz, w_dgrad + p.w_off, nullptr, nullptr, residual, dx, p.g, N, (hipStream_t)stream)) return rc;
     }
     return 0;
 }

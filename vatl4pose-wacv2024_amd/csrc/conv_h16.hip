@@ -28,17 +28,10 @@ namespace vatl {
 constexpr int kH16BM = 128, kH16BK = 64;
 constexpr int kH16Ld = kH16BK + 8;              // LDS row stride in elements (144 bytes)
 
-// Geometry of one launch.  Output pixel (n, oy, ox) of the Ho x Wo grid reads input (oy*stride - pad_y + r, ox*stride - pad_x + s) and is
-// stored at (oy*osy + ooy, ox*osx + oox) of an OH x OW plane (a transposed conv's phase writes every other pixel).
-struct ConvH16Geom {
-    long long M;
-    int H, W, Cin, Cout, R, S, stride, pad_y, pad_x, Ho, Wo, OH, OW, osy, osx, ooy, oox, relu, out_f32_nchw;
-};
-
 template <typename T, int BN>
 __global__ __launch_bounds__(256) void conv_h16_kernel(const unsigned short* __restrict__ x, const unsigned short* __restrict__ w,
                                                        const float* __restrict__ scale, const float* __restrict__ bias,
-                                                       const unsigned short* __restrict__ residual, void* __restrict__ y, ConvH16Geom g) {
+                                                       const unsigned short* __restrict__ residual, void* __restrict__ y, ConvGeom g) {
     constexpr int NB = BN / 32;                 // filters staged per thread
     constexpr int CT = BN / 32, PT = 4;         // 16 x 16 MFMA tiles of a wave: channels x pixels
     constexpr int HB = BN / 2;                  // channels of a wave
@@ -157,7 +150,7 @@ __global__ __launch_bounds__(256) void conv_h16_kernel(const unsigned short* __r
             const float sc = scale && in ? scale[cbase + e] : 1.f, bi = bias && in ? bias[cbase + e] : 0.f;
             v[e] = fmaf(acc[e >> 2][b][e & 3], sc, bi);
         }
-        if (g.out_f32_nchw) {
+        if (g.out_nchw) {
             float* yf = reinterpret_cast<float*>(y);
 #pragma unroll
             for (int e = 0; e < 4 * CT; ++e) {
@@ -188,7 +181,7 @@ __global__ __launch_bounds__(256) void conv_h16_kernel(const unsigned short* __r
 }
 
 template <typename T>
-static void launch_conv_h16_t(const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y, const ConvH16Geom& g,
+static void launch_conv_h16_t(const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y, const ConvGeom& g,
                               hipStream_t st) {
     const unsigned gx = (unsigned)((g.M + kH16BM - 1) / kH16BM);
     const unsigned short *xs = (const unsigned short*)x, *ws = (const unsigned short*)w, *rs = (const unsigned short*)residual;
@@ -199,7 +192,7 @@ static void launch_conv_h16_t(const void* x, const void* w, const float* scale, 
 }
 
 static int launch_conv_h16(const char* what, const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y,
-                           const ConvH16Geom& g, int N, int dtype, hipStream_t st) {
+                           const ConvGeom& g, int N, int dtype, hipStream_t st) {
     if (g.M <= 0) return 0;
     const long long gx = (g.M + kH16BM - 1) / kH16BM;
     if (gx > 0x7FFFFFFFLL || (long long)N * g.OH * g.OW * g.Cout >= (1LL << 40) || (long long)N * g.H * g.W * g.Cin >= (1LL << 40))
@@ -227,12 +220,8 @@ template <typename T>
 __global__ void pack_conv_weight_h16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int Cout, int Cin, int Cin8, int R, int S) {
     const long long total = (long long)Cout * R * S * Cin8;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % Cin8);
-        long long t = i / Cin8;
-        const int s = (int)(t % S); t /= S;
-        const int r = (int)(t % R);
-        const long long co = t / R;
-        dst[i] = c < Cin ? T::from_f32(src[((co * Cin + c) * R + r) * S + s]) : (unsigned short)0;
+        const long long j = conv_weight_src<true>(i, Cin, Cin8, R, S);
+        dst[i] = j >= 0 ? T::from_f32(src[j]) : (unsigned short)0;
     }
 }
 
@@ -241,20 +230,13 @@ template <typename T>
 __global__ void pack_deconv_weight_h16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int Cin, int Cin8, int Cout) {
     const long long total = 16LL * Cout * Cin8;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % Cin8);
-        long long t = i / Cin8;
-        const int tx = (int)(t & 1), ty = (int)((t >> 1) & 1); t >>= 2;
-        const int co = (int)(t % Cout);
-        const int ph = (int)(t / Cout);
-        const int ky = 3 - (ph >> 1) - 2 * ty, kx = 3 - (ph & 1) - 2 * tx;
-        dst[i] = c < Cin ? T::from_f32(src[(((long long)c * Cout + co) * 4 + ky) * 4 + kx]) : (unsigned short)0;
+        const long long j = deconv_weight_src<true>(i, Cin, Cin8, Cout);
+        dst[i] = j >= 0 ? T::from_f32(src[j]) : (unsigned short)0;
     }
 }
 
-static inline int pack_grid_h16(long long n) { long long b = (n + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
-
 // DATA GRADIENT of the bf16 fine-tune step: dx = conv(dz, filter with the two channel counts exchanged), on conv_h16_kernel as it is.
-// The phase geometry (DgradAxis, dgrad_axis, dgrad_phase_offset) is dgrad_phase.h, shared with the float64 reference.
+// The phase geometry (dgrad_phase.h) is shared with the float64 reference.
 template <typename T>
 __global__ void pack_dgrad_weight_h16_kernel(const float* __restrict__ src, unsigned short* __restrict__ dst, int Cout, int Cin, int Cout8, int Cin8, int R, int S,
                                              int stride, int pad) {
@@ -264,13 +246,8 @@ __global__ void pack_dgrad_weight_h16_kernel(const float* __restrict__ src, unsi
         unsigned short* out = dst + dgrad_phase_offset(R, S, stride, pad, phase, cc);
         const long long total = cc * ay.taps * ax.taps;
         for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-            const int co = (int)(i % Cout8);
-            long long t = i / Cout8;
-            const int tx = (int)(t % ax.taps); t /= ax.taps;
-            const int ty = (int)(t % ay.taps);
-            const int ci = (int)(t / ay.taps);
-            const int r = ay.r0 - stride * ty, s = ax.r0 - stride * tx;
-            out[i] = (co < Cout && ci < Cin) ? T::from_f32(src[(((long long)co * Cin + ci) * R + r) * S + s]) : (unsigned short)0;
+            const long long j = dgrad_weight_src<true>(i, ay, ax, Cout, Cin, Cout8, R, S, stride);
+            out[i] = j >= 0 ? T::from_f32(src[j]) : (unsigned short)0;
         }
     }
 }
@@ -296,46 +273,35 @@ using namespace vatl;
 extern "C" int vatl_pack_conv_weight_h16(const float* w_oihw, void* w_packed, int Cout, int Cin, int R, int S, int dtype, void* stream) {
     if (!w_oihw || !w_packed || Cout < 1 || Cin < 1 || R < 1 || S < 1 || !h16_dtype_ok(dtype)) return fail(VATL_EINVAL, "pack_conv_weight_h16: bad arguments");
     const int Cin8 = (Cin + 7) & ~7;
-    const dim3 grid(pack_grid_h16((long long)Cout * Cin8 * R * S));
-    if (dtype == kH16F16)
-        hipLaunchKernelGGL(pack_conv_weight_h16_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cin8, R, S);
-    else
-        hipLaunchKernelGGL(pack_conv_weight_h16_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cin8, R, S);
+    const auto kernel = dtype == kH16F16 ? pack_conv_weight_h16_kernel<F16> : pack_conv_weight_h16_kernel<BF16>;
+    hipLaunchKernelGGL(kernel, dim3(pack_grid((long long)Cout * Cin8 * R * S)), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cin8, R,
+                       S);
     return check_launch("pack_conv_weight_h16");
 }
 
 extern "C" int vatl_pack_deconv4x4s2_weight_h16(const float* w_iohw, void* w_packed, int Cin, int Cout, int dtype, void* stream) {
     if (!w_iohw || !w_packed || Cout < 1 || Cin < 1 || !h16_dtype_ok(dtype)) return fail(VATL_EINVAL, "pack_deconv4x4s2_weight_h16: bad arguments");
     const int Cin8 = (Cin + 7) & ~7;
-    const dim3 grid(pack_grid_h16(16LL * Cout * Cin8));
-    if (dtype == kH16F16)
-        hipLaunchKernelGGL(pack_deconv_weight_h16_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, w_iohw, (unsigned short*)w_packed, Cin, Cin8, Cout);
-    else
-        hipLaunchKernelGGL(pack_deconv_weight_h16_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, w_iohw, (unsigned short*)w_packed, Cin, Cin8, Cout);
+    const auto kernel = dtype == kH16F16 ? pack_deconv_weight_h16_kernel<F16> : pack_deconv_weight_h16_kernel<BF16>;
+    hipLaunchKernelGGL(kernel, dim3(pack_grid(16LL * Cout * Cin8)), dim3(256), 0, (hipStream_t)stream, w_iohw, (unsigned short*)w_packed, Cin, Cin8, Cout);
     return check_launch("pack_deconv4x4s2_weight_h16");
 }
 
 extern "C" int vatl_conv2d_fwd_h16(const void* x, const void* w, const float* scale, const float* bias, const void* residual, void* y, int N, int H, int W,
                                    int Cin, int Cout, int R, int S, int stride, int pad, int relu, int out_f32_nchw, int dtype, void* stream) {
     if (const int rc = conv_h16_contract("conv2d_fwd_h16", x, w, residual, y, Cin, Cout, out_f32_nchw != 0, dtype)) return rc;
-    if (N < 0 || H < 1 || W < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0)
-        return fail(VATL_EINVAL, "conv2d_fwd_h16: N %d, %dx%d, %d -> %d channels, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", N, H, W, Cin,
-                    Cout, R, S, stride, pad);
-    if (H + 2 * pad < R || W + 2 * pad < S) return fail(VATL_EINVAL, "conv2d_fwd_h16: a %dx%d filter does not fit a %dx%d plane with pad %d", R, S, H, W, pad);
-    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-    ConvH16Geom g{(long long)N * Ho * Wo, H, W, Cin, Cout, R, S, stride, pad, pad, Ho, Wo, Ho, Wo, 1, 1, 0, 0, relu != 0, out_f32_nchw != 0};
-    return launch_conv_h16("conv2d_fwd_h16", x, w, scale, bias, residual, y, g, N, dtype, (hipStream_t)stream);
+    if (const int rc = conv_shape_contract("conv2d_fwd_h16", "->", false, N, H, W, Cin, Cout, R, S, stride, pad)) return rc;
+    return launch_conv_h16("conv2d_fwd_h16", x, w, scale, bias, residual, y, conv_fwd_geom(N, H, W, Cin, Cout, R, S, stride, pad, relu, out_f32_nchw), N, dtype,
+                           (hipStream_t)stream);
 }
 
 extern "C" int vatl_deconv4x4s2_fwd_h16(const void* x, const void* w, const float* scale, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
                                         int relu, int dtype, void* stream) {
     if (const int rc = conv_h16_contract("deconv4x4s2_fwd_h16", x, w, nullptr, y, Cin, Cout, 0, dtype)) return rc;
     if (N < 0 || H < 1 || W < 1) return fail(VATL_EINVAL, "deconv4x4s2_fwd_h16: bad shape");
-    for (int ph = 0; ph < 4; ++ph) {                // output (2y+py, 2x+px) = 2x2 taps over inputs (y + py - 1 + ty, x + px - 1 + tx)
-        const int py = ph >> 1, px = ph & 1;
-        ConvH16Geom g{(long long)N * H * W, H, W, Cin, Cout, 2, 2, 1, 1 - py, 1 - px, H, W, 2 * H, 2 * W, 2, 2, py, px, relu != 0, 0};
-        const int rc = launch_conv_h16("deconv4x4s2_fwd_h16", x, (const unsigned short*)w + (long long)ph * Cout * 4 * Cin, scale, bias, nullptr, y, g, N, dtype,
-                                       (hipStream_t)stream);
+    for (int ph = 0; ph < 4; ++ph) {
+        const int rc = launch_conv_h16("deconv4x4s2_fwd_h16", x, (const unsigned short*)w + (long long)ph * Cout * 4 * Cin, scale, bias, nullptr, y,
+                                       deconv_phase_geom(N, H, W, Cin, Cout, ph, relu), N, dtype, (hipStream_t)stream);
         if (rc) return rc;
     }
     return 0;
@@ -345,13 +311,9 @@ extern "C" int vatl_pack_conv_weight_dgrad_h16(const float* w_oihw, void* w_pack
     if (!w_oihw || !w_packed || Cout < 1 || Cin < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0 || !h16_dtype_ok(dtype))
         return fail(VATL_EINVAL, "pack_conv_weight_dgrad_h16: bad arguments");
     const int Cin8 = (Cin + 7) & ~7, Cout8 = (Cout + 7) & ~7;
-    const dim3 grid(pack_grid_h16((long long)Cin8 * Cout8 * R * S));
-    if (dtype == kH16F16)
-        hipLaunchKernelGGL(pack_dgrad_weight_h16_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cout8, Cin8, R, S,
-                           stride, pad);
-    else
-        hipLaunchKernelGGL(pack_dgrad_weight_h16_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cout8, Cin8, R, S,
-                           stride, pad);
+    const auto kernel = dtype == kH16F16 ? pack_dgrad_weight_h16_kernel<F16> : pack_dgrad_weight_h16_kernel<BF16>;
+    hipLaunchKernelGGL(kernel, dim3(pack_grid((long long)Cin8 * Cout8 * R * S)), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)w_packed, Cout, Cin, Cout8,
+                       Cin8, R, S, stride, pad);
     return check_launch("pack_conv_weight_dgrad_h16");
 }
 
@@ -360,26 +322,20 @@ extern "C" int vatl_conv2d_dgrad_h16(const void* dz, const void* w_dgrad, const 
     const char* what = "conv2d_dgrad_h16";
     // roles on the kernel: dz is the input (Cout8 channels), dx the output (Cin8 channels)
     if (const int rc = conv_h16_contract(what, dz, w_dgrad, residual, dx, Cout8, Cin8, 0, dtype)) return rc;
-    if (N < 0 || H < 1 || W < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0 || H + 2 * pad < R || W + 2 * pad < S)
-        return fail(VATL_EINVAL, "%s: N %d, %dx%d, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", what, N, H, W, R, S, stride, pad);
+    if (const int rc = conv_shape_contract(what, nullptr, true, N, H, W, Cin8, Cout8, R, S, stride, pad)) return rc;
     if (N == 0) return 0;
-    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - S) / stride + 1;
-    const long long cc = (long long)Cin8 * Cout8;
     for (int phase = 0; phase < stride * stride; ++phase) {
-        const int py = phase / stride, px = phase % stride;
-        const int Hp = H > py ? (H - py + stride - 1) / stride : 0, Wp = W > px ? (W - px + stride - 1) / stride : 0;
-        if (Hp == 0 || Wp == 0) continue;
-        const DgradAxis ay = dgrad_axis(R, stride, pad, py), ax = dgrad_axis(S, stride, pad, px);
-        if (ay.taps == 0 || ax.taps == 0) {
-            const long long total = (long long)N * Hp * Wp * (Cin8 >> 3);
-            hipLaunchKernelGGL(dgrad_fill_phase_h16_kernel, dim3(pack_grid_h16(total)), dim3(256), 0, (hipStream_t)stream, (const uint4*)residual, (uint4*)dx,
-                               (long long)N, H, W, Cin8 >> 3, stride, py, px, Hp, Wp);
+        const DgradPhase p = dgrad_phase_geom(N, H, W, Cin8, Cout8, R, S, stride, pad, phase);
+        if (p.Hp == 0 || p.Wp == 0) continue;
+        if (p.ay.taps == 0 || p.ax.taps == 0) {
+            const long long total = (long long)N * p.Hp * p.Wp * (Cin8 >> 3);
+            hipLaunchKernelGGL(dgrad_fill_phase_h16_kernel, dim3(pack_grid(total)), dim3(256), 0, (hipStream_t)stream, (const uint4*)residual, (uint4*)dx,
+                               (long long)N, H, W, Cin8 >> 3, stride, p.py, p.px, p.Hp, p.Wp);
             if (const int rc = check_launch(what)) return rc;
             continue;
         }
-        ConvH16Geom g{(long long)N * Hp * Wp, Ho, Wo, Cout8, Cin8, ay.taps, ax.taps, 1, ay.pad, ax.pad, Hp, Wp, H, W, stride, stride, py, px, 0, 0};
-        const unsigned short* wp = (const unsigned short*)w_dgrad + dgrad_phase_offset(R, S, stride, pad, phase, cc);
-        if (const int rc = launch_conv_h16(what, dz, wp, nullptr, nullptr, residual, dx, g, N, dtype, (hipStream_t)stream)) return rc;
+        if (const int rc = launch_conv_h16(what, dz, (const unsigned short*)w_dgrad + p.w_off, nullptr, nullptr, residual, dx, p.g, N, dtype, (hipStream_t)stream))
+            return rc;
     }
     return 0;
 }
