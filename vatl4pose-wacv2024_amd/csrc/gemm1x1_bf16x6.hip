@@ -24,28 +24,42 @@ namespace vatl {
 //    (n-tile, stage) 12 KB = [plane 3][column block 4][lane 64] x 16 bytes, lane l of column block jb holding piece `plane` of
 //    W[128 n_tile + 32 jb + (l & 31)][16 stage + 8 (l >> 5) + 0 .. 7].  The DMA copies it linearly, a fragment is one ds_read_b128 at
 //    lane * 16: conflict-free, no swizzle.
-//  * a stage is 16 k = 8 KB of A + 12 KB of B, a ring of four is 80 KB per block, two blocks per CU: the vector work of one block's
-//    wave (the split) runs under the MFMAs of the other block's wave on the same SIMD.  Per stage and wave 24 MFMAs, five DMA
+//  * a stage is 16 k = 8 KB of A + 12 KB of B, a ring of four is 80 KB per block, two blocks per CU.  Per stage and wave 24 MFMAs, five DMA
 //    requests, one counted s_waitcnt, one barrier.
+//  * the k-loop is software-pipelined inside the wave: iteration s issues the 24 MFMAs of stage s from registers (A pieces and B fragments, two
+//    sets) and, between them, reads the fragments of stage s + 1 from the ring and splits its A values into the other set: the split's 88 vector
+//    instructions stand five to an MFMA gap, where they cost nothing (tools/probes/mfma_valu_overlap.hip), not in front of the MFMAs.
+//    Ring discipline: behind the barrier of iteration s every wave's pieces of stage s + 1 have landed, and slot s % 4 is free — its fragments went
+//    into registers in iteration s - 1, and the counted wait in front of the barrier also waits for those LDS reads (lgkmcnt(0)) — so the request of
+//    stage s + 4 goes there.  Counted waits (per wave, oldest first; five requests a stage, VMEM retires in order):
+//      prologue      [0, 1, 2, 3]                    vmcnt(15): stage 0 landed; barrier; stage 0 into set 0
+//      s <= S-5      [s+1, s+2, s+3]                 vmcnt(10): stage s + 1 landed; barrier; then the request of stage s + 4
+//      s  = S-4      [S-3, S-2, S-1]                 vmcnt(10); no request left
+//      s  = S-3      [S-2, S-1]                      vmcnt(5)
+//      s  = S-2      [S-1]                           vmcnt(0)
+//      s  = S-1      nothing to read: MFMAs only, no wait, no barrier
+//    Dual source: S1 = 2 k1 is a multiple of 4 (x6_shape_ok), so the four requests of a group of iterations s .. s + 3 (stages s + 4 .. s + 7) read one
+//    source: x while s + 4 < S1, else x2.  The prologue's four stages read x (S1 >= 4).  The counts do not change at the crossing.
 //  * the residual is read in the write-out, after the two accumulator sets are added (the registers the ring kernel keeps it in hold
 //    the second set here).
 // Arithmetic per output row depends on that row's inputs and the filter only: the same bits alone and in any batch position.
 // Tail rows read row M-1; their stores lie past the descriptor and are dropped.  No atomics, no split-K.
-// Dual source: stages 0 .. 2 k1 - 1 read x, the rest x2 at the row's strided pixel (the ring kernel's rules).
+// Dual source: stages 0 .. S1 - 1 = 2 k1 - 1 read x, the rest x2 at the row's strided pixel (the ring kernel's rules).
 //
 // SHORT (128 <= K < 512, N >= 512: conv3 of ResNet stages 2 and 3; gemm1x1_bf16x6_short_kernel): the same loop, products and order — 8 to 28
 // stages — with the per-tile cost that a long loop hides taken out of the tail:
 //  * scale, bias and the write-out addresses are loaded / computed in front of the k-loop;
-//  * the residual tile is requested by LDS-DMA into the ring slots that fall free at the tail: stages S-3, S-2 and S-1 issue no operand
-//    requests, so slot (s - 1) % 4 is free from the barrier of each of them on — 60 KB.  The 64 KB tile less the last eight rows of
+//  * the residual tile is requested by LDS-DMA into the ring slots that fall free at the tail: iterations S-4 .. S-1 issue no operand requests, so
+//    slot s % 4 is free from the barrier of iterations S-4, S-3 and S-2 on — 60 KB.  The 64 KB tile less the last eight rows of
 //    either wave row (56 KB: compact row cr = 56 wm + lr, lr < 56, 512 bytes each, linear from the ring's base) goes there in 5 + 5 + 4
 //    requests per wave, the 2 x 4 elements a lane owns of the other eight rows are loaded into registers in front of the loop.  The
 //    write-out reads the tile with ds_read_b32 (16-byte chunk c of row cr sits at position c ^ 8 ((cr >> 2) & 1): the two half-waves
-//    of a read, four rows apart, take opposite halves of the 64 banks).  The residual's HBM round trip thus runs under the last three
-//    stages' MFMAs.  Counted waits of the tail (per wave, oldest first): S-3: [S-3, S-2, S-1] -> vmcnt(10), then R0 (5); S-2: [S-2, S-1, R0]
-//    -> vmcnt(10), then R1 (5); S-1: [S-1, R0, R1] -> vmcnt(10), then R2 (4); after the loop vmcnt(0) and one barrier.  The register
+//    of a read, four rows apart, take opposite halves of the 64 banks).  The residual's HBM round trip thus runs under the last four
+//    iterations' MFMAs.  Counted waits of the tail (per wave, oldest first): S-4: [S-3, S-2, S-1] -> vmcnt(10), then R0 (5); S-3: [S-2, S-1, R0]
+//    -> vmcnt(10), then R1 (5); S-2: [S-1, R0, R1] -> vmcnt(10), then R2 (4); S-1: none; after the loop vmcnt(0) and one barrier.  The register
 //    loads and the scale / bias loads in front of the loop share the counter: wherever the compiler puts them among the first requests, an
-//    operation younger than stage s's pieces can only make a counted wait stricter (vmcnt(N) leaves at most the N youngest outstanding).
+//    operation younger than stage s + 1's pieces can only make a counted wait stricter (vmcnt(N) leaves at most the N youngest outstanding), and
+//    an older one has retired before them.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int X6_BK = 16;                             // k per stage
 constexpr int X6_NS = 4;                              // stages in the ring
@@ -57,11 +71,12 @@ constexpr int X6_BYTES = X6_NS * X6_STAGE * (int)sizeof(float);
 typedef __bf16 x6_bf16x8 __attribute__((ext_vector_type(8)));
 
 template <int N>
-__device__ __forceinline__ void x6_wait_vm() {       // s_waitcnt vmcnt(N), N a compile-time count of this wave's younger DMA requests
-    static_assert(N == 0 || N == 5 || N == 10, "add the count here");
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+__device__ __forceinline__ void x6_wait_vm() {       // s_waitcnt vmcnt(N), N a compile-time count of this wave's younger DMA requests; and every LDS read of
+    static_assert(N == 0 || N == 5 || N == 10 || N == 15, "add the count here");     // the iteration before is done before the barrier that frees its slot
+    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)" ::: "memory");
+    else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(15) lgkmcnt(0)" ::: "memory");
 }
 
 __device__ __forceinline__ f32x16 x6_mfma(u32x4 a, u32x4 b, f32x16 c) {
@@ -185,95 +200,134 @@ __device__ __forceinline__ void gemm1x1_bf16x6_body(const ConvParams& p, float* 
 #pragma unroll
             for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; sml[i][j][e] = 0.f; }
 
-    // One stage.  KIND 0: steady state (stages s+1, s+2 in flight behind s: vmcnt(10)), then the request of stage s+3 into the slot every
-    // wave finished reading before this barrier (stage s-1's); 1: s = S-3, nothing left to request; 2: s = S-2 (stage S-1 younger);
-    // 3: s = S-1.  VMEM operations retire in order, so each count waits for this wave's pieces of stage s exactly.
-    auto stage = [&](auto slot, auto kind, auto src, int s) {
-        constexpr int B = decltype(slot)::value, KIND = decltype(kind)::value;
-        if constexpr (KIND <= 1 || LDSRES) x6_wait_vm<10>();      // (LDSRES: the tail's residual requests keep two pieces behind stage s, see above)
-        else if constexpr (KIND == 2) x6_wait_vm<5>();
-        else x6_wait_vm<0>();
-        __builtin_amdgcn_s_barrier();                 // every wave's pieces of stage s have landed; every wave is done reading slot (s - 1) % 4
-        asm volatile("" ::: "memory");
-        f32x4 af[2][2];
-        u32x4 bw[3][2];
+    // Operands in registers, two sets (set = stage & 1): the A pieces pa[set][piece][i] and the B fragments bw[set][plane][j].
+    u32x4 pa[2][3][2], bw[2][3][2];
+    auto read_a = [&](auto slot, f32x4 (&af)[2][2]) {
+        constexpr int B = decltype(slot)::value;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int c = 0; c < 2; ++c) af[i][c] = *reinterpret_cast<const f32x4*>(Ard[c] + B * X6_STAGE + i * 32 * X6_BK);
+    };
+    auto read_b = [&](auto slot, int pl, u32x4 (&b)[3][2]) {
+        constexpr int B = decltype(slot)::value;
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) bw[pl][j] = *reinterpret_cast<const u32x4*>(Brd + B * X6_STAGE + (4 * pl + j) * 256);
-        if constexpr (KIND == 0) issue(src, (B + 3) & 3, s + 3);
-        else if constexpr (LDSRES) issue_res(std::integral_constant<int, KIND - 1>{});      // into slot B - 1 = KIND - 1 (S % 4 == 0)
-        // the split (split16.h): fragment dword d = k pair (2d, 2d + 1) of the lane's eight
-        u32x4 a0[2], a1[2], a2[2];
+        for (int j = 0; j < 2; ++j) b[pl][j] = *reinterpret_cast<const u32x4*>(Brd + B * X6_STAGE + (4 * pl + j) * 256);
+    };
+    auto split = [&](const f32x4 (&af)[2][2], u32x4 (&q)[3][2]) {       // split16.h: fragment dword d = k pair (2d, 2d + 1) of the lane's eight
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 const split16::Pieces e = split16::split3(af[i][d >> 1][(2 * d) & 3]), o = split16::split3(af[i][d >> 1][(2 * d + 1) & 3]);
-                a0[i][d] = split16::pack_pair(e.hi, o.hi);
-                a1[i][d] = split16::pack_pair(e.mid, o.mid);
-                a2[i][d] = split16::pack_pair(e.lo, o.lo);
+                q[0][i][d] = split16::pack_pair(e.hi, o.hi);
+                q[1][i][d] = split16::pack_pair(e.mid, o.mid);
+                q[2][i][d] = split16::pack_pair(e.lo, o.lo);
             }
+    };
+
+    // One iteration: the 24 MFMAs of stage s from the registers of set s & 1, and between them everything stage s + 1 needs to be in the other set.
+    // KIND 0: steady state; 1: s = S-4, 2: s = S-3, 3: s = S-2 (nothing left to request); 4: s = S-1 (nothing left to read: MFMAs only, no barrier).
+    // Instruction order (sched_group_barrier; the scheduler is free only inside a group): MFMA | the four A reads and the plane-0 B reads of stage s + 1 |
+    // then 23 times one MFMA and either one DMA request (the first five gaps of an iteration that has requests) or five of the split's 88 instructions;
+    // the plane-1 / plane-2 B reads of stage s + 1 follow the 16th / 20th MFMA, the last that reads those registers for stage s.  No split instruction
+    // stands in front of the first two MFMAs: the A reads' latency runs under them.  (tools/probes/mfma_valu_overlap.hip: up to five of these per gap of
+    // this MFMA cost nothing, in front of the MFMAs they cost 352 cycles; profiles/bf16x6_pipe_notes.md: one request per gap beats five in one gap.)
+    auto stage = [&](auto slot, auto kind, auto src, int s) {
+        constexpr int B = decltype(slot)::value, KIND = decltype(kind)::value, CUR = B & 1, NXT = CUR ^ 1;
+        using Next = std::integral_constant<int, (B + 1) & 3>;
+        f32x4 af[2][2];
+        if constexpr (KIND <= 3) {
+            if constexpr (KIND <= 1 || LDSRES) x6_wait_vm<10>();  // (LDSRES: the tail's residual requests keep two pieces behind stage s + 1, see above)
+            else if constexpr (KIND == 2) x6_wait_vm<5>();
+            else x6_wait_vm<0>();
+            __builtin_amdgcn_s_barrier();             // every wave's pieces of stage s + 1 have landed; every wave has read slot s % 4 into registers
+            asm volatile("" ::: "memory");
+            read_a(Next{}, af);
+            read_b(Next{}, 0, bw[NXT]);
+            if constexpr (KIND == 0) issue(src, B, s + 4);
+            else if constexpr (LDSRES) issue_res(std::integral_constant<int, KIND - 1>{});      // into slot B = KIND - 1 (S % 4 == 0)
+        }
+        auto& a = pa[CUR];
+        auto& b = bw[CUR];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = x6_mfma(a0[i], bw[0][j], acc[i][j]);
+            for (int j = 0; j < 2; ++j) acc[i][j] = x6_mfma(a[0][i], b[0][j], acc[i][j]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a0[i], bw[1][j], sml[i][j]);
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a[0][i], b[1][j], sml[i][j]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a1[i], bw[0][j], sml[i][j]);
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a[1][i], b[0][j], sml[i][j]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a1[i], bw[1][j], sml[i][j]);
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a[1][i], b[1][j], sml[i][j]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a0[i], bw[2][j], sml[i][j]);
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a[0][i], b[2][j], sml[i][j]);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a2[i], bw[0][j], sml[i][j]);
-        __builtin_amdgcn_sched_barrier(0);            // a stage's reads and requests stay between its barrier and the next
+            for (int j = 0; j < 2; ++j) sml[i][j] = x6_mfma(a[2][i], b[0][j], sml[i][j]);
+        if constexpr (KIND <= 3) {
+            read_b(Next{}, 1, bw[NXT]);
+            read_b(Next{}, 2, bw[NXT]);
+            split(af, pa[NXT]);
+            __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
+            constexpr int NREQ = KIND == 0 ? 5 : (LDSRES ? (KIND == 3 ? 4 : 5) : 0);      // DMA requests of this iteration
+#pragma unroll
+            for (int g = 1; g < 24; ++g) {
+                __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+                if (g <= NREQ) __builtin_amdgcn_sched_group_barrier(0x10, 1, 0);
+                else if (g >= 2) __builtin_amdgcn_sched_group_barrier(0x2, 5, 0);
+                if (g == 15 || g == 19) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);            // an iteration's reads and requests stay between its barrier and the next
     };
     using C0 = std::integral_constant<int, 0>;
     using C1 = std::integral_constant<int, 1>;
     using C2 = std::integral_constant<int, 2>;
     using C3 = std::integral_constant<int, 3>;
+    using C4 = std::integral_constant<int, 4>;
 
     using X2 = std::integral_constant<int, DUAL ? 1 : 0>;   // source of the stages past S1 (x itself for the plain form)
-    auto group = [&](auto src, int s) {               // four steady-state stages whose requests all read one source
+    auto group = [&](auto src, int s) {               // four steady-state iterations; their requests (stages s + 4 .. s + 7) all read one source: S1 % 4 == 0
         stage(C0{}, C0{}, src, s);
         stage(C1{}, C0{}, src, s + 1);
         stage(C2{}, C0{}, src, s + 2);
         stage(C3{}, C0{}, src, s + 3);
     };
 
-    issue(C0{}, 0, 0);                                // (S1 >= 4: the first three stages read x)
+    issue(C0{}, 0, 0);                                // (S1 >= 4: the first four stages read x)
     issue(C0{}, 1, 1);
     issue(C0{}, 2, 2);
-    int s = 0;
-    if constexpr (DUAL) {
-        for (; s < S1 - 4; s += 4) group(C0{}, s);
-        stage(C0{}, C0{}, C0{}, s);                   // the group whose requests cross from x to x2 (S1 - 1 | S1 .. S1 + 2)
-        stage(C1{}, C0{}, X2{}, s + 1);
-        stage(C2{}, C0{}, X2{}, s + 2);
-        stage(C3{}, C0{}, X2{}, s + 3);
-        s += 4;
+    issue(C0{}, 3, 3);
+    {                                                 // stage 0 into set 0
+        x6_wait_vm<15>();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        f32x4 af[2][2];
+        read_a(C0{}, af);
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) read_b(C0{}, pl, bw[0]);
+        split(af, pa[0]);
+        __builtin_amdgcn_sched_barrier(0);
     }
+    int s = 0;
+    if constexpr (DUAL)
+        for (; s < S1 - 4; s += 4) group(C0{}, s);    // requests up to stage S1 - 1
     for (; s < S - 4; s += 4) group(X2{}, s);
-    stage(C0{}, C0{}, X2{}, s);                       // the last group: requests the last stage
-    stage(C1{}, C1{}, X2{}, s + 1);
-    stage(C2{}, C2{}, X2{}, s + 2);
-    stage(C3{}, C3{}, X2{}, s + 3);
+    stage(C0{}, C1{}, X2{}, s);                       // the last four: nothing left to request
+    stage(C1{}, C2{}, X2{}, s + 1);
+    stage(C2{}, C3{}, X2{}, s + 2);
+    stage(C3{}, C4{}, X2{}, s + 3);
 
     // ---- write-out from the accumulator layout (the ring kernel's): element e of tile (i, j) is row 32 i + (e & 3) + 8 (e >> 2) + 4 h,
     // channel 64 wn + 32 j + frow; rows >= M lie past the descriptor (loads read 0, stores are dropped).  Same expression as conv_epilogue.
