@@ -1076,6 +1076,26 @@ int vatl_bn_train_bwd_h16(const void* dy, const void* y_or_null, const void* z, 
                           void* dz, void* g_out_or_null, float* dgamma, float* dbeta, int64_t M, int C, float* coef3C, double* workspace, int dtype,
                           void* stream);
 int vatl_maxpool3x3s2_bwd_h16(const void* dpool, const void* x, void* dx, int N, int H, int W, int C, int dtype, void* stream);
+/* Every 16-bit filter re-pack of one bf16 training step in ONE launch (csrc/pack_h16.hip): the bytes of the per-tensor entry points,
+ * from the same source-index functions.  jobs_device: device array of njobs descriptors in ascending first_block = the running sum of
+ * ceil(elements / 1024) over the preceding jobs (256 threads write 1024 consecutive destination elements); total_blocks = that sum
+ * over all jobs.  Elements of a job, with C8 = C rounded up to 8:
+ *   kind 0  vatl_pack_conv_weight_h16:        src (Cout,Cin,R,S), Cout*R*S*Cin8 elements; stride / pad unused;
+ *   kind 1  vatl_pack_deconv4x4s2_weight_h16: src (Cin,Cout,4,4), 16*Cout*Cin8 elements; R = S = 4, stride / pad unused;
+ *   kind 2  vatl_pack_conv_weight_dgrad_h16:  src (Cout,Cin,R,S), all stride*stride phase filters, Cin8*R*S*Cout8 elements (a phase no tap
+ *           reaches is empty); R, S <= 7, stride 1 or 2.
+ * Blocks past total_blocks and the part of a job's last slice past its end write nothing; njobs == 0 launches nothing and returns 0.
+ * Every job of a table has the storage type named by `dtype`. */
+typedef struct VatlPackJobH16 {
+    const float* src;
+    void* dst;
+    int64_t first_block;
+    int32_t kind;
+    int32_t Cout, Cin, R, S;
+    int32_t stride, pad;
+    int32_t reserved;
+} VatlPackJobH16;
+int vatl_pack_weights_h16_multi(const VatlPackJobH16* jobs_device, int njobs, int64_t total_blocks, int dtype, void* stream);
 
 /* FLOAT64 REFERENCE GRADIENTS (csrc/wgrad_f64.hip, csrc/train_glue_f64.hip, the data-gradient launcher of csrc/conv_f64.hip;
  * alphapose/models/hip_train_f64.py).  The yardstick of the fine-tune step, beside the float64 forward above: no trainer, plan or

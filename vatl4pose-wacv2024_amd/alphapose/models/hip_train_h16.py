@@ -1,4 +1,5 @@
-"""Opt-in bf16 fine-tune step of SimplePose on the 16-bit matrix pipe (``cfg.RETRAIN.PRECISION: bf16``).
+"""Opt-in bf16 training step of SimplePose on the 16-bit matrix pipe (``cfg.RETRAIN.PRECISION: bf16`` for the fine-tune,
+``cfg.TRAIN.PRECISION: bf16`` / ``--precision bf16`` for ``alphapose.pretrain``).
 
 The fp32 trainer of ``hip_train`` multiplies on the fp32 matrix pipe; this one stores the input, every conv / deconv output z, every
 BatchNorm (+ residual) (+ ReLU) output y, the pooled stem output and every gradient with respect to them as bfloat16 (NHWC, channels
@@ -12,7 +13,8 @@ padded to 8) and multiplies on ``v_mfma_f32_16x16x32_bf16`` with fp32 accumulati
             gradient added in the write-out.
 
 Master weights stay the fp32 ``nn.Parameter``s: the bf16 filters (forward and data-gradient layouts) are re-packed whenever a parameter's
-(storage, version) has changed, i.e. in every step that follows an ``optimizer.step()``; the pack launches are part of the step.
+(storage, version) has changed, i.e. in every step that follows an ``optimizer.step()``: all of them by ONE launch at the start of the
+forward pass (``vatl_hip.PackPlanH16``, csrc/pack_h16.hip; ``_USE_PACK_PLAN``), which is part of the step.
 Gradients land as fp32 in each parameter's own layout, straight in the ``GradArena`` slices when one is given, so the optimiser, the
 all-reduce buckets and ``retrain_model``'s DataParallel-chunk logic are the fp32 trainer's.  BatchNorm running statistics follow the fp32
 trainer's semantics (momentum, unbiased variance, ``num_batches_tracked``).  Every reduction has one fixed order and there are no
@@ -23,6 +25,8 @@ bf16 only (fp16 would need loss scaling for the heat-map MSE gradients), SimpleP
 are refused by name and stay on the fp32 trainer.
 """
 from __future__ import annotations
+
+import threading
 
 import torch
 import torch.nn as nn
@@ -47,18 +51,63 @@ def _check_model(m):
             raise NotImplementedError("RETRAIN.PRECISION bf16 serves the bottleneck ResNets (50 / 101 / 152) only")
 
 
-class _Packed:
-    """A bf16 copy of an fp32 parameter in some packed layout, refreshed when the parameter's (storage, version) has changed."""
+_USE_PACK_PLAN = True      # False: every re-pack its own launch (same bits; tests/test_gpu_pretrain_h16.py A/Bs it)
+_tls = threading.local()   # per host thread: the plan of the trainer whose forward / backward pass is running
 
-    def __init__(self, p, pack):
-        self.p, self.pack, self.key, self.buf = p, pack, None, None
+
+class _Packed:
+    """A bf16 copy of an fp32 parameter in some packed layout, refreshed when the parameter's (storage, version) has changed: by the
+    running trainer's one-launch re-pack (vatl_hip.PackPlanH16) where its plan keeps the copy, otherwise on the spot."""
+
+    def __init__(self, p, pack, kind, stride=1, pad=0):
+        self.p, self.pack, self.job, self.key, self.buf = p, pack, (kind, stride, pad), None, None
 
     def get(self):
-        key = (self.p.data_ptr(), self.p._version)
+        p = self.p
+        plan = getattr(_tls, "plan", None) if p.is_contiguous() else None    # the one launch reads the parameter's own storage
+        key = (p.data_ptr(), p._version)
+        if plan is not None:
+            kept = plan.lookup(self, p)
+            if kept is not None:
+                self.buf, self.key = kept, key
+                return kept
         if key != self.key:
-            self.buf = self.pack(self.p.detach())
+            self.buf = self.pack(p.detach())
             self.key = key
+        if plan is not None:
+            plan.record(self, p.detach(), self.buf, *self.job)
         return self.buf
+
+
+def _planned(kind):
+    """Trainer.forward / Trainer.backward under the trainer's PackPlanH16, as ``hip_train._planned`` runs the fp32 trainers: the forward
+    pass starts with ONE launch that refreshes every bf16 filter the step reads (forward and data-gradient layouts).  A forward pass
+    without a ready plan records them: it packs per tensor, the data-gradient layouts at its end, and seals the record."""
+    def deco(fn):
+        def inner(self, *a, **k):
+            if not _USE_PACK_PLAN:
+                return fn(self, *a, **k)
+            plan = self.__dict__.get("_pack_plan")
+            if plan is None:
+                plan = self.__dict__["_pack_plan"] = vh.PackPlanH16(DT)
+            prev = getattr(_tls, "plan", None)
+            _tls.plan = plan
+            try:
+                if kind == "forward":
+                    plan.begin()
+                else:
+                    plan.note_stream()
+                out = fn(self, *a, **k)
+                if kind == "forward" and not plan.ready:
+                    for q in self.packed:
+                        q.get()
+                    plan.seal()
+                return out
+            finally:
+                _tls.plan = prev
+        inner.__name__, inner.__doc__ = fn.__name__, fn.__doc__
+        return inner
+    return deco
 
 
 class _ConvBN:
@@ -70,8 +119,8 @@ class _ConvBN:
         self.conv, self.bn, self.relu, self.need_dx = conv, bn, relu, need_dx
         self.cout, self.cin, self.r, self.s = conv.weight.shape
         self.stride, self.pad = conv.stride[0], conv.padding[0]
-        self.w = _Packed(conv.weight, lambda w: vh.pack_conv_weight_h16(w, DT))
-        self.wd = _Packed(conv.weight, lambda w: vh.pack_conv_weight_dgrad_h16(w, self.stride, self.pad, DT)) if need_dx else None
+        self.w = _Packed(conv.weight, lambda w: vh.pack_conv_weight_h16(w, DT), vh.PACK_H16_CONV)
+        self.wd = _Packed(conv.weight, lambda w: vh.pack_conv_weight_dgrad_h16(w, self.stride, self.pad, DT), vh.PACK_H16_DGRAD, self.stride, self.pad) if need_dx else None
 
     def forward(self, x, skip=None):
         bn = self.bn
@@ -109,9 +158,9 @@ class _DeconvBN:
             raise NotImplementedError(f"no bf16 training path for {dc}")
         self.dc, self.bn = dc, bn
         self.cin, self.cout = dc.weight.shape[:2]
-        self.w = _Packed(dc.weight, lambda w: vh.pack_deconv_weight_h16(w, DT))
+        self.w = _Packed(dc.weight, lambda w: vh.pack_deconv_weight_h16(w, DT), vh.PACK_H16_DECONV)
         # the data gradient is a plain 4x4 / stride 2 / pad 1 conv of dz whose "OIHW" weight is the (Cin,Cout,4,4) parameter itself
-        self.wd = _Packed(dc.weight, lambda w: vh.pack_conv_weight_h16(w, DT))
+        self.wd = _Packed(dc.weight, lambda w: vh.pack_conv_weight_h16(w, DT), vh.PACK_H16_CONV)
 
     def forward(self, x):
         bn = self.bn
@@ -162,8 +211,8 @@ class _HeadT:
             raise NotImplementedError(f"no bf16 training path for the head {conv}")
         self.conv = conv
         self.cout, self.cin = conv.weight.shape[:2]
-        self.w = _Packed(conv.weight, lambda w: vh.pack_conv_weight_h16(w, DT))
-        self.wd = _Packed(conv.weight, lambda w: vh.pack_conv_weight_dgrad_h16(w, 1, 0, DT))
+        self.w = _Packed(conv.weight, lambda w: vh.pack_conv_weight_h16(w, DT), vh.PACK_H16_CONV)
+        self.wd = _Packed(conv.weight, lambda w: vh.pack_conv_weight_dgrad_h16(w, 1, 0, DT), vh.PACK_H16_DGRAD, 1, 0)
 
     def forward(self, x):
         self.x = x
@@ -191,6 +240,8 @@ class SimplePoseTrainerH16:
         d = m.deconv_layers
         self.deconvs = [_DeconvBN(d[0], d[1]), _DeconvBN(d[3], d[4]), _DeconvBN(d[6], d[7])]
         self.head = _HeadT(m.final_layer)
+        convs = [self.stem] + [c for b in self.blocks for c in (b.c1, b.c2, b.c3, b.proj) if c is not None] + self.deconvs + [self.head]
+        self.packed = [q for c in convs for q in (c.w, c.wd) if q is not None]    # every bf16 filter of a step: 57 + 56 for the R50
 
     def trunk_forward(self, x_nchw, blocks=None):
         """Stem, max-pool and the first ``blocks`` bottlenecks (None: all) -> the last block's output, bf16 NHWC.  ``forward`` runs the
@@ -214,6 +265,7 @@ class SimplePoseTrainerH16:
         self.stem.backward(vh.maxpool3x3s2_bwd_h16(dx, stem_y), grads)
         _side.join()
 
+    @_planned("forward")
     def forward(self, x_nchw):
         """x (B,3,H,W) fp32 NCHW -> heat-maps (B,J,H/4,W/4) fp32 NCHW."""
         x = self.trunk_forward(x_nchw)
@@ -221,6 +273,7 @@ class SimplePoseTrainerH16:
             x = d.forward(x)
         return self.head.forward(x)
 
+    @_planned("backward")
     def backward(self, dout_nchw, arena=None, overlap=False):
         """dout (B,J,H,W) fp32 NCHW, any scale -> {parameter: fp32 gradient} for every parameter of the model.  With ``arena`` the
         gradients are its slices; ``overlap`` lets the arena all-reduce finished buckets while the earlier layers are still in flight."""

@@ -2,6 +2,7 @@
 jrdbpose_train.py) does through ``alphapose.opt``, ``DataParallel``, autograd and ``torch.optim``.
 
     python -m alphapose.pretrain --cfg <yaml> --exp-id <id> [--snapshot 2] [--seed 0] [--workers 8] [--max-epochs N] [--validate-only CKPT]
+                                 [--precision {fp32,bf16}]
 
 writes ``./exp/<exp-id>-<FILE_NAME>/`` with ``training.log``, ``model_<epoch>.pth``, ``model_best.pth``, ``final.pth`` and
 ``predicted_kpt.json`` — the files ``MODEL.PRETRAINED`` of the active-learning yamls names.
@@ -39,6 +40,12 @@ Deliberately different:
   the validation items; log and result name which (``val_metric``: "mAP" | "mOKS").  No AP arithmetic lives here.
   The decode is the batch kernel behind ``heatmap_to_coord_simple``.
 * Checkpoints are CPU tensors under the reference's state-dict keys.
+* ``TRAIN.PRECISION`` (absent = ``fp32``; ``--precision`` overrides it) chooses the training step's trainer: ``fp32`` is
+  ``hip_train.trainer_for``, the bits of every shipped yaml; ``bf16`` is the opt-in step of ``hip_train_h16`` (SimplePose only: bf16
+  storage and products, fp32 accumulation, gradients, master weights and optimiser state; every bf16 filter re-packed in one launch per
+  step).  Only the trainer changes: the loss, the optimiser, the checkpoints (fp32 master weights) and the validation pass (the fp32
+  engine; ``VAL.PRECISION`` is not read here) are the same.  Anything else — ``fp16`` would need loss scaling — is a ``ValueError``
+  and ``bf16`` with another ``MODEL.TYPE`` a ``NotImplementedError``, both raised before a data set is built or the device is touched.
 """
 from __future__ import annotations
 
@@ -58,6 +65,7 @@ from alphapose.models import builder
 from alphapose.utils.config import update_config
 from alphapose.utils.metrics import DataLogger, calc_accuracy_begin, evaluate_mAP, have_coco_tools
 
+PRECISIONS = ("fp32", "bf16")
 FLUSH_EVERY = 50                                      # steps between read-backs of the pending losses / accuracies, at most
 MAX_WORKERS = 16
 
@@ -75,6 +83,7 @@ def parse_args(argv=None):
     parser.add_argument("--workers", default=8, type=int, help=f"threads decoding the next batch's frames ahead (0 = none, at most {MAX_WORKERS})")
     parser.add_argument("--max-epochs", default=None, type=int, help="stop after this many epochs of this run")
     parser.add_argument("--validate-only", default=None, type=str, metavar="CKPT", help="load CKPT (strict), validate, write predicted_kpt.json")
+    parser.add_argument("--precision", default=None, choices=PRECISIONS, help="trainer of the training step; overrides the yaml's TRAIN.PRECISION (absent: fp32)")
     return parser.parse_args(argv)
 
 
@@ -84,6 +93,20 @@ def load_config(path):
     cfg["FILE_NAME"] = os.path.basename(path).split(".")[0]
     cfg.TRAIN.DPG_STEP = [i - cfg.TRAIN.DPG_MILESTONE for i in cfg.TRAIN.DPG_STEP]
     return cfg
+
+
+def train_precision(cfg, override=None) -> str:
+    """``override`` (the ``--precision`` flag) or ``cfg.TRAIN.PRECISION`` -> "fp32" (the default, and what an absent key means:
+    ``hip_train.trainer_for``) or "bf16" (the opt-in step of ``hip_train_h16``, SimplePose only).  "fp16" would need loss scaling for the
+    heat-map MSE gradients and is, like anything else, a ValueError; "bf16" with another network a NotImplementedError."""
+    name = override if override is not None else (cfg.TRAIN.get("PRECISION", "fp32") if "TRAIN" in cfg else "fp32")
+    if not isinstance(name, str) or name not in PRECISIONS:
+        raise ValueError(f"TRAIN.PRECISION must be one of {sorted(PRECISIONS)}, got {name!r}")
+    if name == "bf16":
+        model = cfg.MODEL.get("TYPE")
+        if model != "SimplePose":
+            raise NotImplementedError(f"TRAIN.PRECISION bf16 serves SimplePose only, not MODEL.TYPE {model!r} (FastPose, DCN and HRNet train in fp32)")
+    return name
 
 
 def work_dir_for(exp_id, cfg) -> str:
@@ -236,13 +259,20 @@ def _columns(batch):
     return batch[0], batch[1], batch[2]
 
 
-def train_epoch(model, batches, optimizer):
-    """``train()`` (:30-87) over any iterable of the data set's batches -> (loss, accuracy), batch-size weighted averages."""
+def train_epoch(model, batches, optimizer, precision="fp32"):
+    """``train()`` (:30-87) over any iterable of the data set's batches -> (loss, accuracy), batch-size weighted averages.
+    ``precision`` "bf16" takes the bf16 trainer (same interface); the default never imports it."""
     from alphapose.models import hip_train
+    if precision not in PRECISIONS:
+        raise ValueError(f"TRAIN.PRECISION must be one of {sorted(PRECISIONS)}, got {precision!r}")
     device = _device_of(model)
     loss_logger, acc_logger = DataLogger(), DataLogger()
     model.train()
-    trainer = hip_train.trainer_for(model)
+    if precision == "bf16":                                   # opt-in: bf16 storage and products, fp32 gradients into the same arena
+        from alphapose.models import hip_train_h16
+        trainer = hip_train_h16.trainer_for_h16(model)
+    else:
+        trainer = hip_train.trainer_for(model)
     arena = hip_train.arena_for(model)
     pending = []
 
@@ -328,13 +358,14 @@ def validate(model, cfg, dataset, work_dir, batches=None):
 # the epoch loop
 # ---------------------------------------------------------------------------------------------------------------------
 
-def run_epochs(cfg, model, optimizer, train_fn, validate_fn, work_dir, snapshot=2, max_epochs=None, log=print, save=None):
+def run_epochs(cfg, model, optimizer, train_fn, validate_fn, work_dir, snapshot=2, max_epochs=None, log=print, save=None, precision="fp32"):
     """posetrack_train.py:160-212 with the training epoch and the validation pass as callables: ``train_fn(epoch) -> (loss, acc)``,
-    ``validate_fn(epoch) -> {"metric", "val_metric", ...}``.  Returns the run's summary dict."""
+    ``validate_fn(epoch) -> {"metric", "val_metric", ...}``.  Returns the run's summary dict; ``precision`` (what ``train_fn`` trains
+    in) is only noted there."""
     save = save or (lambda m, path: torch.save(cpu_state_dict(m), path))
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=list(cfg.TRAIN.LR_STEP), gamma=cfg.TRAIN.LR_FACTOR)
     out = {"work_dir": work_dir, "epochs": [], "lr": [], "train_loss": [], "train_acc": [], "val": [], "val_metric": None, "best_score": 0,
-           "best_epoch": None, "saved": [], "ended": "end_epoch"}
+           "best_epoch": None, "saved": [], "ended": "end_epoch", "precision": precision}
 
     def keep(name):
         path = os.path.join(work_dir, name)
@@ -382,6 +413,7 @@ def seed_everything(seed: int):
 def main(argv=None):
     opt = parse_args(argv)
     cfg = load_config(opt.cfg)
+    precision = train_precision(cfg, opt.precision)           # refused here: before the device, the work dir and the data sets
     if not torch.cuda.is_available():
         raise vh.VatlError("the pose networks train on MI355X only (no CPU fallback)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -392,6 +424,7 @@ def main(argv=None):
     try:
         log(f"options: {vars(opt)}")
         log(f"config: {dict(cfg)}")
+        log(f"training precision: {precision} (TRAIN.PRECISION / --precision; checkpoints and validation are fp32)")
         seed_everything(opt.seed)
         if opt.validate_only:
             cfg.MODEL.PRETRAINED, cfg.MODEL.TRY_LOAD = opt.validate_only, ""
@@ -413,9 +446,9 @@ def main(argv=None):
         gen.manual_seed(opt.seed)
         log(f"train items: {len(train_set)}, validation items: {len(val_set)}, decode-ahead threads: {pool.workers}")
         out = run_epochs(cfg, model, optimizer,
-                         train_fn=lambda i: train_epoch(model, pool.batches(epoch_batches(len(train_set), batch_size, gen)), optimizer),
+                         train_fn=lambda i: train_epoch(model, pool.batches(epoch_batches(len(train_set), batch_size, gen)), optimizer, precision),
                          validate_fn=lambda i: validate(model, cfg, val_set, work_dir),
-                         work_dir=work_dir, snapshot=opt.snapshot, max_epochs=opt.max_epochs, log=log)
+                         work_dir=work_dir, snapshot=opt.snapshot, max_epochs=opt.max_epochs, log=log, precision=precision)
         log(f"run ended: {out['ended']}; best {out['val_metric']}: {out['best_score']} (epoch {out['best_epoch']})")
         out["model"] = model
         return out

@@ -40,24 +40,25 @@ inline int conv_shape_contract(const char* what, const char* arrow, bool dgrad, 
 
 // Filter layouts: element i of the packed buffer -> element of the module's fp32 parameter, or -1 where i is a padded channel (Cinp:
 // the channel count as stored; kPadded: the 16-bit types pad it to 8, float64 stores Cinp = Cin).  The pack kernels convert and zero-fill.
+// I: the integer type i is divided in (long long; unsigned where the caller knows the buffer has fewer than 2^31 elements: 64-bit division is slow).
 // OIHW -> [Cout][R][S][Cinp]
-template <bool kPadded>
-__host__ __device__ inline long long conv_weight_src(long long i, int Cin, int Cinp, int R, int S) {
-    const int c = (int)(i % Cinp);
-    long long t = i / Cinp;
-    const int s = (int)(t % S); t /= S;
-    const int r = (int)(t % R);
-    const long long co = t / R;
+template <bool kPadded, typename I>
+__host__ __device__ inline long long conv_weight_src(I i, int Cin, int Cinp, int R, int S) {
+    const int c = (int)(i % (I)Cinp);
+    I t = i / (I)Cinp;
+    const int s = (int)(t % (I)S); t /= (I)S;
+    const int r = (int)(t % (I)R);
+    const long long co = (long long)(t / (I)R);
     return !kPadded || c < Cin ? ((co * Cin + c) * R + r) * S + s : -1;
 }
 // ConvTranspose2d(4,2,1) weight (Cin,Cout,4,4) -> [phase = py*2+px][Cout][ty][tx][Cinp], ky = 3-py-2ty, kx = 3-px-2tx
-template <bool kPadded>
-__host__ __device__ inline long long deconv_weight_src(long long i, int Cin, int Cinp, int Cout) {
-    const int c = (int)(i % Cinp);
-    long long t = i / Cinp;
+template <bool kPadded, typename I>
+__host__ __device__ inline long long deconv_weight_src(I i, int Cin, int Cinp, int Cout) {
+    const int c = (int)(i % (I)Cinp);
+    I t = i / (I)Cinp;
     const int tx = (int)(t & 1), ty = (int)((t >> 1) & 1); t >>= 2;
-    const int co = (int)(t % Cout);
-    const int ph = (int)(t / Cout);
+    const int co = (int)(t % (I)Cout);
+    const int ph = (int)(t / (I)Cout);
     const int ky = 3 - (ph >> 1) - 2 * ty, kx = 3 - (ph & 1) - 2 * tx;
     return !kPadded || c < Cin ? (((long long)c * Cout + co) * 4 + ky) * 4 + kx : -1;
 }

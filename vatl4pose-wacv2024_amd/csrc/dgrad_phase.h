@@ -27,14 +27,14 @@ __host__ __device__ inline long long dgrad_phase_offset(int R, int S, int stride
     for (int q = 0; q < phase; ++q) off += cc * dgrad_axis(R, stride, pad, q / stride).taps * dgrad_axis(S, stride, pad, q % stride).taps;
     return off;
 }
-// OIHW -> element i of ONE phase of that buffer, or -1 for a padded channel (kPadded as in conv_generic.h)
-template <bool kPadded>
-__host__ __device__ inline long long dgrad_weight_src(long long i, DgradAxis ay, DgradAxis ax, int Cout, int Cin, int Coutp, int R, int S, int stride) {
-    const int co = (int)(i % Coutp);
-    long long t = i / Coutp;
-    const int tx = (int)(t % ax.taps); t /= ax.taps;
-    const int ty = (int)(t % ay.taps);
-    const int ci = (int)(t / ay.taps);
+// OIHW -> element i of ONE phase of that buffer, or -1 for a padded channel (kPadded and I as in conv_generic.h)
+template <bool kPadded, typename I>
+__host__ __device__ inline long long dgrad_weight_src(I i, DgradAxis ay, DgradAxis ax, int Cout, int Cin, int Coutp, int R, int S, int stride) {
+    const int co = (int)(i % (I)Coutp);
+    I t = i / (I)Coutp;
+    const int tx = (int)(t % (I)ax.taps); t /= (I)ax.taps;
+    const int ty = (int)(t % (I)ay.taps);
+    const int ci = (int)(t / (I)ay.taps);
     const int r = ay.r0 - stride * ty, s = ax.r0 - stride * tx;
     return !kPadded || (co < Cout && ci < Cin) ? (((long long)co * Cin + ci) * R + r) * S + s : -1;
 }

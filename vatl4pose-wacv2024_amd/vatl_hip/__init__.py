@@ -234,6 +234,7 @@ SIGNATURES = {
     "vatl_bn_apply_h16": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _p]),
     "vatl_bn_train_bwd_h16": (_i, [_p] * 10 + [_i64, _i, _p, _p, _i, _p]),
     "vatl_maxpool3x3s2_bwd_h16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "vatl_pack_weights_h16_multi": (_i, [_p, _i, _i64, _i, _p]),
     "vatl_wgrad_f64_splits": (_i64, [_i64]),
     "vatl_conv2d_wgrad_f64_workspace_doubles": (_i64, [_i, _i, _i, _i, _i64]),
     "vatl_conv2d_wgrad_f64": (_i, [_p, _p, _p, _i64] + [_i] * 10 + [_p]),
@@ -2792,6 +2793,121 @@ def pack_conv_weight_dgrad_h16(w: torch.Tensor, stride: int, pad: int, dtype) ->
     _check(lib().vatl_pack_conv_weight_dgrad_h16(_ptr(w.contiguous()), _ptr(out, dtype), cout, cin, r, s, stride, pad, code, _stream()),
            "vatl_pack_conv_weight_dgrad_h16")
     return out
+
+
+# VatlPackJobH16.kind (include/vatl_hip.h: vatl_pack_weights_h16_multi) = which per-tensor packer's bytes the job writes
+PACK_H16_CONV = 0                   # pack_conv_weight_h16: src (Cout,Cin,R,S)
+PACK_H16_DECONV = 1                 # pack_deconv_weight_h16: src (Cin,Cout,4,4)
+PACK_H16_DGRAD = 2                  # pack_conv_weight_dgrad_h16: src (Cout,Cin,R,S), every phase of (stride, pad)
+_PACK_H16_SLICE = 1024              # destination elements per block
+
+
+class _PackJobH16(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("first_block", C.c_int64), ("kind", C.c_int32), ("Cout", C.c_int32), ("Cin", C.c_int32),
+                ("R", C.c_int32), ("S", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PackPlanH16:
+    """The 16-bit filter re-packs of one bf16 training step as ONE launch (vatl_pack_weights_h16_multi): ``PackPlan``'s life cycle for
+    the packers of the 16-bit route.
+
+    The first step under a plan packs per tensor (``pack_conv_weight_h16`` / ``pack_deconv_weight_h16`` / ``pack_conv_weight_dgrad_h16``)
+    and RECORDS each call: source tensor, kind, geometry and the destination, which is then kept.  ``seal()`` uploads the table.  From
+    the next step on ``begin()`` refreshes every kept destination with one launch and ``lookup`` hands the kept buffers out — only while
+    the source is the recorded storage at the version it had at ``begin()``; anything else makes the caller pack on the spot and the
+    plan record again, into fresh buffers, at its next ``begin()``.
+
+    The kept buffers are overwritten in place, so ``begin()`` has to come after the last reader of the previous step: it does on the
+    same stream, and it makes the current stream wait for every other stream a step has been noted on since (``note_stream``)."""
+
+    def __init__(self, dtype):
+        self.dtype, self.code = dtype, _h16_code(dtype)
+        self.jobs = {}            # key -> [src tensor, dst tensor, (kind, Cout, Cin, R, S, stride, pad), version at begin()]
+        self.table = None
+        self.total_blocks = 0
+        self.ready = False
+        self.stale = False
+        self.streams = []         # where the kept buffers may still be read
+
+    def note_stream(self):
+        """The pass that starts now reads the kept buffers on the current stream."""
+        cur = torch.cuda.current_stream()
+        if cur not in self.streams:
+            self.streams.append(cur)
+        return cur
+
+    def begin(self):
+        cur = torch.cuda.current_stream()
+        if self.ready and not self.stale:
+            for st in self.streams:
+                if st != cur:
+                    cur.wait_stream(st)
+            for j in self.jobs.values():
+                j[3] = j[0]._version
+            _check(lib().vatl_pack_weights_h16_multi(_ptr(self.table, torch.uint8), len(self.jobs), self.total_blocks, self.code, _stream()),
+                   "vatl_pack_weights_h16_multi")
+        else:
+            for j in self.jobs.values():                     # let go of the kept buffers only behind their readers on other streams
+                for st in self.streams:
+                    if st != cur:
+                        j[1].record_stream(st)
+            self.jobs, self.table, self.total_blocks, self.ready, self.stale = {}, None, 0, False, False
+        self.streams = [cur]
+
+    def lookup(self, key, w):
+        if not self.ready:
+            return None
+        j = self.jobs.get(key)
+        if j is None or j[0].data_ptr() != w.data_ptr() or j[3] != w._version:
+            self.stale = True                      # a filter the recording did not see, or weights that changed since begin()
+            return None
+        return j[1]
+
+    @staticmethod
+    def elements(kind: int, shape) -> int:
+        """Destination elements of a job of ``kind`` whose source has ``shape``."""
+        a, b, r, s = (int(v) for v in shape)
+        if kind == PACK_H16_CONV:
+            return a * r * s * _pad8(b)
+        if kind == PACK_H16_DECONV:
+            return 16 * b * _pad8(a)
+        if kind == PACK_H16_DGRAD:
+            return _pad8(b) * r * s * _pad8(a)
+        raise VatlError(f"PackPlanH16: unknown kind {kind}")
+
+    def record(self, key, w, dst, kind: int, stride: int = 1, pad: int = 0):
+        """Note that ``dst`` holds the ``kind`` pack of ``w`` (just written by the per-tensor packer) and is to be kept."""
+        if self.ready or key in self.jobs:
+            return
+        if w.dim() != 4 or w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous():
+            raise VatlError("PackPlanH16: the source must be a contiguous 4-D fp32 device tensor")
+        a, b, r, s = (int(v) for v in w.shape)
+        if kind == PACK_H16_DECONV:
+            if (r, s) != (4, 4):
+                raise VatlError(f"PackPlanH16: a 4x4 filter is needed, got {r}x{s}")
+            cout, cin = b, a
+        else:
+            cout, cin = a, b
+        if kind == PACK_H16_DGRAD and (r > 7 or s > 7 or stride not in (1, 2) or pad < 0):
+            raise VatlError(f"PackPlanH16: no data-gradient pack for a {r}x{s} filter with stride {stride}, pad {pad}")
+        if dst.dtype != self.dtype or dst.device != w.device or not dst.is_contiguous() or dst.numel() != self.elements(kind, w.shape):
+            raise VatlError(f"PackPlanH16: destination of {dst.numel()} {dst.dtype} elements does not fit kind {kind} of a {tuple(w.shape)} filter")
+        self.jobs[key] = [w, dst, (kind, cout, cin, r, s, int(stride), int(pad)), w._version]
+
+    def seal(self):
+        if self.ready or not self.jobs:
+            return
+        arr = (_PackJobH16 * len(self.jobs))()
+        blocks = 0
+        for k, (src, dst, f, _) in enumerate(self.jobs.values()):
+            jb = arr[k]
+            jb.src, jb.dst, jb.first_block = src.data_ptr(), dst.data_ptr(), blocks
+            jb.kind, jb.Cout, jb.Cin, jb.R, jb.S, jb.stride, jb.pad = f
+            blocks += (dst.numel() + _PACK_H16_SLICE - 1) // _PACK_H16_SLICE
+        dev = next(iter(self.jobs.values()))[1].device
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        self.total_blocks = blocks
+        self.ready = True
 
 
 def conv2d_dgrad_h16(dz, w_dgrad, xshape, r: int, s: int, stride: int, pad: int, residual=None):
