@@ -39,6 +39,20 @@ __device__ __forceinline__ Nyxc nyxc(long long i, int H, int W, int C4) {
     return p;
 }
 
+// Column reductions of the bf16 and float64 training glue (train_glue_h16.hip, train_glue_f64.hip): a block owns kRowsPerBlock consecutive
+// rows and writes partial[(rb * C + c) * 2 + {0, 1}] in double
+constexpr int kRowsPerBlock = 512;
+static inline int tg_row_blocks(long long M) { return (int)((M + kRowsPerBlock - 1) / kRowsPerBlock); }
+// ... and a wave per channel sums them: lane l adds the row blocks l, l + 64, ... in ascending order, then the fixed xor tree
+__device__ __forceinline__ void tg_sum_partials(const double* __restrict__ partial, int nrb, int C, int c, int lane, double& s, double& q) {
+    s = 0.0;
+    q = 0.0;
+    if (c < C)
+        for (int rb = lane; rb < nrb; rb += 64) { s += partial[((long long)rb * C + c) * 2]; q += partial[((long long)rb * C + c) * 2 + 1]; }
+    s = wave_sum(s);
+    q = wave_sum(q);
+}
+
 // pool.hip's per-item pixel reductions of small batches (mode 0: average pool, 1: SE gate gradient); false = not one of their shapes
 __attribute__((visibility("hidden"))) bool hw_reduce_try(int mode, const float* a, const float* y, const float* u, const float* gate, float* out, int N, int HW,
                                                          int C, hipStream_t st);

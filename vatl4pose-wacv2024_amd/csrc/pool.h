@@ -15,6 +15,7 @@ __device__ __forceinline__ int pool_tap(int iy, int ix, int oy, int ox) { return
 // one step of the scan over the taps k = 0..8 that lie inside the image, in order: does v take over from the best so far?  The
 // first maximum wins (bk = winning tap so far, 255: none yet)
 __device__ __forceinline__ bool pool_takes(float v, float best, int bk) { return v > best || bk == 255; }
+__device__ __forceinline__ bool pool_takes(double v, double best, int bk) { return v > best || bk == 255; }
 
 // gradient of input pixel (n, iy, ix), channels V*cv .. V*cv + V - 1: sum over the covering windows whose winner is this pixel.
 // V = 4: float4 / uchar4 per window; V = 1: one channel (channel counts that are no multiple of 4).  Same sums, same order.

@@ -4,7 +4,7 @@
 //   * everything is float64: statistics, (scale, bias), dgamma, dbeta, the running statistics a step WOULD write (returned, never
 //     written to the module).  Formulas of bn_train.hip: mean = s / M, biased variance = max(q / M - mean^2, 0) for the normalisation,
 //     unbiased (M > 1) into the running variance, momentum as nn.BatchNorm2d;
-//   * every reduction has one fixed order and no atomics: a block owns kRowsPerBlockF64 consecutive rows (boundaries: the row count
+//   * every reduction has one fixed order and no atomics: a block owns kRowsPerBlock consecutive rows (boundaries: the row count
 //     only), a thread adds every eighth row of them in ascending order, the eight row lanes are combined in lane order, the row blocks
 //     in ascending order per wave lane and through a fixed xor tree;
 //   * the ReLU mask is taken from the STORED y (y > 0); the max-pool gradient goes to the FIRST maximum of a window in scan order
@@ -13,10 +13,6 @@
 #include "pool.h"
 
 namespace vatl {
-
-constexpr int kRowsPerBlockF64 = 512;           // rows of a reduction block
-
-static inline int tg64_row_blocks(long long M) { return (int)((M + kRowsPerBlockF64 - 1) / kRowsPerBlockF64); }
 
 // Column reduction over the M rows: block (rb, slab of 32 channels), thread = channel t & 31, row lane t >> 5.
 // MODE 0: (sum a, sum a^2).  MODE 1: (sum g, sum g * xhat), g = a * [y > 0] (y NULL: no mask), xhat = (z - mean) * invstd.
@@ -28,8 +24,8 @@ __global__ __launch_bounds__(256) void tg64_col_reduce_kernel(const double* __re
     __shared__ double sh[2][8][33];
     const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
     const int c = blockIdx.y * 32 + cl;
-    const long long r0 = (long long)blockIdx.x * kRowsPerBlockF64;
-    const long long r1 = r0 + kRowsPerBlockF64 < M ? r0 + kRowsPerBlockF64 : M;
+    const long long r0 = (long long)blockIdx.x * kRowsPerBlock;
+    const long long r1 = r0 + kRowsPerBlock < M ? r0 + kRowsPerBlock : M;
     double s = 0.0, q = 0.0;
     if (c < C) {
         const double mu = MODE == 1 ? mean[c] : 0.0, is = MODE == 1 ? invstd[c] : 0.0;
@@ -58,23 +54,13 @@ __global__ __launch_bounds__(256) void tg64_col_reduce_kernel(const double* __re
     }
 }
 
-// wave per channel: lane l adds the row blocks l, l + 64, ... in ascending order, then the fixed xor tree
-__device__ __forceinline__ void tg64_sum_partials(const double* __restrict__ partial, int nrb, int C, int c, int lane, double& s, double& q) {
-    s = 0.0;
-    q = 0.0;
-    if (c < C)
-        for (int rb = lane; rb < nrb; rb += 64) { s += partial[((long long)rb * C + c) * 2]; q += partial[((long long)rb * C + c) * 2 + 1]; }
-    s = wave_sum(s);
-    q = wave_sum(q);
-}
-
 // out: seven rows of C doubles — mean, biased variance, invstd, scale, bias, would-be running mean, would-be running variance
 __global__ __launch_bounds__(256) void tg64_bn_fwd_finalize_kernel(const double* __restrict__ partial, int nrb, long long M, int C, const double* __restrict__ gamma,
                                                                    const double* __restrict__ beta, const double* __restrict__ running_mean,
                                                                    const double* __restrict__ running_var, double momentum, double eps, double* __restrict__ out) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     double s, q;
-    tg64_sum_partials(partial, nrb, C, c, lane, s, q);
+    tg_sum_partials(partial, nrb, C, c, lane, s, q);
     if (c >= C || lane != 0) return;
     const double mean = s / (double)M;
     double var;
@@ -101,7 +87,7 @@ __global__ __launch_bounds__(256) void tg64_bn_bwd_finalize_kernel(const double*
                                                                    double* __restrict__ dbeta) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     double sg, sgx;
-    tg64_sum_partials(partial, nrb, C, c, lane, sg, sgx);
+    tg_sum_partials(partial, nrb, C, c, lane, sg, sgx);
     if (c >= C || lane != 0) return;
     dbeta[c] = sg;
     dgamma[c] = sgx;
@@ -110,7 +96,7 @@ __global__ __launch_bounds__(256) void tg64_bn_bwd_finalize_kernel(const double*
 __global__ __launch_bounds__(256) void tg64_col_sum_finalize_kernel(const double* __restrict__ partial, int nrb, int C, double* __restrict__ out) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     double s, q;
-    tg64_sum_partials(partial, nrb, C, c, lane, s, q);
+    tg_sum_partials(partial, nrb, C, c, lane, s, q);
     if (c >= C || lane != 0) return;
     out[c] = s;
 }
@@ -140,9 +126,6 @@ __global__ void tg64_bn_bwd_apply_kernel(const double* __restrict__ dy, const do
         if (gout) gout[i] = g;
     }
 }
-
-// first maximum in scan order: pool.h's rule on doubles
-__device__ __forceinline__ bool pool_takes(double v, double best, int bk) { return v > best || bk == 255; }
 
 // MaxPool2d(3,2,1) backward in gather form: dx of input pixel (iy, ix) = sum, over the <= 4 windows that cover it in window order, of dpool
 // where this pixel is the window's FIRST maximum in scan order (rows, then columns, padding skipped) — recomputed from x, no index tensor
@@ -182,7 +165,7 @@ static int tg64_contract(const char* what, long long M, int C) {
 
 using namespace vatl;
 
-extern "C" int64_t vatl_bn_f64_workspace_doubles(int64_t M, int C) { return M < 1 || C < 1 ? 0 : 2 * (int64_t)tg64_row_blocks(M) * C; }
+extern "C" int64_t vatl_bn_f64_workspace_doubles(int64_t M, int C) { return M < 1 || C < 1 ? 0 : 2 * (int64_t)tg_row_blocks(M) * C; }
 
 extern "C" int vatl_bn_train_fwd_stats_f64(const double* z, int64_t M, int C, const double* gamma, const double* beta, const double* running_mean,
                                            const double* running_var, double momentum, double eps, double* stats7C, double* workspace, void* stream) {
@@ -190,7 +173,7 @@ extern "C" int vatl_bn_train_fwd_stats_f64(const double* z, int64_t M, int C, co
     if (!z || !stats7C || !workspace) return fail(VATL_EINVAL, "%s: null pointer", what);
     if ((running_mean == nullptr) != (running_var == nullptr)) return fail(VATL_EINVAL, "%s: running mean and variance come together", what);
     if (const int rc = tg64_contract(what, M, C)) return rc;
-    const int nrb = tg64_row_blocks(M);
+    const int nrb = tg_row_blocks(M);
     hipLaunchKernelGGL(tg64_col_reduce_kernel<0>, dim3(nrb, cdiv(C, 32)), dim3(256), 0, (hipStream_t)stream, z, (const double*)nullptr, (const double*)nullptr,
                        (const double*)nullptr, (const double*)nullptr, workspace, (long long)M, C);
     if (const int rc = check_launch("bn_train_fwd_stats_f64 (reduction)")) return rc;
@@ -213,7 +196,7 @@ extern "C" int vatl_bn_train_bwd_f64(const double* dy, const double* y_or_null, 
                                      double* workspace, void* stream) {
     if (!dy || !z || !save_mean || !save_invstd || !dz || !dgamma || !dbeta || !workspace) return fail(VATL_EINVAL, "bn_train_bwd_f64: null pointer");
     if (const int rc = tg64_contract("bn_train_bwd_f64", M, C)) return rc;
-    const int nrb = tg64_row_blocks(M);
+    const int nrb = tg_row_blocks(M);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(tg64_col_reduce_kernel<1>, dim3(nrb, cdiv(C, 32)), dim3(256), 0, st, dy, y_or_null, z, save_mean, save_invstd, workspace, (long long)M, C);
     if (const int rc = check_launch("bn_train_bwd_f64 (reduction)")) return rc;
@@ -237,7 +220,7 @@ extern "C" int vatl_maxpool3x3s2_bwd_f64(const double* dpool, const double* x, d
 extern "C" int vatl_col_sum_f64(const double* x, int64_t M, int C, double* out, double* workspace, void* stream) {
     if (!x || !out || !workspace) return fail(VATL_EINVAL, "col_sum_f64: null pointer");
     if (const int rc = tg64_contract("col_sum_f64", M, C)) return rc;
-    const int nrb = tg64_row_blocks(M);
+    const int nrb = tg_row_blocks(M);
     hipLaunchKernelGGL(tg64_col_reduce_kernel<0>, dim3(nrb, cdiv(C, 32)), dim3(256), 0, (hipStream_t)stream, x, (const double*)nullptr, (const double*)nullptr,
                        (const double*)nullptr, (const double*)nullptr, workspace, (long long)M, C);
     if (const int rc = check_launch("col_sum_f64 (reduction)")) return rc;

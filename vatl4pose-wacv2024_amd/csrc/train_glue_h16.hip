@@ -18,10 +18,6 @@
 
 namespace vatl {
 
-constexpr int kRowsPerBlock = 512;              // rows of a reduction block
-
-static inline int tg_row_blocks(long long M) { return (int)((M + kRowsPerBlock - 1) / kRowsPerBlock); }
-
 // Column reduction over the M rows of an NHWC tensor: block (rb, slab of 32 channel groups), thread = channel group t & 31, row lane t >> 5.
 // MODE 0: (sum z, sum z^2).  MODE 1: (sum g, sum g * xhat), g = dy * [y > 0] (y NULL: no mask), xhat = (z - mean) * invstd.
 // partial[(rb * C + c) * 2 + {0, 1}] in double: the layout bn_train.hip's finalize kernels read.
@@ -76,17 +72,13 @@ __global__ __launch_bounds__(256) void tg_col_reduce_kernel(const uint4* __restr
     }
 }
 
-// (sum g, sum g*xhat) -> dgamma, dbeta and the coefficients of dz = A*g + B*z + Cc (bn_train.hip's formulas): a wave per channel, lane l
-// adds the row blocks l, l + 64, ... in ascending order, then the fixed xor tree
+// (sum g, sum g*xhat) -> dgamma, dbeta and the coefficients of dz = A*g + B*z + Cc (bn_train.hip's formulas): a wave per channel
 __global__ __launch_bounds__(256) void tg_bn_bwd_finalize_kernel(const double* __restrict__ partial, int nrb, long long M, int C, const float* __restrict__ gamma,
                                                                  const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ dgamma,
                                                                  float* __restrict__ dbeta, float* __restrict__ coef) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    double sg = 0.0, sgx = 0.0;
-    if (c < C)
-        for (int rb = lane; rb < nrb; rb += 64) { sg += partial[((long long)rb * C + c) * 2]; sgx += partial[((long long)rb * C + c) * 2 + 1]; }
-    sg = wave_sum(sg);
-    sgx = wave_sum(sgx);
+    double sg, sgx;
+    tg_sum_partials(partial, nrb, C, c, lane, sg, sgx);
     if (c >= C || lane != 0) return;
     if (dbeta) dbeta[c] = (float)sg;
     if (dgamma) dgamma[c] = (float)sgx;

@@ -20,7 +20,7 @@
 // LDS banks: a row of the image is kWg64Ld = 80 doubles = 160 dwords.  ds_read_b64 is served per 32-lane half over 64 banks: a half
 // reads pixel rows k and k + 1, sixteen consecutive doubles (32 banks) of each, and 160 = 32 (mod 64) puts the second row on the other
 // 32 banks — conflict-free.  ds_write_b64 is served per sixteen lanes over 32 banks: sixteen consecutive doubles, conflict-free.
-#include "common.h"
+#include "wgrad_generic.h"
 
 namespace vatl {
 
@@ -30,15 +30,7 @@ constexpr int kWg64Tile = 64;                    // rows and columns of a block'
 constexpr int kWg64K = 16;                       // pixels per staged image
 constexpr int kWg64Ld = kWg64Tile + 16;          // LDS row pitch in doubles (see the bank argument above)
 
-struct WgradF64Geom {
-    long long M;                                 // pixels of the dz side
-    int chunk;                                   // pixels per split
-    int Ho, Wo, Ca;                              // dz side: plane and channels (rows of the GEMM)
-    int H, W, Cb;                                // x side: plane and channels
-    int R, S, stride, pad, ncol;                 // ncol = R*S*Cb
-};
-
-__global__ __launch_bounds__(256) void wgrad_f64_kernel(const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ ws, WgradF64Geom g) {
+__global__ __launch_bounds__(256) void wgrad_f64_kernel(const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ ws, WgradGeom g) {
     __shared__ double As[kWg64K][kWg64Ld];
     __shared__ double Bs[kWg64K][kWg64Ld];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -122,30 +114,14 @@ __global__ __launch_bounds__(256) void wgrad_f64_kernel(const double* __restrict
         }
 }
 
-// dw[row][c][tap] = sum over splits, ascending, of ws[split][row][tap][c]: thread per output element in the workspace's order (c fastest)
-__global__ void wgrad_f64_reduce_kernel(const double* __restrict__ ws, double* __restrict__ dw, int splits, int rows, int cols, int RS) {
-    const long long total = (long long)rows * cols * RS;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % cols);
-        const long long t = i / cols;
-        const int tap = (int)(t % RS);
-        const long long row = t / RS;
-        double s = 0.0;
-        for (int k = 0; k < splits; ++k) s += ws[k * total + i];
-        dw[(row * cols + c) * RS + tap] = s;
-    }
-}
-
-static inline long long wgrad_f64_splits(long long M) { return M <= 0 ? 0 : (M + VATL_WGRAD_F64_CHUNK - 1) / VATL_WGRAD_F64_CHUNK; }
-
 }  // namespace vatl
 
 using namespace vatl;
 
-extern "C" int64_t vatl_wgrad_f64_splits(int64_t M) { return wgrad_f64_splits(M); }
+extern "C" int64_t vatl_wgrad_f64_splits(int64_t M) { return wgrad_splits(M, VATL_WGRAD_F64_CHUNK); }
 
 extern "C" int64_t vatl_conv2d_wgrad_f64_workspace_doubles(int Cout, int Cin, int R, int S, int64_t M) {
-    return wgrad_f64_splits(M) * (int64_t)Cout * R * S * Cin;
+    return wgrad_splits(M, VATL_WGRAD_F64_CHUNK) * (int64_t)Cout * R * S * Cin;
 }
 
 extern "C" int vatl_conv2d_wgrad_f64(const double* x, const double* dz, double* workspace, int64_t workspace_doubles, int N, int H, int W, int Cin, int Cout,
@@ -156,38 +132,14 @@ extern "C" int vatl_conv2d_wgrad_f64(const double* x, const double* dz, double* 
     if (Cin < 1 || Cout < 1) return fail(VATL_EINVAL, "%s: %d -> %d channels", what, Cin, Cout);
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(workspace)) & 7u)
         return fail(VATL_EINVAL, "%s: float64 tensors must be 8-byte aligned", what);
-    if (N < 1 || H < 1 || W < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0)
-        return fail(VATL_EINVAL, "%s: N %d, %dx%d, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", what, N, H, W, R, S, stride, pad);
-    WgradF64Geom g{};
-    const double *a, *b;
-    if (transposed) {                                     // ConvTranspose2d(4,2,1): the forward input is the dz side of a 4x4 / 2 / pad 1 conv of the output gradient
-        if (R != 4 || S != 4 || stride != 2 || pad != 1) return fail(VATL_EINVAL, "%s: the transposed form serves ConvTranspose2d(4, 2, 1) only", what);
-        g.Ho = H; g.Wo = W; g.Ca = Cin; g.H = 2 * H; g.W = 2 * W; g.Cb = Cout;
-        a = x; b = dz;
-    } else {
-        if (H + 2 * pad < R || W + 2 * pad < S) return fail(VATL_EINVAL, "%s: a %dx%d filter does not fit a %dx%d plane with pad %d", what, R, S, H, W, pad);
-        g.Ho = (H + 2 * pad - R) / stride + 1; g.Wo = (W + 2 * pad - S) / stride + 1; g.Ca = Cout; g.H = H; g.W = W; g.Cb = Cin;
-        a = dz; b = x;
-    }
-    g.M = (long long)N * g.Ho * g.Wo;
-    g.chunk = VATL_WGRAD_F64_CHUNK;
-    g.R = R; g.S = S; g.stride = stride; g.pad = pad; g.ncol = R * S * g.Cb;
-    const long long splits = wgrad_f64_splits(g.M);
-    if (g.M >= (1LL << 31) || (long long)N * g.H * g.W * g.Cb >= (1LL << 40) || g.M * g.Ca >= (1LL << 40) || splits > 65535 || cdiv(g.Ca, kWg64Tile) > 65535)
-        return fail(VATL_EINVAL, "%s: tensor too large", what);
-    const long long need = splits * g.Ca * g.ncol;
-    if (workspace_doubles < need) return fail(VATL_EINVAL, "%s: the workspace holds %lld doubles, %lld are needed", what, (long long)workspace_doubles, need);
-    const dim3 grid((unsigned)cdiv(g.ncol, kWg64Tile), (unsigned)cdiv(g.Ca, kWg64Tile), (unsigned)splits);
-    hipLaunchKernelGGL(wgrad_f64_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, b, workspace, g);
+    WgradGeom g;
+    if (const int rc = wgrad_geom(what, VATL_WGRAD_F64_CHUNK, N, H, W, Cin, Cout, R, S, stride, pad, transposed, &g)) return rc;
+    if (cdiv(g.Ca, kWg64Tile) > 65535) return fail(VATL_EINVAL, "%s: tensor too large", what);
+    if (const int rc = wgrad_workspace_contract(what, "doubles", workspace_doubles, g)) return rc;
+    hipLaunchKernelGGL(wgrad_f64_kernel, wgrad_grid(g, kWg64Tile), dim3(256), 0, (hipStream_t)stream, transposed ? x : dz, transposed ? dz : x, workspace, g);
     return check_launch(what);
 }
 
 extern "C" int vatl_wgrad_f64_reduce(const double* workspace, double* dw, int64_t M, int Cout, int Cin, int R, int S, int transposed, void* stream) {
-    if (!workspace || !dw || M < 1 || Cout < 1 || Cin < 1 || R < 1 || S < 1) return fail(VATL_EINVAL, "wgrad_f64_reduce: bad arguments");
-    const int rows = transposed ? Cin : Cout, cols = transposed ? Cout : Cin;
-    const long long total = (long long)rows * cols * R * S;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wgrad_f64_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, workspace, dw, (int)wgrad_f64_splits(M), rows, cols, R * S);
-    return check_launch("wgrad_f64_reduce");
+    return wgrad_reduce("wgrad_f64_reduce", workspace, dw, M, VATL_WGRAD_F64_CHUNK, Cout, Cin, R, S, transposed, 1, stream);
 }

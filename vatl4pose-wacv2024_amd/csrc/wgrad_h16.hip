@@ -27,19 +27,12 @@
 // parities the two halves of the 64 banks — conflict-free by construction.
 // Operand lane maps (as conv_h16.hip): A[row lane&15][k 8(lane>>4)+j], B[k 8(lane>>4)+j][col lane&15]; result col lane&15, row 4(lane>>4)+reg.
 #include "h16.h"
+#include "wgrad_generic.h"
 
 namespace vatl {
 
 constexpr int kWgTile = 64;                      // rows and columns of a block's tile, and pixels per staged image
 typedef short wg_s16x4 __attribute__((ext_vector_type(4)));
-
-struct WgradH16Geom {
-    long long M;                                 // pixels of the dz side
-    int chunk;                                   // pixels per split
-    int Ho, Wo, Ca;                              // dz side: plane and stored channels (rows of the GEMM)
-    int H, W, Cb;                                // x side: plane and stored channels
-    int R, S, stride, pad, ncol;                 // ncol = R*S*Cb
-};
 
 __device__ __forceinline__ int wg_swz(int row, int ch) { return ch ^ ((((row >> 1) & 1) | (((row >> 3) & 1) << 1)) << 1); }
 
@@ -60,7 +53,7 @@ __device__ __forceinline__ h16_u32x4 wg_frag(const unsigned short* img, int k0, 
 
 template <typename T>
 __global__ __launch_bounds__(256) void wgrad_h16_kernel(const unsigned short* __restrict__ a, const unsigned short* __restrict__ b, float* __restrict__ ws,
-                                                        WgradH16Geom g) {
+                                                        WgradGeom g) {
     __shared__ __attribute__((aligned(16))) unsigned short As[kWgTile * kWgTile];
     __shared__ __attribute__((aligned(16))) unsigned short Bs[kWgTile * kWgTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -148,32 +141,14 @@ __global__ __launch_bounds__(256) void wgrad_h16_kernel(const unsigned short* __
         }
 }
 
-// dw[row][c][r][s] = sum over splits, ascending, of ws[split][row][r][s][c] for row < rows, c < cols: thread per output element, in the
-// workspace's order (c fastest): the reads — `splits` times the bytes of the writes — are the coalesced side
-__global__ void wgrad_h16_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int splits, int rows, int cols, int rows8, int cols8, int RS) {
-    const long long total = (long long)rows * cols * RS, slab = (long long)rows8 * RS * cols8;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int c = (int)(i % cols);
-        const long long t = i / cols;
-        const int tap = (int)(t % RS);
-        const long long row = t / RS;
-        const float* src = ws + (row * RS + tap) * cols8 + c;
-        float s = 0.f;
-        for (int k = 0; k < splits; ++k) s += src[k * slab];
-        dw[(row * cols + c) * RS + tap] = s;
-    }
-}
-
-static inline long long wgrad_h16_splits(long long M) { return M <= 0 ? 0 : (M + VATL_WGRAD_H16_CHUNK - 1) / VATL_WGRAD_H16_CHUNK; }
-
 }  // namespace vatl
 
 using namespace vatl;
 
-extern "C" int64_t vatl_wgrad_h16_splits(int64_t M) { return wgrad_h16_splits(M); }
+extern "C" int64_t vatl_wgrad_h16_splits(int64_t M) { return wgrad_splits(M, VATL_WGRAD_H16_CHUNK); }
 
 extern "C" int64_t vatl_conv2d_wgrad_h16_workspace_floats(int Cout8, int Cin8, int R, int S, int64_t M) {
-    return wgrad_h16_splits(M) * (int64_t)Cout8 * R * S * Cin8;
+    return wgrad_splits(M, VATL_WGRAD_H16_CHUNK) * (int64_t)Cout8 * R * S * Cin8;
 }
 
 extern "C" int vatl_conv2d_wgrad_h16(const void* x, const void* dz, float* workspace, int64_t workspace_floats, int N, int H, int W, int Cin8, int Cout8, int R,
@@ -185,42 +160,16 @@ extern "C" int vatl_conv2d_wgrad_h16(const void* x, const void* dz, float* works
     if (Cin8 < 8 || (Cin8 & 7)) return fail(VATL_EINVAL, "%s: Cin %d is not a multiple of 8 (pad the input with zero channels)", what, Cin8);
     if (Cout8 < 8 || (Cout8 & 7)) return fail(VATL_EINVAL, "%s: Cout %d is not a multiple of 8 (pad the output gradient with zero channels)", what, Cout8);
     if (!h16_aligned16(x) || !h16_aligned16(dz) || (reinterpret_cast<uintptr_t>(workspace) & 3u)) return fail(VATL_EINVAL, "%s: 16-bit tensors must be 16-byte aligned", what);
-    if (N < 1 || H < 1 || W < 1 || R < 1 || S < 1 || R > 7 || S > 7 || (stride != 1 && stride != 2) || pad < 0)
-        return fail(VATL_EINVAL, "%s: N %d, %dx%d, %dx%d / %d, pad %d is not served (R, S <= 7, stride 1 or 2)", what, N, H, W, R, S, stride, pad);
-    WgradH16Geom g{};
-    const void *a, *b;
-    if (transposed) {                                     // ConvTranspose2d(4,2,1): the forward input is the dz side of a 4x4 / 2 / pad 1 conv of the output gradient
-        if (R != 4 || S != 4 || stride != 2 || pad != 1) return fail(VATL_EINVAL, "%s: the transposed form serves ConvTranspose2d(4, 2, 1) only", what);
-        g.Ho = H; g.Wo = W; g.Ca = Cin8; g.H = 2 * H; g.W = 2 * W; g.Cb = Cout8;
-        a = x; b = dz;
-    } else {
-        if (H + 2 * pad < R || W + 2 * pad < S) return fail(VATL_EINVAL, "%s: a %dx%d filter does not fit a %dx%d plane with pad %d", what, R, S, H, W, pad);
-        g.Ho = (H + 2 * pad - R) / stride + 1; g.Wo = (W + 2 * pad - S) / stride + 1; g.Ca = Cout8; g.H = H; g.W = W; g.Cb = Cin8;
-        a = dz; b = x;
-    }
-    g.M = (long long)N * g.Ho * g.Wo;
-    g.chunk = VATL_WGRAD_H16_CHUNK;
-    g.R = R; g.S = S; g.stride = stride; g.pad = pad; g.ncol = R * S * g.Cb;
-    const long long splits = wgrad_h16_splits(g.M);
-    if (g.M >= (1LL << 31) || (long long)N * g.H * g.W * g.Cb >= (1LL << 40) || g.M * g.Ca >= (1LL << 40) || splits > 65535)
-        return fail(VATL_EINVAL, "%s: tensor too large", what);
-    const long long need = splits * g.Ca * g.ncol;
-    if (workspace_floats < need) return fail(VATL_EINVAL, "%s: the workspace holds %lld floats, %lld are needed", what, (long long)workspace_floats, need);
-    const dim3 grid((unsigned)cdiv(g.ncol, kWgTile), (unsigned)cdiv(g.Ca, kWgTile), (unsigned)splits);
-    const unsigned short *as = (const unsigned short*)a, *bs = (const unsigned short*)b;
+    WgradGeom g;
+    if (const int rc = wgrad_geom(what, VATL_WGRAD_H16_CHUNK, N, H, W, Cin8, Cout8, R, S, stride, pad, transposed, &g)) return rc;
+    if (const int rc = wgrad_workspace_contract(what, "floats", workspace_floats, g)) return rc;
+    const dim3 grid = wgrad_grid(g, kWgTile);
+    const unsigned short *as = (const unsigned short*)(transposed ? x : dz), *bs = (const unsigned short*)(transposed ? dz : x);
     if (dtype == kH16F16) hipLaunchKernelGGL(wgrad_h16_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, as, bs, workspace, g);
     else hipLaunchKernelGGL(wgrad_h16_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, as, bs, workspace, g);
     return check_launch(what);
 }
 
 extern "C" int vatl_wgrad_h16_reduce(const float* workspace, float* dw, int64_t M, int Cout, int Cin, int R, int S, int transposed, void* stream) {
-    if (!workspace || !dw || M < 1 || Cout < 1 || Cin < 1 || R < 1 || S < 1) return fail(VATL_EINVAL, "wgrad_h16_reduce: bad arguments");
-    const int rows = transposed ? Cin : Cout, cols = transposed ? Cout : Cin;
-    const int rows8 = (rows + 7) & ~7, cols8 = (cols + 7) & ~7;
-    const long long total = (long long)rows * cols * R * S;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wgrad_h16_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, workspace, dw, (int)wgrad_h16_splits(M), rows, cols, rows8,
-                       cols8, R * S);
-    return check_launch("wgrad_h16_reduce");
+    return wgrad_reduce("wgrad_h16_reduce", workspace, dw, M, VATL_WGRAD_H16_CHUNK, Cout, Cin, R, S, transposed, 8, stream);
 }

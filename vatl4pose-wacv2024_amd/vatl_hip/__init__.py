@@ -2484,6 +2484,52 @@ def fuse_upsample_add_f64(base, ups, relu: bool):
 
 # float64 reference gradients (csrc/wgrad_f64.hip, csrc/train_glue_f64.hip, the data-gradient launcher of csrc/conv_f64.hip)
 
+def _wgrad_shapes(who: str, x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: int, transposed: bool, out, align: int, dtype):
+    """The shape contract of conv2d_wgrad_{f64,h16} (channels stored in multiples of ``align``) -> (n, h, w) of x, the pixels m of the dz
+    side, the stored rows and columns of the GEMM, and ``out`` (allocated as ``dtype`` in the parameter's shape where None)."""
+    n, h, w, cx = x.shape
+    cz = dz.shape[-1]
+    cin_s, cout_s = -(-cin // align) * align, -(-cout // align) * align
+    if cx != cin_s or cz != cout_s:
+        raise VatlError(f"{who}: tensors carry {cx} / {cz} channels, the filter has {cin} / {cout}")
+    if transposed:
+        want, m, rows, cols, shape = (n, 2 * h, 2 * w, cout_s), n * h * w, cin_s, cout_s, (cin, cout, 4, 4)
+    else:
+        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+        want, m, rows, cols, shape = (n, ho, wo, cout_s), n * ho * wo, cout_s, cin_s, (cout, cin, r, s)
+    if tuple(dz.shape) != want:
+        raise VatlError(f"{who}: dz has shape {tuple(dz.shape)}, expected {want}")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=dtype)
+    elif tuple(out.shape) != shape:
+        raise VatlError(f"{who}: out has shape {tuple(out.shape)}, expected {shape}")
+    return (n, h, w), m, rows, cols, out
+
+
+def _dgrad_shapes(who: str, dz, w_dgrad, xshape, r: int, s: int, stride: int, pad: int, residual):
+    """The shape contract of conv2d_dgrad_{f64,h16} -> (n, h, w, cin, cout), channels as stored."""
+    n, h, w, cin = xshape
+    cout = dz.shape[-1]
+    ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+    if tuple(dz.shape) != (n, ho, wo, cout) or w_dgrad.numel() != cin * r * s * cout:
+        raise VatlError(f"{who}: dz {tuple(dz.shape)} / filter of {w_dgrad.numel()} elements do not match input {tuple(xshape)}")
+    if residual is not None and tuple(residual.shape) != (n, h, w, cin):
+        raise VatlError(f"{who}: residual has shape {tuple(residual.shape)}, expected {(n, h, w, cin)}")
+    return n, h, w, cin, cout
+
+
+def _maxpool_bwd_shapes(who: str, dpool, x):
+    n, h, w, c = x.shape
+    if tuple(dpool.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
+        raise VatlError(f"{who}: dpool has shape {tuple(dpool.shape)}")
+    return n, h, w, c
+
+
+def _bn_ws(m: int, c: int, device, kind: str):
+    """The float64 row-block partials of the BatchNorm / column reductions of the ``kind`` ("f64", "h16") training glue."""
+    return torch.empty(int(getattr(lib(), f"vatl_bn_{kind}_workspace_doubles")(m, c)), device=device, dtype=torch.float64)
+
+
 def wgrad_f64_splits(m: int) -> int:
     return int(lib().vatl_wgrad_f64_splits(m))
 
@@ -2491,21 +2537,7 @@ def wgrad_f64_splits(m: int) -> int:
 def conv2d_wgrad_f64(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pad: int, transposed: bool = False, out=None):
     """Weight gradient in float64: (cout,cin,r,s) from x (N,H,W,cin) and dz (N,Ho,Wo,cout); ``transposed``: ConvTranspose2d(4,2,1)
     with x its forward input and dz (N,2H,2W,cout) its output gradient -> (cin,cout,4,4)."""
-    n, h, w, cx = x.shape
-    cz = dz.shape[-1]
-    if cx != cin or cz != cout:
-        raise VatlError(f"conv2d_wgrad_f64: tensors carry {cx} / {cz} channels, the filter has {cin} / {cout}")
-    if transposed:
-        want, m, rows, cols, shape = (n, 2 * h, 2 * w, cout), n * h * w, cin, cout, (cin, cout, 4, 4)
-    else:
-        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
-        want, m, rows, cols, shape = (n, ho, wo, cout), n * ho * wo, cout, cin, (cout, cin, r, s)
-    if tuple(dz.shape) != want:
-        raise VatlError(f"conv2d_wgrad_f64: dz has shape {tuple(dz.shape)}, expected {want}")
-    if out is None:
-        out = _new_f64(shape, x)
-    elif tuple(out.shape) != shape:
-        raise VatlError(f"conv2d_wgrad_f64: out has shape {tuple(out.shape)}, expected {shape}")
+    (n, h, w), m, rows, cols, out = _wgrad_shapes("conv2d_wgrad_f64", x, dz, cout, cin, r, s, stride, pad, transposed, out, 1, torch.float64)
     doubles = int(lib().vatl_conv2d_wgrad_f64_workspace_doubles(rows, cols, r, s, m))
     ws = _new_f64((doubles,), x)
     _check(lib().vatl_conv2d_wgrad_f64(_f64(x), _f64(dz), _f64(ws), doubles, n, h, w, cin, cout, r, s, stride, pad, int(transposed), _stream()),
@@ -2524,21 +2556,11 @@ def pack_conv_weight_dgrad_f64(w: torch.Tensor, stride: int, pad: int) -> torch.
 
 def conv2d_dgrad_f64(dz, w_dgrad, xshape, r: int, s: int, stride: int, pad: int, residual=None):
     """dx (N,H,W,Cin) = data gradient of a (r x s, stride, pad) conv from dz (N,Ho,Wo,Cout); ``residual`` shaped like dx is added."""
-    n, h, w, cin = xshape
-    cout = dz.shape[-1]
-    ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
-    if tuple(dz.shape) != (n, ho, wo, cout) or w_dgrad.numel() != cin * r * s * cout:
-        raise VatlError(f"conv2d_dgrad_f64: dz {tuple(dz.shape)} / filter of {w_dgrad.numel()} elements do not match input {tuple(xshape)}")
-    if residual is not None and tuple(residual.shape) != (n, h, w, cin):
-        raise VatlError(f"conv2d_dgrad_f64: residual has shape {tuple(residual.shape)}, expected {(n, h, w, cin)}")
+    n, h, w, cin, cout = _dgrad_shapes("conv2d_dgrad_f64", dz, w_dgrad, xshape, r, s, stride, pad, residual)
     dx = _new_f64((n, h, w, cin), dz)
     _check(lib().vatl_conv2d_dgrad_f64(_f64(dz), _f64(w_dgrad), _f64(residual), _f64(dx), n, h, w, cin, cout, r, s, stride, pad, _stream()),
            "vatl_conv2d_dgrad_f64")
     return dx
-
-
-def _bn_ws_f64(m: int, c: int, like):
-    return _new_f64((int(lib().vatl_bn_f64_workspace_doubles(m, c)),), like)
 
 
 def bn_train_fwd_stats_f64(z, gamma, beta, running_mean, running_var, momentum: float, eps: float):
@@ -2551,7 +2573,7 @@ def bn_train_fwd_stats_f64(z, gamma, beta, running_mean, running_var, momentum: 
             raise VatlError(f"bn_train_fwd_stats_f64: {name} has {t.numel()} elements, z {c} channels")
     out = _new_f64((7, c), z)
     _check(lib().vatl_bn_train_fwd_stats_f64(_f64(z), m, c, _f64(gamma), _f64(beta), _f64(running_mean), _f64(running_var), float(momentum), float(eps),
-                                             _f64(out), _f64(_bn_ws_f64(m, c, z)), _stream()), "vatl_bn_train_fwd_stats_f64")
+                                             _f64(out), _f64(_bn_ws(m, c, z.device, "f64")), _stream()), "vatl_bn_train_fwd_stats_f64")
     return out
 
 
@@ -2574,15 +2596,13 @@ def bn_train_bwd_f64(dy, y, z, gamma, save_mean, save_invstd, want_g: bool = Fal
     g = torch.empty_like(z) if want_g else None
     dgamma, dbeta = _new_f64((c,), z), _new_f64((c,), z)
     _check(lib().vatl_bn_train_bwd_f64(_f64(dy), _f64(y), _f64(z), _f64(gamma), _f64(save_mean), _f64(save_invstd), _f64(dz), _f64(g), _f64(dgamma),
-                                       _f64(dbeta), m, c, _f64(_bn_ws_f64(m, c, z)), _stream()), "vatl_bn_train_bwd_f64")
+                                       _f64(dbeta), m, c, _f64(_bn_ws(m, c, z.device, "f64")), _stream()), "vatl_bn_train_bwd_f64")
     return dz, g, dgamma, dbeta
 
 
 def maxpool3x3s2_bwd_f64(dpool, x):
     """Gradient of MaxPool2d(3,2,1)'s input x (N,H,W,C) from dpool: first maximum in scan order takes it (torch's tie rule)."""
-    n, h, w, c = x.shape
-    if tuple(dpool.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
-        raise VatlError(f"maxpool3x3s2_bwd_f64: dpool has shape {tuple(dpool.shape)}")
+    n, h, w, c = _maxpool_bwd_shapes("maxpool3x3s2_bwd_f64", dpool, x)
     dx = torch.empty_like(x)
     _check(lib().vatl_maxpool3x3s2_bwd_f64(_f64(dpool), _f64(x), _f64(dx), n, h, w, c, _stream()), "vatl_maxpool3x3s2_bwd_f64")
     return dx
@@ -2593,7 +2613,7 @@ def col_sum_f64(x2d):
     c = x2d.shape[-1]
     m = x2d.numel() // c
     out = _new_f64((c,), x2d)
-    _check(lib().vatl_col_sum_f64(_f64(x2d), m, c, _f64(out), _f64(_bn_ws_f64(m, c, x2d)), _stream()), "vatl_col_sum_f64")
+    _check(lib().vatl_col_sum_f64(_f64(x2d), m, c, _f64(out), _f64(_bn_ws(m, c, x2d.device, "f64")), _stream()), "vatl_col_sum_f64")
     return out
 
 
@@ -2762,21 +2782,8 @@ def conv2d_wgrad_h16(x, dz, cout: int, cin: int, r: int, s: int, stride: int, pa
     ConvTranspose2d(4,2,1) with x its forward input and dz (N,2H,2W,Cout8) its output gradient -> (cin,cout,4,4)."""
     t = x.dtype
     code = _h16_code(t)
-    n, h, w, cin8 = x.shape
-    cout8 = dz.shape[-1]
-    if cin8 != _pad8(cin) or cout8 != _pad8(cout):
-        raise VatlError(f"conv2d_wgrad_h16: tensors carry {cin8} / {cout8} channels, the filter has {cin} / {cout}")
-    if transposed:
-        want, m, rows8, cols8, shape = (n, 2 * h, 2 * w, cout8), n * h * w, cin8, cout8, (cin, cout, 4, 4)
-    else:
-        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
-        want, m, rows8, cols8, shape = (n, ho, wo, cout8), n * ho * wo, cout8, cin8, (cout, cin, r, s)
-    if tuple(dz.shape) != want:
-        raise VatlError(f"conv2d_wgrad_h16: dz has shape {tuple(dz.shape)}, expected {want}")
-    if out is None:
-        out = torch.empty(shape, device=x.device, dtype=torch.float32)
-    elif tuple(out.shape) != shape:
-        raise VatlError(f"conv2d_wgrad_h16: out has shape {tuple(out.shape)}, expected {shape}")
+    (n, h, w), m, rows8, cols8, out = _wgrad_shapes("conv2d_wgrad_h16", x, dz, cout, cin, r, s, stride, pad, transposed, out, 8, torch.float32)
+    cin8, cout8 = x.shape[-1], dz.shape[-1]
     floats = int(lib().vatl_conv2d_wgrad_h16_workspace_floats(rows8, cols8, r, s, m))
     ws = torch.empty(floats, device=x.device, dtype=torch.float32)
     _check(lib().vatl_conv2d_wgrad_h16(_ptr(x, t), _ptr(dz, t), _ptr(ws), floats, n, h, w, cin8, cout8, r, s, stride, pad, int(transposed), code, _stream()),
@@ -2914,21 +2921,11 @@ def conv2d_dgrad_h16(dz, w_dgrad, xshape, r: int, s: int, stride: int, pad: int,
     """dx (N,H,W,Cin8) = data gradient of a (r x s, stride, pad) conv from dz (N,Ho,Wo,Cout8); ``residual`` shaped like dx is added."""
     t = dz.dtype
     code = _h16_code(t)
-    n, h, w, cin8 = xshape
-    cout8 = dz.shape[-1]
-    ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
-    if tuple(dz.shape) != (n, ho, wo, cout8) or w_dgrad.numel() != cin8 * r * s * cout8:
-        raise VatlError(f"conv2d_dgrad_h16: dz {tuple(dz.shape)} / filter of {w_dgrad.numel()} elements do not match input {tuple(xshape)}")
-    if residual is not None and tuple(residual.shape) != (n, h, w, cin8):
-        raise VatlError(f"conv2d_dgrad_h16: residual has shape {tuple(residual.shape)}, expected {(n, h, w, cin8)}")
+    n, h, w, cin8, cout8 = _dgrad_shapes("conv2d_dgrad_h16", dz, w_dgrad, xshape, r, s, stride, pad, residual)
     dx = _new_like((n, h, w, cin8), dz)
     _check(lib().vatl_conv2d_dgrad_h16(_ptr(dz, t), _ptr(w_dgrad, t), _ptr(residual, t), _ptr(dx, t), n, h, w, cin8, cout8, r, s, stride, pad, code, _stream()),
            "vatl_conv2d_dgrad_h16")
     return dx
-
-
-def _bn_ws_h16(m: int, c: int, device):
-    return torch.empty(int(lib().vatl_bn_h16_workspace_doubles(m, c)), device=device, dtype=torch.float64)
 
 
 def bn_train_fwd_stats_h16(z, gamma, beta, running_mean, running_var, momentum: float, eps: float):
@@ -2938,7 +2935,7 @@ def bn_train_fwd_stats_h16(z, gamma, beta, running_mean, running_var, momentum: 
     m = z.numel() // c
     outs = [torch.empty(c, device=z.device, dtype=torch.float32) for _ in range(4)]
     _check(lib().vatl_bn_train_fwd_stats_h16(_ptr(z, z.dtype), m, c, _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), momentum, eps,
-                                             _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(_bn_ws_h16(m, c, z.device), torch.float64), code,
+                                             _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(_bn_ws(m, c, z.device, "h16"), torch.float64), code,
                                              _stream()), "vatl_bn_train_fwd_stats_h16")
     return outs
 
@@ -2961,7 +2958,7 @@ def bn_train_bwd_h16(dy, y, z, gamma, save_mean, save_invstd, want_g: bool = Fal
     dz, dgamma, dbeta, coef = _bn_bwd_outs(z, dgamma, dbeta)
     g = torch.empty_like(z) if want_g else None
     _check(lib().vatl_bn_train_bwd_h16(_ptr(dy, t), _ptr(y, t), _ptr(z, t), _ptr(gamma), _ptr(save_mean), _ptr(save_invstd), _ptr(dz, t), _ptr(g, t),
-                                       _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _ptr(_bn_ws_h16(m, c, z.device), torch.float64), code, _stream()),
+                                       _ptr(dgamma), _ptr(dbeta), m, c, _ptr(coef), _ptr(_bn_ws(m, c, z.device, "h16"), torch.float64), code, _stream()),
            "vatl_bn_train_bwd_h16")
     return dz, g, dgamma, dbeta
 
@@ -2969,9 +2966,7 @@ def bn_train_bwd_h16(dy, y, z, gamma, save_mean, save_invstd, want_g: bool = Fal
 def maxpool3x3s2_bwd_h16(dpool, x):
     """Gradient of MaxPool2d(3,2,1)'s input x (N,H,W,C) from dpool: first maximum in scan order takes it (torch's tie rule)."""
     code = _h16_code(x.dtype)
-    n, h, w, c = x.shape
-    if tuple(dpool.shape) != (n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
-        raise VatlError(f"maxpool3x3s2_bwd_h16: dpool has shape {tuple(dpool.shape)}")
+    n, h, w, c = _maxpool_bwd_shapes("maxpool3x3s2_bwd_h16", dpool, x)
     dx = torch.empty_like(x)
     _check(lib().vatl_maxpool3x3s2_bwd_h16(_ptr(dpool, x.dtype), _ptr(x, x.dtype), _ptr(dx, x.dtype), n, h, w, c, code, _stream()), "vatl_maxpool3x3s2_bwd_h16")
     return dx
