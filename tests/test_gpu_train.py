@@ -575,11 +575,9 @@ def _expect_deconv_pack(vh, w):
 
 
 def _expect_dgrad_pack(vh, w, taps):
-    cout, cin = w.shape[:2]
-    out = np.zeros((vh.conv_cout_pad(cin), len(taps), cout), np.float32)
-    for t, (r, s) in enumerate(taps):
-        out[:cin, t, :] = w[:, :, r, s].T
-    return out
+    from tests import dgrad_cases                          # the layout is stated once, and held to autograd in tests/test_dgrad_cpu.py
+    assert vh.conv_cout_pad(w.shape[1]) == dgrad_cases.cout_pad(w.shape[1])
+    return dgrad_cases.expect_dgrad_pack(w, taps)
 
 
 _FLIPPED9 = [(2 - r, 2 - s) for r in range(3) for s in range(3)]
