@@ -1,7 +1,7 @@
-"""fp32 data gradients (alphapose/models/hip_train.py: _ConvBN._dgrad, the launch logic on vatl_conv2d_fwd_ex and the F(2x2,3x3) data-gradient
-filter): the seeded cases of tests/test_dgrad_cpu.py and tests/test_gpu_dgrad.py, one per launch branch, a float64 reference, and a host
-restatement of everything between the layer and the kernel.  The module imports no library: it is proved against autograd on the host
-(tests/test_dgrad_cpu.py) before the GPU test holds the library to it.
+"""fp32 data gradients (alphapose/models/hip_train.py: _ConvBN._dgrad — _igemm_dgrad, the launch logic on vatl_conv2d_fwd_ex every layer class
+shares, and the F(2x2,3x3) data-gradient filter): the seeded cases of tests/test_dgrad_cpu.py and tests/test_gpu_dgrad.py, one per launch
+branch, a float64 reference, and a host restatement of everything between the layer and the kernel.  The module imports no library: it is
+proved against autograd on the host (tests/test_dgrad_cpu.py) before the GPU test holds the library to it.
 
     dx[b][iy][ix][c] = sum_{n, r, s} dz[b][oy][ox][n] * w[n][c][r][s]   with (iy, ix) = (oy*stride - pad + r, ox*stride - pad + s)   (+ residual)
     dz (N, Ho, Wo, CoutK)   NHWC gradient of the conv's output; CoutK >= Cout is what the tensor carries (the 17-joint head and the DCN offset conv
@@ -11,8 +11,9 @@ restatement of everything between the layer and the kernel.  The module imports 
 
 A case is ``Case(route, n, h, w, cin, cout, k, stride, pad, coutk, via, knobs, scope)``: n, h, w are the layer INPUT's (= dx's).  ``route`` is the
 route counter the case must bump, ``via`` says who issues the launches ("layer": _ConvBN._dgrad; "direct": the launches of ``launches(case)`` on
-conv2d_fwd_ex with ``cout_k``, as _DeformConvBN.backward and the head do), ``knobs`` the product knobs set for the run (all documented
-bit-identical), ``scope`` whether the run is inside vatl_hip.streamk_scope.  Inputs are regenerated from the case's seed, never stored.
+conv2d_fwd_ex with ``cout_k``, which must equal what _igemm_dgrad issues with the ``cout_k`` _DeformConvBN.backward and the head pass),
+``knobs`` the product knobs set for the run (all documented bit-identical), ``scope`` whether the run is inside vatl_hip.streamk_scope.
+Inputs are regenerated from the case's seed, never stored.
 """
 import zlib
 from collections import Counter, namedtuple
@@ -124,7 +125,7 @@ PHASE_TAPS = {0: [1], 1: [2, 0]}      # 3x3 / stride 2 / pad 1, per input parity
 
 
 def launches(case):
-    """The conv2d_fwd_ex launches _ConvBN._dgrad issues (for a Winograd case: the stride-1 launch that computes the same tensor)."""
+    """The conv2d_fwd_ex launches hip_train._igemm_dgrad issues (for a Winograd case: the stride-1 launch that computes the same tensor)."""
     c = case
     ho, wo = out_size(c)
     if c.stride == 1:
@@ -173,7 +174,7 @@ def fwd_ex_model(x, wp, cout, L, out, residual=None):
 
 
 def dgrad_model(case, dz, w, residual=None, only=None):
-    """_ConvBN._dgrad on the host model, float64: the output starts as NaN (stride 1 and the four phases must write every pixel), as zeros
+    """hip_train._igemm_dgrad on the host model, float64: the output starts as NaN (stride 1 and the four phases must write every pixel), as zeros
     or as a clone of the residual (1x1 / stride 2).  ``only``: indices of the launches to issue."""
     c = case
     x = torch.from_numpy(np.asarray(dz, np.float64))

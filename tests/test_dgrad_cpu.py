@@ -1,5 +1,5 @@
 """tests/dgrad_cases.py before anything trusts it (no GPU): the host model of conv2d_fwd_ex on the host-stated filter packing, assembled as
-_ConvBN._dgrad assembles it, is float64 autograd; the impulse expectation is autograd of the impulse; the integer regime cannot round; the
+hip_train._igemm_dgrad assembles it, is float64 autograd; the impulse expectation is autograd of the impulse; the integer regime cannot round; the
 claims of the case comments follow from the restated dispatch rules; the restated launch logic is the trainer's, line for line."""
 import ast
 import os
@@ -154,16 +154,45 @@ def test_pack_layout_pads_with_zeros():
 
 
 def test_the_restated_launch_logic_is_the_trainers():
-    """The parts of hip_train.py this module restates, compared as source: the parity -> taps lists of _ConvBN._dgrad (and of
-    _DeformConvBN.backward, which repeats them) and _flipped_taps.  A change there must be made here as well, where autograd judges it."""
+    """The parts of hip_train.py this module restates, compared as source: the parity -> taps lists of _igemm_dgrad — the one place that
+    assembles an implicit-GEMM data gradient, for every layer class — and _flipped_taps.  A change there must be made here as well, where
+    autograd judges it.  And the BatchNorm backward's three-way choice and its fusion gate are each written in one function."""
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vatl4pose-wacv2024_amd", "alphapose", "models", "hip_train.py")
     tree = ast.parse(open(path).read())
-    found = {"rows": [], "cols": []}
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name) and node.targets[0].id in found and isinstance(node.value, ast.IfExp):
-            found[node.targets[0].id].append((ast.literal_eval(node.value.body), ast.literal_eval(node.value.orelse)))
+
+    def phase_lists(root):
+        found = {"rows": [], "cols": []}
+        for node in ast.walk(root):
+            if isinstance(node, ast.Assign) and isinstance(node.targets[0], ast.Name) and node.targets[0].id in found and isinstance(node.value, ast.IfExp):
+                found[node.targets[0].id].append((ast.literal_eval(node.value.body), ast.literal_eval(node.value.orelse)))
+        return found
     want = (D.PHASE_TAPS[0], D.PHASE_TAPS[1])
-    assert found["rows"] == [want, want] and found["cols"] == [want, want], found
+    dgrad = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "_igemm_dgrad")
+    assert phase_lists(tree) == phase_lists(dgrad) == {"rows": [want], "cols": [want]}
+
+    readers = {}                                                             # name -> [function that reads it (outermost def, Class.method for methods)]
+
+    def visit(node, where):
+        for child in ast.iter_child_nodes(node):
+            if isinstance(child, ast.ClassDef) and where is None:
+                visit(child, child.name + ".")
+            elif isinstance(child, ast.FunctionDef) and (where is None or where.endswith(".")):
+                visit(child, (where or "") + child.name)
+            else:
+                name = child.attr if isinstance(child, ast.Attribute) else child.id if isinstance(child, ast.Name) else None
+                if name is not None and isinstance(child.ctx, ast.Load):
+                    readers.setdefault(name, []).append(where)
+                visit(child, where)
+    visit(tree, None)
+    for name in ("pack_dgrad_weight", "conv2d_fwd_ex"):                      # the data-gradient launches: _igemm_dgrad alone
+        assert set(readers[name]) == {"_igemm_dgrad"}, (name, readers[name])
+    # ... and the transposed conv's 4x4 / stride-2 conv on the forward packing, a geometry of its own
+    assert sorted(readers["conv2d_fwd_ex_bnbwd"]) == ["_DeconvBN.backward", "_igemm_dgrad"], readers["conv2d_fwd_ex_bnbwd"]
+    for name in ("bn_bwd_from_stats", "bn_train_bwd_relu", "bn_train_bwd", "_FUSE_BN_MIN_C", "_FUSE_BN_BWD"):
+        assert len(set(readers[name])) == 1 and None not in readers[name], (name, readers[name])
+    assert set(readers["bn_bwd_from_stats"] + readers["bn_train_bwd_relu"] + readers["bn_train_bwd"]) == {"_bn_backward"}
+    assert set(readers["_FUSE_BN_MIN_C"] + readers["_FUSE_BN_BWD"]) == {"_bn_spec"}
+
     fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "_flipped_taps")
     ns = {}
     exec(compile(ast.Module([fn], []), path, "exec"), ns)

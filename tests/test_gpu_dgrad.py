@@ -85,8 +85,9 @@ def _layer(case, w):
 
 
 def _direct(vh, case, dz, w, res, only=None, out=None):
-    """The launches of D.launches(case) on conv2d_fwd_ex with the case's cout_k, as _DeformConvBN.backward and the head issue them (a
-    Winograd case: its one launch with ``out``)."""
+    """The launches of D.launches(case) on conv2d_fwd_ex with the case's cout_k, one by one: what lets a single phase and a caller's ``out``
+    be tested (a Winograd case: its one launch with ``out``).  hip_train._igemm_dgrad, which _DeformConvBN.backward and the head call with
+    their cout_k, must give the same bits (test_the_assembler_equals_the_direct_launches)."""
     c = case
     if D.is_winograd(c):
         return vh.conv3x3_winograd_fwd(dz, vh.pack_winograd_weight(w, data_gradient=True), None, None, c.cin, False, residual=res, out=out)
@@ -107,6 +108,25 @@ def _run(vh, case, dz, w, res, knobs=None, only=None, out=None):
         if case.via == "layer" and only is None and out is None:
             return _layer(case, w)._dgrad(dz, (case.n, case.h, case.w, case.cin), res)
         return _direct(vh, case, dz, w, res, only, out)
+
+
+DIRECT_CASES = [c for c in D.CASES if c.via != "layer"]
+
+
+@pytest.mark.parametrize("with_res", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("case", DIRECT_CASES, ids=ids(DIRECT_CASES))
+def test_the_assembler_equals_the_direct_launches(vh, case, with_res):
+    """hip_train._igemm_dgrad with the case's cout_k — the call of _DeformConvBN.backward (27 in 32 channels, stride 1 and 2) and of the
+    head (17 in 32) — against the launches of D.launches(case) issued here one by one: the same bits."""
+    from alphapose.models import hip_train
+    c = case
+    assert DIRECT_CASES and c.stride in (1, 2)
+    dz, w, res, _, _, _ = _data(c, "random")
+    r = res if with_res else None
+    with _setup(vh, c):
+        got = hip_train._igemm_dgrad(dz, w, (c.n, c.h, c.w, c.cin), c.k, c.k, c.stride, c.pad, residual=r, cout_k=c.coutk if c.coutk != c.cout else None)
+        want = _direct(vh, c, dz, w, r)
+    assert got.shape == want.shape and torch.equal(got, want)
 
 
 def _first_wrong(got, want):

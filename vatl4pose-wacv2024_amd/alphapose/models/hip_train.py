@@ -20,6 +20,8 @@ RETRAIN.OPTIMIZER SGD/Adam) are wired.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 
@@ -219,6 +221,93 @@ def _wino_wgrad_fits(xshape, mo: int) -> bool:
     return n * th * tw < (1 << 20) and n * th < (1 << 20)
 
 
+def _igemm_dgrad(dz, wt, xshape, r, s, stride, pad, residual=None, spec=None, cout_k=None):
+    """dx (xshape, NHWC) of a conv with filter wt (Cout,Cin,r,s) from its output gradient dz, on the implicit GEMM: stride 1 as one conv with the
+    flipped taps, stride 2 as launches over the dz grid that scatter to the input pixels of one parity (no zero stuffing).  ``residual`` (the skip
+    gradient) is added in the epilogue; ``spec``: the BnBwdSpec of the layer that receives dx — the launches then mask dx with its ReLU and run the
+    reduction pass of its BatchNorm backward; ``cout_k``: the channels dz carries when that is more than Cout (zeros behind Cout)."""
+    n, h, w, cin = xshape
+    ho, wo = dz.shape[1], dz.shape[2]
+
+    def conv(taps, *a, **k):
+        wd = vh.pack_dgrad_weight(wt, taps, cout_k=cout_k)
+        return vh.conv2d_fwd_ex_bnbwd(dz, wd, cin, *a, spec, **k) if spec is not None else vh.conv2d_fwd_ex(dz, wd, cin, *a, **k)
+    if stride == 1:
+        return conv(_flipped_taps(r, s), r, s, 1, r - 1 - pad, s - 1 - pad, h, w, h, w, 1, 1, 0, 0, residual=residual)
+    assert stride == 2 and h == 2 * ho and w == 2 * wo
+    if r == 1:                                            # 1x1/2 projection: only even pixels receive gradient
+        assert spec is None
+        # even pixels: dx = W^T dz + residual; the kernel reads the residual at the scattered positions
+        dx = torch.zeros((n, h, w, cin), device=dz.device, dtype=torch.float32) if residual is None else residual.clone()
+        return conv([(0, 0)], 1, 1, 1, 0, 0, ho, wo, h, w, 2, 2, 0, 0, out=dx, residual=residual)
+    assert r == 3 and pad == 1
+    dx = torch.empty((n, h, w, cin), device=dz.device, dtype=torch.float32)
+    for py in (0, 1):                                     # input-pixel parity -> which filter rows reach it
+        rows = [1] if py == 0 else [2, 0]                 # dz row y+t  <->  filter row rows[t]
+        for px in (0, 1):
+            cols = [1] if px == 0 else [2, 0]
+            conv([(a, b) for a in rows for b in cols], len(rows), len(cols), 1, 0, 0, ho, wo, h, w, 2, 2, py, px, out=dx, residual=residual)
+    return dx
+
+
+class _BnTape(NamedTuple):
+    """What a conv / deconv / deformable conv + BatchNorm(train) layer keeps for its backward."""
+    x: torch.Tensor                # (first: tests/test_gpu_train.py takes the layer input as saved[0])
+    z: torch.Tensor
+    mean: torch.Tensor
+    invstd: torch.Tensor
+    mask: tuple | None             # (scale, bias) — ReLU without a skip: the backward recomputes the mask from z and never reads y
+    y: torch.Tensor | None         # the output — ReLU after a skip sum.  Neither: no ReLU
+    had_skip: bool
+
+
+def _bn_args(bn):
+    """The BatchNorm arguments of the ``*_fwd_bnstats`` launches."""
+    return bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.momentum, bn.eps
+
+
+def _bn_forward(bn, x, stats, skip=None, relu=True):
+    """The tail of a layer's training forward, from ``stats`` = (z, mean, invstd, scale, bias) of the conv launch whose epilogue took the batch
+    statistics: y = relu(z*scale + bias (+ skip)) -> y, tape."""
+    z, mean, invstd, scale, bias = stats
+    _count_batch(bn)
+    y = vh.scale_bias_act(z, scale, bias, skip, relu)
+    if relu:
+        _tap(y)
+    return y, _BnTape(x, z, mean, invstd, (scale, bias) if (relu and skip is None) else None, y if (relu and skip is not None) else None, skip is not None)
+
+
+def _bn_spec(cout, tape):
+    """What the launch that PRODUCES a layer's output gradient needs in order to run the reduction pass of the layer's BatchNorm backward in
+    its own epilogue (the ``_bnbwd`` entries); taken before ``backward`` consumes the tape."""
+    if not _FUSE_BN_BWD or cout < _FUSE_BN_MIN_C:
+        return None
+    if tape.mask is not None:
+        return vh.BnBwdSpec(tape.z, tape.mean, tape.invstd, scale=tape.mask[0], bias=tape.mask[1])
+    return vh.BnBwdSpec(tape.z, tape.mean, tape.invstd, mask_y=tape.y)
+
+
+def _bn_backward(bn, tape, dy, grads, pre):
+    """BatchNorm(train) backward of a layer from the gradient dy of its output -> (dz, gradient of the skip input or None); dgamma and dbeta go
+    to ``grads``.  ``pre``: the spec this layer handed to the producer of dy — dy is then already masked and its (sum g, sum g*xhat) partials
+    are in ``pre``."""
+    gamma, og, ob = bn.weight.detach(), _gout(grads, bn.weight), _gout(grads, bn.bias)
+    if pre is not None:
+        dz, dgamma, dbeta = vh.bn_bwd_from_stats(pre, dy, gamma, dgamma=og, dbeta=ob)
+        g = dy if tape.had_skip else None
+    elif tape.mask is not None:
+        dz, dgamma, dbeta = vh.bn_train_bwd_relu(dy, tape.mask[0], tape.mask[1], tape.z, gamma, tape.mean, tape.invstd, dgamma=og, dbeta=ob)
+        g = None
+    else:
+        dz, g, dgamma, dbeta = vh.bn_train_bwd(dy, tape.y, tape.z, gamma, tape.mean, tape.invstd, want_g=tape.had_skip and tape.y is not None,
+                                               dgamma=og, dbeta=ob)
+    if tape.had_skip and tape.y is None:
+        g = dy                                             # no ReLU between the sum and the output: the skip gradient is dy
+    grads[bn.weight] = dgamma
+    grads[bn.bias] = dbeta
+    return dz, g
+
+
 class _ConvBN:
     """Conv2d (bias-free) + BatchNorm2d(train) (+ residual) (+ ReLU)."""
 
@@ -237,32 +326,19 @@ class _ConvBN:
     # ---- forward -------------------------------------------------------------
     def _igemm_bnstats(self, x):
         """z = conv(x) on the implicit GEMM with the batch statistics from its epilogue -> z, save_mean, save_invstd, scale, bias."""
-        bn = self.bn
         w = vh.pack_conv_weight(self.conv.weight.detach())
-        return vh.conv2d_fwd_bnstats(x, w, self.cout, self.r, self.s, self.stride, self.pad, bn.weight.detach(), bn.bias.detach(),
-                                     bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+        return vh.conv2d_fwd_bnstats(x, w, self.cout, self.r, self.s, self.stride, self.pad, *_bn_args(self.bn))
 
     def forward(self, x, skip=None, relu=None):
         relu = self.relu if relu is None else relu
-        bn = self.bn
         # z = conv(x); the batch statistics come out of the conv epilogue (no extra pass over z)
         if self.wino and self._f4(x.shape, self.cin, self.cout):
-            z, mean, invstd, scale, bias = vh.conv3x3_winograd_f4_fwd_bnstats(x, vh.pack_winograd_f4_weight(self.conv.weight.detach()), self.cout,
-                                                                              bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                                                              bn.momentum, bn.eps)
+            stats = vh.conv3x3_winograd_f4_fwd_bnstats(x, vh.pack_winograd_f4_weight(self.conv.weight.detach()), self.cout, *_bn_args(self.bn))
         elif self.wino:
-            z, mean, invstd, scale, bias = vh.conv3x3_winograd_fwd_bnstats(x, vh.pack_winograd_weight(self.conv.weight.detach()), self.cout,
-                                                                           bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                                                           bn.momentum, bn.eps)
+            stats = vh.conv3x3_winograd_fwd_bnstats(x, vh.pack_winograd_weight(self.conv.weight.detach()), self.cout, *_bn_args(self.bn))
         else:
-            z, mean, invstd, scale, bias = self._igemm_bnstats(x)
-        _count_batch(bn)
-        y = vh.scale_bias_act(z, scale, bias, skip, relu)
-        if relu:
-            _tap(y)
-        # ReLU without a skip: the backward recomputes the mask from (z, scale, bias) and never reads y
-        mask = (scale, bias) if (relu and skip is None) else None
-        self.saved = (x, z, y if (relu and skip is not None) else None, mean, invstd, skip is not None, mask)
+            stats = self._igemm_bnstats(x)
+        y, self.saved = _bn_forward(self.bn, x, stats, skip, relu)
         return y
 
     def forward_pool(self, x):
@@ -271,72 +347,47 @@ class _ConvBN:
         z, mean, invstd, scale, bias = self._igemm_bnstats(x)
         _count_batch(self.bn)
         y, idx = vh.maxpool3x3s2_fwd_idx_affine(z, scale, bias)
-        self.saved = (x, z, None, mean, invstd, False, (scale, bias))
+        self.saved = _BnTape(x, z, mean, invstd, (scale, bias), None, False)
         self.pool_idx = idx
         return y
 
     def backward_pool(self, dpool, grads):
         """Backward of forward_pool from the pooled output's gradient (no full-resolution gradient tensor).  The stem's own input
         gradient is never needed (need_dx False)."""
-        x, z, _, mean, invstd, _, mask = self.saved
-        self.saved = None
+        t, self.saved = self.saved, None
         idx, self.pool_idx = self.pool_idx, None
-        dz, dgamma, dbeta = vh.bn_train_bwd_relu_pool(dpool, idx, mask[0], mask[1], z, self.bn.weight.detach(), mean, invstd,
+        dz, dgamma, dbeta = vh.bn_train_bwd_relu_pool(dpool, idx, t.mask[0], t.mask[1], t.z, self.bn.weight.detach(), t.mean, t.invstd,
                                                       dgamma=_gout(grads, self.bn.weight), dbeta=_gout(grads, self.bn.bias))
         grads[self.bn.weight] = dgamma
         grads[self.bn.bias] = dbeta
-        cin_w = 3 if self.cin == 3 else self.cin
-        ow = _gout(grads, self.conv.weight)
-        grads[self.conv.weight] = _side.run(lambda: vh.conv2d_wgrad(x, dz, self.cout, cin_w, self.r, self.s, self.stride, self.pad, out=ow), x, dz)
+        self._wgrad(t.x, dz, grads, winograd=False)
         assert not self.need_dx
 
     # ---- backward ------------------------------------------------------------
     def bn_spec(self):
-        """What the launch that PRODUCES this layer's output gradient needs in order to run the reduction pass of this layer's
-        BatchNorm backward in its own epilogue (vatl_conv2d_fwd_ex_bnbwd); taken before ``backward`` consumes the tape."""
-        if not _FUSE_BN_BWD or self.cout < _FUSE_BN_MIN_C:
-            return None
-        x, z, y, mean, invstd, had_skip, mask = self.saved
-        if mask is not None:                               # ReLU, no skip: mask recomputed from z
-            return vh.BnBwdSpec(z, mean, invstd, scale=mask[0], bias=mask[1])
-        return vh.BnBwdSpec(z, mean, invstd, mask_y=y)     # ReLU after a skip sum (y saved), or no ReLU at all (y is None)
+        return _bn_spec(self.cout, self.saved)
 
     def backward(self, dy, grads, dx_residual=None, pre=None, consumer=None):
-        """dy: gradient of the layer output.  Returns (dx, g_skip); parameter gradients go to ``grads``.
-        ``pre``: the BnBwdSpec this layer handed to the producer of dy — dy is then already masked and its (sum g, sum g*xhat)
-        partials are in ``pre``.  ``consumer``: the BnBwdSpec of the layer that will receive dx."""
-        x, z, y, mean, invstd, had_skip, mask = self.saved
-        self.saved = None
-        og, ob = _gout(grads, self.bn.weight), _gout(grads, self.bn.bias)
-        if pre is not None:
-            dz, dgamma, dbeta = vh.bn_bwd_from_stats(pre, dy, self.bn.weight.detach(), dgamma=og, dbeta=ob)
-            g = dy if had_skip else None
-        elif mask is not None:
-            dz, dgamma, dbeta = vh.bn_train_bwd_relu(dy, mask[0], mask[1], z, self.bn.weight.detach(), mean, invstd, dgamma=og, dbeta=ob)
-            g = None
-        else:
-            dz, g, dgamma, dbeta = vh.bn_train_bwd(dy, y, z, self.bn.weight.detach(), mean, invstd, want_g=had_skip and y is not None,
-                                                   dgamma=og, dbeta=ob)
-        if had_skip and y is None:
-            g = dy                                         # no ReLU between the sum and the output: the skip gradient is dy
-        grads[self.bn.weight] = dgamma
-        grads[self.bn.bias] = dbeta
-        cin_w = 3 if self.cin == 3 else self.cin
-        ow = _gout(grads, self.conv.weight)
-        if self.wino and min(self.cin, self.cout) >= _WINOGRAD_WGRAD_MIN_C and _wino_wgrad_fits(x.shape, 2):      # transform-domain weight gradient (csrc/winograd_wgrad.hip)
-            grads[self.conv.weight] = _side.run(lambda: vh.conv3x3_winograd_wgrad(x, dz, out=ow), x, dz)
-        else:
-            grads[self.conv.weight] = _side.run(lambda: vh.conv2d_wgrad(x, dz, self.cout, cin_w, self.r, self.s, self.stride, self.pad, out=ow), x, dz)
-        dx = self._dgrad(dz, x.shape, dx_residual, consumer) if self.need_dx else None
+        """dy: gradient of the layer output.  Returns (dx, g_skip); parameter gradients go to ``grads``.  ``pre``: the BnBwdSpec this layer
+        handed to the producer of dy (_bn_backward).  ``consumer``: the BnBwdSpec of the layer that will receive dx."""
+        t, self.saved = self.saved, None
+        dz, g = _bn_backward(self.bn, t, dy, grads, pre)
+        self._wgrad(t.x, dz, grads)
+        dx = self._dgrad(dz, t.x.shape, dx_residual, consumer) if self.need_dx else None
         return dx, g
 
-    def _dgrad(self, dz, xshape, residual, spec=None):
-        n, h, w, cin = xshape
-        wt = self.conv.weight.detach()
-        ho, wo = dz.shape[1], dz.shape[2]
+    def _wgrad(self, x, dz, grads, winograd=True):
+        """dW = wgrad(x, dz) beside the critical chain (_SideStream); the filter's own channel count (the stem's x carries 4 channels, its
+        filter 3).  ``winograd`` False: the implicit GEMM whatever the layer."""
+        ow = _gout(grads, self.conv.weight)
+        if winograd and self.wino and min(self.cin, self.cout) >= _WINOGRAD_WGRAD_MIN_C and _wino_wgrad_fits(x.shape, 2):      # transform-domain weight gradient (csrc/winograd_wgrad.hip)
+            grads[self.conv.weight] = _side.run(lambda: vh.conv3x3_winograd_wgrad(x, dz, out=ow), x, dz)
+        else:
+            grads[self.conv.weight] = _side.run(lambda: vh.conv2d_wgrad(x, dz, self.cout, self.cin, self.r, self.s, self.stride, self.pad, out=ow), x, dz)
 
-        def conv(*a, **k):                                # with a consumer spec: mask + BatchNorm-backward reduction in the epilogue
-            return vh.conv2d_fwd_ex_bnbwd(*a, spec, **k) if spec is not None else vh.conv2d_fwd_ex(*a, **k)
+    def _dgrad(self, dz, xshape, residual, spec=None):
+        cin = xshape[3]
+        wt = self.conv.weight.detach()
         if self.wino and self._f4(dz.shape, self.cout, cin):           # the data gradient is a 3x3 conv of dz with cout input and cin output channels
             ud = vh.pack_winograd_f4_weight(wt, data_gradient=True)
             if spec is not None:
@@ -347,28 +398,7 @@ class _ConvBN:
             if spec is not None:
                 return vh.conv3x3_winograd_fwd_bnbwd(dz, ud, cin, spec, residual=residual)
             return vh.conv3x3_winograd_fwd(dz, ud, None, None, cin, False, residual=residual)
-        if self.stride == 1:
-            wd = vh.pack_dgrad_weight(wt, _flipped_taps(self.r, self.s))
-            return conv(dz, wd, cin, self.r, self.s, 1, self.r - 1 - self.pad, self.s - 1 - self.pad, h, w, h, w, 1, 1, 0, 0, residual=residual)
-        assert self.stride == 2 and h == 2 * ho and w == 2 * wo
-        if self.r == 1:                                   # 1x1/2 projection: only even pixels receive gradient
-            assert spec is None
-            dx = torch.zeros((n, h, w, cin), device=dz.device, dtype=torch.float32) if residual is None else residual.clone()
-            wd = vh.pack_dgrad_weight(wt, [(0, 0)])
-            res_view = None
-            if residual is not None:
-                # even pixels: dx = W^T dz + residual; the kernel reads the residual at the scattered positions
-                res_view = residual
-            return vh.conv2d_fwd_ex(dz, wd, cin, 1, 1, 1, 0, 0, ho, wo, h, w, 2, 2, 0, 0, out=dx, residual=res_view)
-        assert self.r == 3 and self.pad == 1
-        dx = torch.empty((n, h, w, cin), device=dz.device, dtype=torch.float32)
-        for py in (0, 1):                                 # input-pixel parity -> which filter rows reach it
-            rows = [1] if py == 0 else [2, 0]             # dz row y+t  <->  filter row rows[t]
-            for px in (0, 1):
-                cols = [1] if px == 0 else [2, 0]
-                wd = vh.pack_dgrad_weight(wt, [(a, b) for a in rows for b in cols])
-                conv(dz, wd, cin, len(rows), len(cols), 1, 0, 0, ho, wo, h, w, 2, 2, py, px, out=dx, residual=residual)
-        return dx
+        return _igemm_dgrad(dz, wt, xshape, self.r, self.s, self.stride, self.pad, residual, spec)
 
 
 class _DeformConvBN:
@@ -391,36 +421,24 @@ class _DeformConvBN:
 
     def forward(self, x):
         from .layers.dcn import columns_forward
-        bn = self.bn
         _, ob = vh.bn_fold(None, None, None, None, 0.0, self.off.bias.detach(), channels=self.offc)
         o = vh.conv2d_fwd(x, vh.pack_conv_weight(self.off.weight.detach()), None, ob, self.offc, 3, 3, self.stride, 1, False)
         col, wg = columns_forward(x, o, self.mask, self.conv.weight.detach(), self.stride, self.dg)
-        z, mean, invstd, scale, bias = vh.conv2d_fwd_bnstats(col, vh.pack_conv_weight(wg, planned=False), self.cout, 1, 1, 1, 0, bn.weight.detach(),
-                                                             bn.bias.detach(), bn.running_mean, bn.running_var, bn.momentum, bn.eps)
-        _count_batch(bn)
-        y = _tap(vh.scale_bias_act(z, scale, bias, None, True))
-        self.saved = (x, o, col, z, mean, invstd, (scale, bias))
+        stats = vh.conv2d_fwd_bnstats(col, vh.pack_conv_weight(wg, planned=False), self.cout, 1, 1, 1, 0, *_bn_args(self.bn))
+        y, tape = _bn_forward(self.bn, x, stats)
+        self.saved = (tape, o, col)
         return y
 
     def bn_spec(self):
-        if not _FUSE_BN_BWD or self.cout < _FUSE_BN_MIN_C:
-            return None
-        z, mean, invstd, mask = self.saved[3:]
-        return vh.BnBwdSpec(z, mean, invstd, scale=mask[0], bias=mask[1])
+        return _bn_spec(self.cout, self.saved[0])
 
     def backward(self, dy, grads, pre=None, consumer=None):
         """-> (gradient of the block's conv1 output, None).  ``consumer`` is not served: the caller runs conv1's BatchNorm backward unfused."""
         from .layers.dcn import columns_backward, is_deterministic
         assert consumer is None
-        x, o, col, z, mean, invstd, mask = self.saved
-        self.saved = None
-        og, ob = _gout(grads, self.bn.weight), _gout(grads, self.bn.bias)
-        if pre is not None:
-            dz, dgamma, dbeta = vh.bn_bwd_from_stats(pre, dy, self.bn.weight.detach(), dgamma=og, dbeta=ob)
-        else:
-            dz, dgamma, dbeta = vh.bn_train_bwd_relu(dy, mask[0], mask[1], z, self.bn.weight.detach(), mean, invstd, dgamma=og, dbeta=ob)
-        grads[self.bn.weight] = dgamma
-        grads[self.bn.bias] = dbeta
+        (tape, o, col), self.saved = self.saved, None
+        x = tape.x
+        dz, _ = _bn_backward(self.bn, tape, dy, grads, pre)
         wt = self.conv.weight.detach()
         gpad = (self.offc + 31) // 32 * 32                  # the offset conv's output gradient, zero behind its channels (as the 17-joint head's)
         dxd, d_off, _, dw = columns_backward(dz, col, vh.deform_gemm_weight(wt), x, o, self.mask, wt, self.stride, self.dg, grad_channels=gpad,
@@ -428,21 +446,7 @@ class _DeformConvBN:
         grads[self.conv.weight] = dw
         grads[self.off.bias] = vh.col_sum(d_off)[:self.offc].contiguous()
         grads[self.off.weight] = vh.conv2d_wgrad(x, d_off, self.offc, self.cin, 3, 3, self.stride, 1, out=_gout(grads, self.off.weight))
-        ow = self.off.weight.detach()
-        n, h, w, cin = x.shape
-        ho, wo = d_off.shape[1], d_off.shape[2]
-        if self.stride == 1:
-            wd = vh.pack_dgrad_weight(ow, _flipped_taps(3, 3), cout_k=gpad)
-            return vh.conv2d_fwd_ex(d_off, wd, cin, 3, 3, 1, 1, 1, h, w, h, w, 1, 1, 0, 0, residual=dxd), None
-        assert h == 2 * ho and w == 2 * wo
-        dx = torch.empty((n, h, w, cin), device=x.device, dtype=torch.float32)
-        for py in (0, 1):                                 # input-pixel parity -> which filter rows reach it (as _ConvBN._dgrad)
-            rows = [1] if py == 0 else [2, 0]
-            for px in (0, 1):
-                cols = [1] if px == 0 else [2, 0]
-                wd = vh.pack_dgrad_weight(ow, [(a, b) for a in rows for b in cols], cout_k=gpad)
-                vh.conv2d_fwd_ex(d_off, wd, cin, len(rows), len(cols), 1, 0, 0, ho, wo, h, w, 2, 2, py, px, out=dx, residual=dxd)
-        return dx, None
+        return _igemm_dgrad(d_off, self.off.weight.detach(), x.shape, 3, 3, self.stride, 1, residual=dxd, cout_k=gpad), None
 
 
 def _conv2_of(blk):
@@ -457,35 +461,20 @@ class _DeconvBN:
         self.cin, self.cout = dc.weight.shape[:2]
 
     def forward(self, x):
-        bn = self.bn
         if _WINOGRAD and self.cin % 16 == 0 and self.cout % 4 == 0:      # four 2x2 phase convolutions as Winograd F(3x3, 2x2)
-            z, mean, invstd, scale, bias = vh.deconv4x4s2_winograd_fwd_bnstats(x, vh.pack_winograd_deconv_weight(self.dc.weight.detach()), self.cout,
-                                                                               bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                                                                               bn.momentum, bn.eps)
+            stats = vh.deconv4x4s2_winograd_fwd_bnstats(x, vh.pack_winograd_deconv_weight(self.dc.weight.detach()), self.cout, *_bn_args(self.bn))
         else:
-            z, mean, invstd, scale, bias = vh.deconv4x4s2_fwd_bnstats(x, vh.pack_deconv_weight(self.dc.weight.detach()), self.cout, bn.weight.detach(),
-                                                                      bn.bias.detach(), bn.running_mean, bn.running_var, bn.momentum, bn.eps)
-        _count_batch(bn)
-        y = _tap(vh.scale_bias_act(z, scale, bias, None, True))
-        self.saved = (x, z, scale, bias, mean, invstd)
+            stats = vh.deconv4x4s2_fwd_bnstats(x, vh.pack_deconv_weight(self.dc.weight.detach()), self.cout, *_bn_args(self.bn))
+        y, self.saved = _bn_forward(self.bn, x, stats)
         return y
 
     def bn_spec(self):
-        if not _FUSE_BN_BWD or self.cout < _FUSE_BN_MIN_C:
-            return None
-        x, z, scale, bias, mean, invstd = self.saved
-        return vh.BnBwdSpec(z, mean, invstd, scale=scale, bias=bias)
+        return _bn_spec(self.cout, self.saved)
 
     def backward(self, dy, grads, pre=None, consumer=None):
-        x, z, scale, bias, mean, invstd = self.saved
-        self.saved = None
-        if pre is not None:
-            dz, dgamma, dbeta = vh.bn_bwd_from_stats(pre, dy, self.bn.weight.detach(), dgamma=_gout(grads, self.bn.weight), dbeta=_gout(grads, self.bn.bias))
-        else:
-            dz, dgamma, dbeta = vh.bn_train_bwd_relu(dy, scale, bias, z, self.bn.weight.detach(), mean, invstd,
-                                                     dgamma=_gout(grads, self.bn.weight), dbeta=_gout(grads, self.bn.bias))
-        grads[self.bn.weight] = dgamma
-        grads[self.bn.bias] = dbeta
+        tape, self.saved = self.saved, None
+        x = tape.x
+        dz, _ = _bn_backward(self.bn, tape, dy, grads, pre)
         ow = _gout(grads, self.dc.weight)
         if _WINOGRAD and min(self.cin, self.cout) >= _WINOGRAD_WGRAD_MIN_C and _wino_wgrad_fits(x.shape, 3):      # transform-domain weight gradient (1.04 - 1.16x at B = 120)
             grads[self.dc.weight] = _side.run(lambda: vh.deconv4x4s2_winograd_wgrad(x, dz, out=ow), x, dz)
@@ -567,11 +556,7 @@ class _HeadT:
         dy = vh.nchw_to_nhwc(dout_nchw.contiguous(), 32)                         # 17 -> 32 channels (zeros)
         grads[self.conv.bias] = vh.col_sum(dy)[:self.cout].contiguous()
         grads[self.conv.weight] = vh.conv2d_wgrad(x, dy, self.cout, self.cin, k, k, 1, p, out=_gout(grads, self.conv.weight))
-        wd = vh.pack_dgrad_weight(self.conv.weight.detach(), _flipped_taps(k, k), cout_k=32)
-        n, h, w, _ = x.shape
-        if consumer is not None:
-            return vh.conv2d_fwd_ex_bnbwd(dy, wd, self.cin, k, k, 1, p, p, h, w, h, w, 1, 1, 0, 0, consumer)
-        return vh.conv2d_fwd_ex(dy, wd, self.cin, k, k, 1, p, p, h, w, h, w, 1, 1, 0, 0)
+        return _igemm_dgrad(dy, self.conv.weight.detach(), x.shape, k, k, 1, p, spec=consumer, cout_k=32)     # (pads k - 1 - p = p: k is odd)
 
 
 class SimplePoseTrainer:
@@ -640,8 +625,8 @@ class _LinearT:
         ow = _gout(grads, self.lin.weight)
         grads[self.lin.weight] = vh.conv2d_wgrad(x2d.reshape(b, 1, 1, self.ci), dy.reshape(b, 1, 1, self.co), self.co, self.ci, 1, 1, 1, 0,
                                                  out=None if ow is None else ow.view(self.co, self.ci, 1, 1)).reshape(self.co, self.ci)
-        wd = vh.pack_dgrad_weight(self.lin.weight.detach().reshape(self.co, self.ci, 1, 1), [(0, 0)])
-        return vh.conv2d_fwd_ex(dy.reshape(b, 1, 1, self.co), wd, self.ci, 1, 1, 1, 0, 0, 1, 1, 1, 1, 1, 1, 0, 0).reshape(b, self.ci)
+        w4 = self.lin.weight.detach().reshape(self.co, self.ci, 1, 1)
+        return _igemm_dgrad(dy.reshape(b, 1, 1, self.co), w4, (b, 1, 1, self.ci), 1, 1, 1, 0).reshape(b, self.ci)
 
 
 class _SEBottleneckT:
