@@ -772,6 +772,12 @@ int vatl_rmsprop_step_multi(const int64_t* table_dev, int n_tensors, int64_t tot
 int vatl_sgd_step(float* p, const float* g, float* buf, int64_t n, double lr, double momentum, double weight_decay, int step,
                   void* stream);
 
+/* The same for a list of tensors at one step count in one launch: the table layout of vatl_adamw_step_multi, the m column holds
+ * buf, the v column is unused (may be 0).  Any element count; base pointers need only be 4-byte aligned.  The same bits per element
+ * as vatl_sgd_step, in both of its forms (opt_update<OPT_SGD_FIRST> at step 1, opt_update<OPT_SGD> after). */
+int vatl_sgd_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double momentum, double weight_decay,
+                        int step, void* stream);
+
 /* compute_OKS (al_metric.py:42-69; called per item at ActiveLearning.py:309): object key-point similarity of the decoded
  * key-points pred (N,17,3) fp32 against ground truth gt (N,51) float64 with the annotation box (N,4) xywh float64 as the
  * object scale; invisible-everywhere items fall back to the distance from the doubled box.  out (N) float64. */

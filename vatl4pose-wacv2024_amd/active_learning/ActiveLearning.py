@@ -79,6 +79,17 @@ def retrain_precision(cfg):
     return name
 
 
+def retrain_graph(cfg):
+    """``cfg.RETRAIN.GRAPH`` -> False (the default, and what an absent key means: ``retrain_model``'s eager step, untouched), True (every
+    single-chunk step through ``hip_train_graph.graphed_step_for``: captured once per batch shape, then replayed) or "auto" (graphed
+    where a replay was measured to win: ``hip_train_graph.auto_max_crops`` — HRNet chunks of at most ``AUTO_MAX_CROPS`` crops).  Anything else is a
+    ValueError."""
+    mode = cfg.RETRAIN.get("GRAPH", False) if "RETRAIN" in cfg else False
+    if not (isinstance(mode, bool) or mode == "auto"):
+        raise ValueError(f"RETRAIN.GRAPH must be true, false or 'auto', got {mode!r}")
+    return mode
+
+
 def _collective(fn):
     """Public entry points run on every rank in lock-step.  On the driver process that owns worker processes, the outermost
     call is announced to them first (active_learning/worker.py); under torchrun every rank calls the method itself."""
@@ -128,6 +139,7 @@ class ActiveLearning:
         self.precision = cfg.VAL.get("PRECISION", "fp32")             # of the evaluation pass's forwards only (_heatmaps)
         self.precision_dtype = precision_dtype(self.precision)
         self.retrain_precision = retrain_precision(cfg)               # of retrain_model's trainer only
+        self.retrain_graph_mode = retrain_graph(cfg)                  # of retrain_model's step only: eager (False), graphed (True), "auto"
         self.finish_margin = 0.05
         # one process per GPU: join the torchrun group, or (plain single process, opt.num_gpu > 1) start the worker ranks
         self._depth = 0
@@ -847,6 +859,13 @@ class ActiveLearning:
         else:
             trainer = hip_train.trainer_for(self.model)
         arena = hip_train.arena_for(self.model)
+        step, graph_max, before = None, 0, None
+        if self.retrain_graph_mode:                            # opt-in (cfg.RETRAIN.GRAPH): one captured graph per batch shape, replayed
+            from alphapose.models import hip_train_graph
+            step = hip_train_graph.graphed_step_for(self.model, self.retrain_precision)
+            graph_max = hip_train_graph.auto_max_crops(self.model, self.retrain_precision) if self.retrain_graph_mode == "auto" else None
+            before, n_reasons = dict(step.stats), len(step.reasons)
+            kept_eager = []                                    # why the loop below kept a step for itself, one entry per step
         # the per-step loss / accuracy read-backs wait until the EPOCH's steps are enqueued: read inside the loop they drain the stream every step, and the host's
         # preparation of the next mini-batch (crops, targets) then runs behind the step instead of beside it.  Flushed once per epoch (one synchronisation, before
         # the scheduler step): the host never runs more than an epoch ahead of the device, a kernel error surfaces in the epoch that produced it (a NaN loss reaches the logger of that epoch), and the
@@ -872,6 +891,14 @@ class ActiveLearning:
                 for k, (lo, hi) in enumerate(mine):
                     x = vh.upload(inps[lo:hi, 0], self.device, torch.float32).contiguous()
                     lab, msk = vh.upload(labels[lo:hi], self.device, torch.float32).contiguous(), vh.upload(label_masks[lo:hi], self.device, torch.float32)
+                    if step is not None and len(mine) == 1 and (graph_max is None or hi - lo <= graph_max):
+                        out, loss = step(x, lab, msk, scale=(hi - lo) / nb)            # the same five lines: eager, captured or replayed
+                        m = msk.reshape(msk.shape[0], -1, 1, 1)
+                        pending.append((loss, calc_accuracy_begin(out * m, lab * m), hi - lo))
+                        continue
+                    if step is not None:
+                        kept_eager.append("eager:more than one DataParallel chunk on this rank" if len(mine) > 1 else
+                                          (f"eager:auto: more than {graph_max} crops" if graph_max else "eager:auto: no measured win for this network"))
                     with torch.no_grad():
                         out = trainer.forward(x)
                         loss, dout = vh.masked_mse_fwd_bwd(out, lab, msk)              # 0.5 * MSE(out*m, label*m) and its gradient
@@ -896,6 +923,10 @@ class ActiveLearning:
             self.scheduler.step()
         D.broadcast_buffers_(self.model)           # BN statistics are per rank; rank 0's survive (DataParallel semantics)
         self.last_train_loss, self.last_train_acc = self._global_avg(loss_logger), self._global_avg(acc_logger)
+        if step is not None:                       # what this round's steps did (hip_train_graph.GraphedStep.stats)
+            self.retrain_graph = {k: step.stats[k] - before[k] for k in ("replayed", "eager", "captured")}
+            self.retrain_graph["eager"] += len(kept_eager)
+            self.retrain_graph["reasons"] = list(step.reasons[n_reasons:]) + sorted(set(kept_eager))
         if "WPU" in self.uncertainty:              # ActiveLearning.py:680-684: a fresh AE is fine-tuned on the labeled poses
             self.AE = self.initialize_AE()
             self.last_ae_loss = self.retrain_AE()

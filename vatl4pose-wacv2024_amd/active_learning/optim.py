@@ -4,7 +4,7 @@
 three groups with lr x{10, 1, 5}); ``step()`` is one ``vatl_adamw_step_multi`` launch per parameter group
 (a device table of tensor pointers) instead of torch's element-wise kernels.  ``lr`` is read from the group at every step, so
 ``torch.optim.lr_scheduler.ExponentialLR`` works on it unchanged.  ``Adam`` and ``RMSprop`` (the two optimisers of the pose-network
-pre-training script, posetrack_train.py:155-158) step the same way: one launch per (group, step).
+pre-training script, posetrack_train.py:155-158) and ``SGD`` step the same way: one launch per (group, step).
 """
 from __future__ import annotations
 
@@ -97,9 +97,10 @@ class RMSprop(_Stepper):
 
 
 class SGD(_Stepper):
-    """torch.optim.SGD with momentum as the reference configures it (ActiveLearning.py:220-221); one launch per tensor."""
+    """torch.optim.SGD with momentum as the reference configures it (ActiveLearning.py:220-221)."""
     _buffers = ("momentum_buffer",)
     _kernel = staticmethod(vh.sgd_step)
+    _multi = staticmethod(vh.sgd_step_multi)       # one launch per (group, step count) instead of 878 for HRNet-W32
 
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
         if lr < 0 or momentum < 0 or weight_decay < 0:

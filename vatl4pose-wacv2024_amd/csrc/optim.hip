@@ -1,7 +1,7 @@
 // Element-wise optimiser steps, pure HBM streams: one update function, one span walker, two kernels.
 //   vatl_adamw_step / _multi    torch.optim.AdamW (decoupled weight decay)            ActiveLearning.py:224-228, :673
 //   vatl_adam_step / _multi     torch.optim.Adam (L2 decay folded into the gradient)  ActiveLearning.py:222-223, posetrack_train.py:155-156
-//   vatl_sgd_step               torch.optim.SGD (momentum, dampening 0, no Nesterov)  ActiveLearning.py:220-221
+//   vatl_sgd_step / _multi      torch.optim.SGD (momentum, dampening 0, no Nesterov)  ActiveLearning.py:220-221
 //   vatl_rmsprop_step / _multi  torch.optim.RMSprop (momentum 0, not centered)        posetrack_train.py:157-158
 // A flat call takes one span; a multi call takes a device table with rows of {p, g, m, v, numel, first_block} (all int64), one launch
 // per parameter group instead of one per tensor (161 tensors for SimplePose-R50).  Either way a block updates kOptBlock (common.h,
@@ -177,6 +177,10 @@ static OptScalars adam_scalars(double lr, double beta1, double beta2, double eps
                       (float)eps, (float)(lr / bc1), decoupled ? (float)(1.0 - lr * weight_decay) : 1.f};
 }
 
+static OptScalars sgd_scalars(double lr, double momentum, double weight_decay) {
+    return OptScalars{(float)weight_decay, 0.f, (float)momentum, 0.f, 1.f, 0.f, (float)lr, 1.f};
+}
+
 static OptScalars rmsprop_scalars(double lr, double alpha, double eps, double weight_decay) {
     return OptScalars{(float)weight_decay, 0.f, (float)alpha, (float)(1.0 - alpha), 1.f, (float)eps, (float)lr, 1.f};
 }
@@ -223,9 +227,17 @@ extern "C" int vatl_sgd_step(float* p, const float* g, float* buf, int64_t n, do
     if (step < 1) return fail(VATL_EINVAL, "sgd_step: step is 1-based");
     if (n <= 0) return 0;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) return fail(VATL_EINVAL, "sgd_step: spans must be 16-byte aligned");
-    const OptScalars s{(float)weight_decay, 0.f, (float)momentum, 0.f, 1.f, 0.f, (float)lr, 1.f};
+    const OptScalars s = sgd_scalars(lr, momentum, weight_decay);
     if (step == 1) return launch_flat<OPT_SGD_FIRST>("sgd_step", p, g, buf, nullptr, n, s, stream);
     return launch_flat<OPT_SGD>("sgd_step", p, g, buf, nullptr, n, s, stream);
+}
+
+// Rows of {p, g, buf, 0, numel, first_block}; every tensor of a call is at the same step, so one call is one form.
+extern "C" int vatl_sgd_step_multi(const int64_t* table_dev, int n_tensors, int64_t total_blocks, double lr, double momentum, double weight_decay,
+                                   int step, void* stream) {
+    const OptScalars s = sgd_scalars(lr, momentum, weight_decay);
+    if (step == 1) return launch_multi<OPT_SGD_FIRST>("sgd_step_multi", table_dev, n_tensors, total_blocks, step, s, stream);
+    return launch_multi<OPT_SGD>("sgd_step_multi", table_dev, n_tensors, total_blocks, step, s, stream);
 }
 
 extern "C" int vatl_rmsprop_step(float* p, const float* g, float* sq, int64_t n, double lr, double alpha, double eps, double weight_decay,

@@ -201,6 +201,7 @@ SIGNATURES = {
     "vatl_rmsprop_step": (_i, [_p, _p, _p, _i64, _d, _d, _d, _d, _p]),
     "vatl_rmsprop_step_multi": (_i, [_p, _i, _i64, _d, _d, _d, _d, _p]),
     "vatl_sgd_step": (_i, [_p, _p, _p, _i64, _d, _d, _d, _i, _p]),
+    "vatl_sgd_step_multi": (_i, [_p, _i, _i64, _d, _d, _d, _i, _p]),
     "vatl_pack_conv_weight_f64": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "vatl_pack_deconv4x4s2_weight_f64": (_i, [_p, _p, _i, _i, _p]),
     "vatl_conv2d_fwd_f64": (_i, [_p] * 6 + [_i] * 11 + [_p]),
@@ -2299,14 +2300,16 @@ _opt_tables = {}                                     # (device, pointers...) -> 
 
 
 def _multi_table(what, params, grads, ms, vs):
-    """The device table of a multi-tensor optimiser launch: rows of {p, g, m, v, numel, first_block} (``ms`` None: the m column is 0)."""
+    """The device table of a multi-tensor optimiser launch: rows of {p, g, m, v, numel, first_block} (``ms`` / ``vs`` None: that
+    column is 0)."""
     key = [params[0].device.index]
-    for k, (p_, g_, v_) in enumerate(zip(params, grads, vs)):
+    for k, (p_, g_) in enumerate(zip(params, grads)):
         m_ = ms[k] if ms is not None else None
-        for t in (p_, g_, v_) + (() if m_ is None else (m_,)):
+        v_ = vs[k] if vs is not None else None
+        for t in (p_, g_) + (() if v_ is None else (v_,)) + (() if m_ is None else (m_,)):
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                 raise VatlError(f"{what} needs contiguous fp32 device tensors")
-        key += [p_.data_ptr(), g_.data_ptr(), 0 if m_ is None else m_.data_ptr(), v_.data_ptr(), p_.numel()]
+        key += [p_.data_ptr(), g_.data_ptr(), 0 if m_ is None else m_.data_ptr(), 0 if v_ is None else v_.data_ptr(), p_.numel()]
     key = tuple(key)
     hit = _opt_tables.get(key)
     if hit is None:                                  # built and uploaded once per (group, storage): no per-step host-to-device copy
@@ -2357,6 +2360,11 @@ def adam_step(p, g, m, v, step: int, lr: float, weight_decay: float = 0.0, betas
 
 def sgd_step(p, g, buf, step: int, lr: float, momentum: float = 0.9, weight_decay: float = 0.0):
     _check(lib().vatl_sgd_step(_ptr(p), _ptr(g), _ptr(buf), p.numel(), lr, momentum, weight_decay, step, _stream()), "vatl_sgd_step")
+
+
+def sgd_step_multi(params, grads, bufs, step: int, lr: float, momentum: float = 0.9, weight_decay: float = 0.0):
+    """``sgd_step`` for a list of tensors at one step count in one launch; the same bits as the per-tensor calls."""
+    _step_multi("sgd_step_multi", params, grads, bufs, None, lr, momentum, weight_decay, step)
 
 
 def adamw_step(p, g, m, v, step: int, lr: float, weight_decay: float, betas=(0.9, 0.999), eps: float = 1e-8):
