@@ -287,6 +287,16 @@ int vatl_upsample_nearest_bwd(const float* dy, const float* yact_or_null, float*
 /* Backward of AdaptiveAvgPool2d(1) (simplepose.py:88-91, SE_module.py:21): dx[n][p][c] = dy[n][c] / HW. */
 int vatl_gap_bwd(const float* dy, float* dx, int N, int HW, int C, void* stream);
 
+/* Flip testing (csrc/flip.hip).  The mirror image of fp32 NCHW crops, rows = N*C*H: y[r][w] = x[r][W-1-w], the reference's
+ * flip (transforms.py:479-483).  Out of place: x == y is refused.  A move of 32-bit words (NaN payloads survive). */
+int vatl_flip_nchw(const float* x, float* y, int64_t rows, int W, void* stream);
+/* ... and the merge of the mirrored pass, in place on hm (N,J,H,W) fp32 NCHW:
+ *   hm[n][j][y][x] = (hm[n][j][y][x] + hm_flip[n][src_joint[j]][y][sx(x)]) / 2,   sx(x) = W-1-x, or with shift = 1: sx(0) = W-1, sx(x) = W-x
+ * = (hms + flip_heatmap(hms_flip, joint_pairs, shift)) / 2 of transforms.py:486-518, :550-552 with the reference's bits (the sum is
+ * rounded once, the halving is exact).  src_joint: J device int32 in [0, J), the joint each output joint takes from the mirrored
+ * maps (the pairs' swaps composed in list order; the caller guarantees the range).  hm_flip must not overlap hm. */
+int vatl_flip_merge(float* hm, const float* hm_flip, const int* src_joint, int N, int J, int H, int W, int shift, void* stream);
+
 /* ------------------------------------------------------------------------ *
  * Scorers on heat-maps (N,J,H,W) fp32 NCHW, one pass over HBM each
  * ------------------------------------------------------------------------ */

@@ -4,6 +4,13 @@ SimpleBaseline-R50 -> decode / THC / WPU / local-peak -> query, through ActiveLe
 
     python tools/al_eval_bench.py [--items 1024] [--batch 256] [--rounds 3]
 Prints items/s of eval_and_query (wall clock, everything included) next to bench.py's device-resident figure.
+
+    python tools/al_eval_bench.py --flip-test [--items 1024] [--repeats 5]
+What cfg.VAL.FLIP_TEST costs: two ActiveLearning objects built from the same seed, the key off and on, in one process; after a warm-up
+round each they take turns for --repeats timed rounds (off, on, off, on, ...), so both see the same box at the same time.  One JSON line
+per leg (every round's seconds, items/s of the median round, the spread), one with the ratio, and one per flip kernel launched alone at
+--items x 17 x 64 x 48 maps / --items x 3 x 256 x 192 crops, timed with device events, as GB/s of the bytes the formula needs (merge: two
+maps read, one written; mirror: one tensor read, one written).
 """
 import argparse
 import json
@@ -36,6 +43,8 @@ def main():
     ap.add_argument("--gc-freeze", action="store_true", help="opt.gc_freeze = True (the constructor freezes what it built; round 5's default)")
     ap.add_argument("--gc-log", action="store_true", help="print every pass of the cyclic collector (generation, ms, collected) with the round it fell into")
     ap.add_argument("--cprofile", action="store_true", help="cProfile the rounds after the first and print the 30 most expensive functions (own time)")
+    ap.add_argument("--flip-test", action="store_true", help="measure eval_and_query with cfg.VAL.FLIP_TEST off and on, taking turns, and the two flip kernels alone")
+    ap.add_argument("--repeats", type=int, default=5, help="timed rounds per leg of --flip-test")
     a = ap.parse_args()
     from active_learning import ActiveLearning
     from alphapose.datasets import FrameVideo
@@ -57,6 +66,8 @@ def main():
         opt = types.SimpleNamespace(work_dir=wd, uncertainty=a.uncertainty, representativeness=a.representativeness, filter=a.filter, strategy=a.uncertainty, video_id="syn",
                                     get_prenext=True, from_scratch=True, continual=True, num_gpu=1, onebyone=False, retrain_thresh=1, THCvsWPU="const",
                                     device_batches=not a.loader, gc_freeze=a.gc_freeze)
+        if a.flip_test:
+            return flip_test_legs(a, cfg, opt, ev, tr)
         torch.manual_seed(0); np.random.seed(0)
         al = ActiveLearning(cfg, opt, eval_dataset=ev, train_dataset=tr)
         times = []
@@ -110,6 +121,67 @@ def main():
         print(json.dumps({"metric": "ActiveLearning.eval_and_query on decoded frames (wall clock)", "items": len(ev), "batch": a.batch,
                           "seconds": [round(t, 3) for t in times], "items_per_s": round(len(ev) / min(times), 1),
                           "sustained_items_per_s": round(len(ev) * (len(times) - 1) / sum(times[1:]), 1) if len(times) > 1 else None}))
+
+
+def flip_test_legs(a, cfg, opt, ev, tr):
+    import copy
+    import statistics
+
+    import vatl_hip as vh
+    from active_learning import ActiveLearning
+    legs = {}
+    for key in (False, True):
+        c = copy.deepcopy(cfg)
+        c.VAL["FLIP_TEST"] = key
+        torch.manual_seed(0); np.random.seed(0)
+        legs[key] = ActiveLearning(c, opt, eval_dataset=ev, train_dataset=tr)
+    times = {False: [], True: []}
+
+    def one_round(al):
+        al.unlabeled_id = list(range(len(ev))); al.labeled_id = []
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        al.eval_and_query()
+        al.flush_records()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    for key in (False, True):                                                  # warm-up: code objects, plans, the allocator's pools
+        one_round(legs[key])
+    for _ in range(a.repeats):
+        for key in (False, True):
+            times[key].append(one_round(legs[key]))
+    rate = {}
+    for key in (False, True):
+        t = times[key]
+        rate[key] = len(ev) / statistics.median(t)
+        print(json.dumps({"metric": "ActiveLearning.eval_and_query on decoded frames (wall clock, records flushed), legs taking turns", "flip_test": key, "items": len(ev),
+                          "batch": a.batch, "seconds": [round(x, 4) for x in t], "items_per_s_median": round(rate[key], 1),
+                          "items_per_s_min_max": [round(len(ev) / max(t), 1), round(len(ev) / min(t), 1)]}), flush=True)
+    print(json.dumps({"metric": "eval_and_query items/s, VAL.FLIP_TEST on / off (medians)", "ratio": round(rate[True] / rate[False], 3)}), flush=True)
+
+    dev = legs[True].device
+    n = a.items
+    hm, fl = (torch.randn((n, 17, 64, 48), device=dev) for _ in range(2))
+    x = torch.randn((n, 3, 256, 192), device=dev)
+    y = torch.empty_like(x)
+    pairs = ev.joint_pairs
+
+    def alone(name, fn, nbytes, iters=20):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(); e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / iters
+        print(json.dumps({"metric": f"{name} alone (device events, {iters} launches back to back)", "shape": list(hm.shape if "merge" in name else x.shape),
+                          "us": round(ms * 1e3, 1), "algorithmic_bytes": nbytes, "GB_per_s": round(nbytes / ms / 1e6, 1)}), flush=True)
+    alone("vatl_flip_merge shift=1", lambda: vh.flip_merge(hm, fl, pairs, True), 3 * hm.numel() * 4)
+    alone("vatl_flip_merge shift=0", lambda: vh.flip_merge(hm, fl, pairs, False), 3 * hm.numel() * 4)
+    alone("vatl_flip_nchw", lambda: vh.flip_nchw(x, out=y), 2 * x.numel() * 4)
+    for al in legs.values():
+        al.close()
 
 
 if __name__ == "__main__":

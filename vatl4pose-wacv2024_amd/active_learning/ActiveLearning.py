@@ -90,6 +90,25 @@ def retrain_graph(cfg):
     return mode
 
 
+def flip_test(cfg, override=None):
+    """``cfg.VAL.FLIP_TEST`` -> False (the default, and what an absent key means: one forward per crop, the bits of every shipped yaml) or
+    True: the evaluation pass also runs the mirrored crops and averages the two heat-maps before decoding, as AlphaPose's validation does
+    (``alphapose.models.hip_engine_flip``; ``flip_heatmap(..., shift=True)`` with the evaluation data set's ``joint_pairs``).  Anything but a
+    bool is a ValueError.  ``override`` (``alphapose.pretrain``'s ``--flip-test`` flag) stands in for the key.  The averaging of MAPS is the
+    ``heatmap_to_coord_simple`` decoder's: with another decoder the reference averages decoded coordinates
+    (``heatmap_to_coord_simple_regress``), which this path does not do — a NotImplementedError naming the decoder."""
+    on = override if override is not None else (cfg.VAL.get("FLIP_TEST", False) if "VAL" in cfg else False)
+    if not isinstance(on, bool):
+        raise ValueError(f"VAL.FLIP_TEST must be true or false, got {on!r}")
+    if on:
+        from alphapose.utils.transforms import heatmap_to_coord_simple
+        decoder = get_func_heatmap_to_coord(cfg)
+        if decoder is not heatmap_to_coord_simple:
+            name = getattr(decoder, "__name__", None) or "[" + ", ".join(d.__name__ for d in decoder) + "]"
+            raise NotImplementedError(f"VAL.FLIP_TEST averages heat-maps, which is what heatmap_to_coord_simple decodes; this config decodes with {name}")
+    return on
+
+
 def _collective(fn):
     """Public entry points run on every rank in lock-step.  On the driver process that owns worker processes, the outermost
     call is announced to them first (active_learning/worker.py); under torchrun every rank calls the method itself."""
@@ -140,6 +159,7 @@ class ActiveLearning:
         self.precision_dtype = precision_dtype(self.precision)
         self.retrain_precision = retrain_precision(cfg)               # of retrain_model's trainer only
         self.retrain_graph_mode = retrain_graph(cfg)                  # of retrain_model's step only: eager (False), graphed (True), "auto"
+        self.flip_test = flip_test(cfg)                               # of the evaluation pass's forwards only (_heatmaps)
         self.finish_margin = 0.05
         # one process per GPU: join the torchrun group, or (plain single process, opt.num_gpu > 1) start the worker ranks
         self._depth = 0
@@ -294,16 +314,26 @@ class ActiveLearning:
         dt = self.precision_dtype
         if dt is not None:                            # cfg.VAL.PRECISION = fp16 / bf16: the same three calls on the 16-bit route
             from alphapose.models import hip_engine_h16
+        if self.flip_test:                            # cfg.VAL.FLIP_TEST: the same three calls, each followed by its mirrored pass and the merge
+            from alphapose.models import hip_engine_flip
+            pairs = self.eval_dataset.joint_pairs
+
+            def flipped(t, buf, emb=None):            # shift=True as in AlphaPose's validation
+                return hip_engine_flip.flip_forward_into(m, t, buf, pairs, shift=True, emb=emb, dtype=dt)
 
         def heatmaps(t):
             # the stream entry point, not `m(t)`: a crop's bits must not depend on the size of the loader batch or of the shard
             # it arrives in (a short last batch would otherwise take the small-batch split-K route of the module call)
             t = t.to(self.device)
             buf = torch.empty((t.shape[0], self.cfg.DATA_PRESET.NUM_JOINTS, *self.hm_size), device=self.device)
+            if self.flip_test:
+                return flipped(t, buf)
             return hip_engine.forward_into(m, t, buf) if dt is None else hip_engine_h16.forward_h16(m, t, buf, dtype=dt)
         with torch.no_grad():
             cur = out if out is not None else torch.empty((x.shape[0], self.cfg.DATA_PRESET.NUM_JOINTS, *self.hm_size), device=self.device)
-            if emb_out is not None:                   # heat-maps and get_embedding from one trunk pass
+            if self.flip_test:
+                flipped(x, cur, emb_out)
+            elif emb_out is not None:                 # heat-maps and get_embedding from one trunk pass
                 if dt is None:
                     hip_engine.forward_with_embedding(m, x, cur, emb_out)
                 else:
@@ -462,6 +492,8 @@ class ActiveLearning:
         res_ann = res if (evaluate or not tp.get("res_ann")) else dict(tp["res_ann"], mOKS=fallback["mOKS"])
         if self.precision_dtype is not None:                       # a 16-bit evaluation pass says so in its round's entry; fp32 entries are as they always were
             res, res_ann = (dict(r, precision=self.precision) if isinstance(r, dict) else r for r in (res, res_ann))
+        if self.flip_test:                                         # ... and so does a flip-tested one
+            res, res_ann = (dict(r, flip_test=True) if isinstance(r, dict) else r for r in (res, res_ann))
         self.percentage.append(len(self.labeled_id) / n * 100)
         self.performance.append(res)
         self.performance_ann.append(res_ann)

@@ -2,7 +2,7 @@
 jrdbpose_train.py) does through ``alphapose.opt``, ``DataParallel``, autograd and ``torch.optim``.
 
     python -m alphapose.pretrain --cfg <yaml> --exp-id <id> [--snapshot 2] [--seed 0] [--workers 8] [--max-epochs N] [--validate-only CKPT]
-                                 [--precision {fp32,bf16}]
+                                 [--precision {fp32,bf16}] [--flip-test]
 
 writes ``./exp/<exp-id>-<FILE_NAME>/`` with ``training.log``, ``model_<epoch>.pth``, ``model_best.pth``, ``final.pth`` and
 ``predicted_kpt.json`` — the files ``MODEL.PRETRAINED`` of the active-learning yamls names.
@@ -46,6 +46,10 @@ Deliberately different:
   step).  Only the trainer changes: the loss, the optimiser, the checkpoints (fp32 master weights) and the validation pass (the fp32
   engine; ``VAL.PRECISION`` is not read here) are the same.  Anything else — ``fp16`` would need loss scaling — is a ``ValueError``
   and ``bf16`` with another ``MODEL.TYPE`` a ``NotImplementedError``, both raised before a data set is built or the device is touched.
+* ``VAL.FLIP_TEST`` (absent = ``false``; ``--flip-test`` switches it on) makes the validation pass run the mirrored crops as well and
+  average the two heat-maps before the decode, as the reference's ``validate_gt`` does under its ``--flip-test``
+  (``active_learning.ActiveLearning.flip_test``: the same key, function and refusals as the active-learning rounds).  The training step is
+  untouched.
 """
 from __future__ import annotations
 
@@ -84,6 +88,7 @@ def parse_args(argv=None):
     parser.add_argument("--max-epochs", default=None, type=int, help="stop after this many epochs of this run")
     parser.add_argument("--validate-only", default=None, type=str, metavar="CKPT", help="load CKPT (strict), validate, write predicted_kpt.json")
     parser.add_argument("--precision", default=None, choices=PRECISIONS, help="trainer of the training step; overrides the yaml's TRAIN.PRECISION (absent: fp32)")
+    parser.add_argument("--flip-test", default=False, action="store_true", help="validate with the mirrored pass merged in; switches the yaml's VAL.FLIP_TEST on (absent: off)")
     return parser.parse_args(argv)
 
 
@@ -301,10 +306,15 @@ def train_epoch(model, batches, optimizer, precision="fp32"):
     return loss_logger.avg, acc_logger.avg
 
 
-def validate(model, cfg, dataset, work_dir, batches=None):
+def validate(model, cfg, dataset, work_dir, batches=None, flip_test=None):
     """``validate_gt`` (:89-133) over ``dataset`` (or over ``batches``, any iterable of its batches) ->
-    {"metric", "val_metric", "records", "detail"}; writes ``<work_dir>/predicted_kpt.json``."""
+    {"metric", "val_metric", "records", "detail"}; writes ``<work_dir>/predicted_kpt.json``.  ``flip_test``: the ``--flip-test`` flag; None
+    reads ``cfg.VAL.FLIP_TEST`` (absent: off)."""
+    from active_learning.ActiveLearning import flip_test as val_flip_test
     from alphapose.models import hip_engine
+    flip = val_flip_test(cfg, flip_test)                      # refused before the device is touched
+    if flip:
+        from alphapose.models import hip_engine_flip
     from alphapose.utils.bbox import bbox_xyxy_to_xywh
     device = _device_of(model)
     eval_joints = list(dataset.EVAL_JOINTS)
@@ -320,7 +330,10 @@ def validate(model, cfg, dataset, work_dir, batches=None):
         x = vh.upload(inps[:, 0], device, torch.float32).contiguous()
         hm = torch.empty((x.shape[0], int(cfg.DATA_PRESET.NUM_JOINTS), *cfg.DATA_PRESET.HEATMAP_SIZE), device=device)
         with torch.no_grad():
-            hip_engine.forward_into(model, x, hm)
+            if flip:                                          # shift=True as in AlphaPose's validation
+                hip_engine_flip.flip_forward_into(model, x, hm, dataset.joint_pairs, shift=True)
+            else:
+                hip_engine.forward_into(model, x, hm)
         pred = hm[:, eval_joints].contiguous()
         bb = vh.upload(bboxes, device, torch.float32).contiguous()
         coords, maxv, _ = vh.decode(pred, bb)                 # heatmap_to_coord_simple's kernel, a batch at a time
@@ -414,6 +427,8 @@ def main(argv=None):
     opt = parse_args(argv)
     cfg = load_config(opt.cfg)
     precision = train_precision(cfg, opt.precision)           # refused here: before the device, the work dir and the data sets
+    from active_learning.ActiveLearning import flip_test
+    flip = flip_test(cfg, True if opt.flip_test else None)    # ... and so is a bad VAL.FLIP_TEST
     if not torch.cuda.is_available():
         raise vh.VatlError("the pose networks train on MI355X only (no CPU fallback)")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -433,7 +448,7 @@ def main(argv=None):
         if hasattr(val_set, "emit_neighbour_crops"):
             val_set.emit_neighbour_crops = False              # only inps[:, 0] is read
         if opt.validate_only:
-            res = validate(model, cfg, val_set, work_dir)
+            res = validate(model, cfg, val_set, work_dir, flip_test=flip)
             log(f"{opt.validate_only} validation, {res['val_metric']} {res['metric']}")
             return {"work_dir": work_dir, "val": [(None, res["metric"])], "val_metric": res["val_metric"], "ended": "validate_only"}
         optimizer = build_optimizer(cfg, model.parameters())
@@ -447,7 +462,7 @@ def main(argv=None):
         log(f"train items: {len(train_set)}, validation items: {len(val_set)}, decode-ahead threads: {pool.workers}")
         out = run_epochs(cfg, model, optimizer,
                          train_fn=lambda i: train_epoch(model, pool.batches(epoch_batches(len(train_set), batch_size, gen)), optimizer, precision),
-                         validate_fn=lambda i: validate(model, cfg, val_set, work_dir),
+                         validate_fn=lambda i: validate(model, cfg, val_set, work_dir, flip_test=flip),
                          work_dir=work_dir, snapshot=opt.snapshot, max_epochs=opt.max_epochs, log=log, precision=precision)
         log(f"run ended: {out['ended']}; best {out['val_metric']}: {out['best_score']} (epoch {out['best_epoch']})")
         out["model"] = model

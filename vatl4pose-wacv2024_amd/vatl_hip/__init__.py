@@ -82,6 +82,8 @@ SIGNATURES = {
     "vatl_fuse_upsample_add": (_i, [_p, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_upsample_nearest_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_gap_bwd": (_i, [_p, _p, _i, _i, _i, _p]),
+    "vatl_flip_nchw": (_i, [_p, _p, C.c_int64, _i, _p]),
+    "vatl_flip_merge": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vatl_decode_argmax_affine": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "vatl_decode_pose": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "vatl_thc_pairs": (_i, [_p, _p, _i64, _i64, _p, _i, _i, _i, _i, _p]),
@@ -1065,6 +1067,59 @@ def fuse_upsample_add(base, ups, relu: bool):
     _check(lib().vatl_fuse_upsample_add(_ptr(base), _ptr(a[0][0]), a[0][1], _ptr(a[1][0]), a[1][1], _ptr(a[2][0]), a[2][1], _ptr(y),
                                         n, h, w, c, int(relu), _stream()), "vatl_fuse_upsample_add")
     return y
+
+
+# ----------------------------------------------------------------------------
+# flip testing: mirrored crops, and the merge of the mirrored pass's heat-maps (csrc/flip.hip)
+# ----------------------------------------------------------------------------
+
+def flip_nchw(x: torch.Tensor, out=None) -> torch.Tensor:
+    """The mirror image of fp32 crops (..., W): out[..., w] = x[..., W-1-w], the reference's ``flip`` (transforms.py:479-483).  Out of place."""
+    if x.dim() < 1 or x.shape[-1] < 1:
+        raise VatlError(f"flip_nchw: no last axis to mirror in shape {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    elif out.shape != x.shape or out.device != x.device:
+        raise VatlError(f"flip_nchw: out {tuple(out.shape)} on {out.device} does not match x {tuple(x.shape)} on {x.device}")
+    w = x.shape[-1]
+    _check(lib().vatl_flip_nchw(_ptr(x), _ptr(out), x.numel() // w, w, _stream()), "vatl_flip_nchw")
+    return out
+
+
+def flip_src_joints(joint_pairs, j: int):
+    """The joint each output joint takes from the mirrored maps: the swaps of ``joint_pairs`` composed in list order, as the reference's
+    flip_heatmap applies them one after another to the current contents (a table that repeats joints gives a general permutation)."""
+    src = list(range(j))
+    for pair in joint_pairs:
+        a, b = (int(v) for v in pair)
+        if not (0 <= a < j and 0 <= b < j):
+            raise VatlError(f"flip_merge: joint pair ({a}, {b}) is outside [0, {j})")
+        src[a], src[b] = src[b], src[a]
+    return src
+
+
+_flip_tables = {}                                    # (pairs, J, device) -> int32 device table of flip_src_joints
+
+
+def _flip_table(joint_pairs, j: int, device):
+    key = (tuple((int(a), int(b)) for a, b in joint_pairs), j, device)
+    t = _flip_tables.get(key)
+    if t is None:
+        t = _flip_tables[key] = upload(torch.tensor(flip_src_joints(key[0], j), dtype=torch.int32), device)
+    return t
+
+
+def flip_merge(hm: torch.Tensor, hm_flip: torch.Tensor, joint_pairs, shift: bool = True) -> torch.Tensor:
+    """In place on hm (N,J,H,W): hm = (hm + flip_heatmap(hm_flip, joint_pairs, shift)) / 2 with the reference's bits (transforms.py:486-518,
+    :550-552); hm_flip, the heat-maps of the mirrored crops, is only read and must not overlap hm."""
+    if hm.dim() != 4 or hm_flip.shape != hm.shape or hm_flip.device != hm.device:
+        raise VatlError(f"flip_merge: hm {tuple(hm.shape)} on {hm.device} and hm_flip {tuple(hm_flip.shape)} on {hm_flip.device} must be equal (N,J,H,W) tensors")
+    n, j, h, w = hm.shape
+    if min(j, h, w) < 1:
+        raise VatlError(f"flip_merge: empty heat-maps {tuple(hm.shape)}")
+    a, b = _ptr(hm), _ptr(hm_flip)
+    _check(lib().vatl_flip_merge(a, b, _ptr(_flip_table(joint_pairs, j, hm.device), torch.int32), n, j, h, w, int(bool(shift)), _stream()), "vatl_flip_merge")
+    return hm
 
 
 # ----------------------------------------------------------------------------
